@@ -7,14 +7,19 @@ scanned against the whole resident subject store, qualifying rows appended on th
 more than one GPU takes part — the per-rank row lists gathered on rank 0 over RCCL.  The packed subject block and the
 packed query batch are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torch.distributed environment, this process only spawns
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` (before touching torch or the GPU), relays
 rank 0's JSON line and exits with the child's code; under torch.distributed.run it is one of the N ranks.
 
 Rank 0 prints ONE JSON line.  Scaling is weak: the store is replicated, every rank scans its own query shard
-of fixed size.  Besides the contract's fields the line carries (N = 1 only, all outside the timed region):
+of fixed size.  A plain run does only what the headline needs: it builds the workload, warms up, times K steps, writes
+the rows of the last timed step under DIR if --dump-outputs is given (dump_outputs) and prints the line; its `roofline`
+block is the timed launches' own HIP-event time against the committed counter record.  --full adds, after the timed
+steps, the result checks (`verified`, `checks`: distances recomputed, planted rows present, prefilter on/off rows
+identical, an oracle sample), the full record (--full-record, default bench_out/bench_full.json) and the side legs below
+(N = 1 only, all outside the timed region; the --no-* flags leave legs out of a --full run):
 
   roofline           dominant kernel of the timed launch, live HIP-event time; VALU-bound: frac = VALU lane-ops/s over the
                      chip's nominal issue peak, instruction count from the committed rocprofv3 counter record of this same
@@ -57,8 +62,13 @@ T_START = time.time()
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (at least 1)")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the result checks, every side leg and the CPU baselines, and write "
+                         "the full record (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows of the last timed step to DIR/{query,subject,dist,count}.npy (float64)")
     ap.add_argument("--db-rows", type=int, default=10_000_000)
     ap.add_argument("--queries", type=int, default=10_000, help="queries per GPU per step")
     ap.add_argument("--seq-len", type=int, default=60)
@@ -92,14 +102,18 @@ def parse_args(argv=None):
     ap.add_argument("--collective", choices=["gather", "all_gather"], default="gather",
                     help="how the per-rank row lists reach rank 0 each step (N > 1)")
     ap.add_argument("--single-device", action="store_true", help="testing only: every rank uses GPU 0")
-    ap.add_argument("--full-record", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
-                    help="where the full record (every leg in detail, ~30 KB) is written; stdout carries the compact line only")
+    ap.add_argument("--full-record", default=None,
+                    help="where the full record (every leg in detail, ~30 KB) is written (default with --full: "
+                         "bench_out/bench_full.json; a plain run writes none unless given); stdout carries the compact line only")
     ap.add_argument("--configs-scale", type=float, default=1.0,
                     help="testing only: the BASELINE configs block with every size multiplied by this (and run whatever the timed "
                          "workload is), so that the line's length can be checked with every leg present")
     ap.add_argument("--no-kth", action="store_true", help="skip the k-th-mode leg (--max-num-hits 5 / 50)")
     ap.add_argument("--no-index", action="store_true", help="skip the block-index legs (smafa_db_build_index)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def find_free_port() -> int:
@@ -448,6 +462,28 @@ def emit(full: dict, full_path) -> None:
     print(line, flush=True)
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+FULL_RECORD_DEFAULT = os.path.join(ROOT, "bench_out", "bench_full.json")  # --full without --full-record
+DUMP_LIMIT = 64_000_000  # bytes in all
+
+
+def dump_outputs(out_dir: str, rows, total: int, limit: int = DUMP_LIMIT) -> None:
+    """The rows the timed path returned in its last step, (n, 3) [query, subject, dist] ordered (query, dist, subject) — the
+    reference's print order, so that two builds compare element for element — as DIR/query.npy, subject.npy, dist.npy
+    (float64: every index is exact) and DIR/count.npy (the number of rows the step found).  Beyond `limit` bytes in all a
+    fixed sample of the rows (seed 0, kept in order) stands for them."""
+    import numpy as np
+
+    rows = np.asarray(rows, dtype=np.uint32).reshape(-1, 3)
+    keep = (limit - 4096) // (3 * 8)  # 4 KB for count.npy and the four .npy headers
+    if len(rows) > keep:
+        rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), size=keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for i, name in enumerate(("query", "subject", "dist")):
+        np.save(os.path.join(out_dir, name + ".npy"), rows[:, i].astype(np.float64))
+    np.save(os.path.join(out_dir, "count.npy"), np.array([total], dtype=np.float64))
+
+
 
 # ------------------------------------------------------------------------------------------ helpers for the side legs
 class Bench:
@@ -648,7 +684,7 @@ def main() -> int:
     alphabet = smafa_amd.ALPHABET_AA if args.alphabet == "aa" else smafa_amd.ALPHABET_NT
     L, N, Q, D = args.seq_len, args.db_rows, args.queries, args.max_div
     max_subs = 10 if alphabet == smafa_amd.ALPHABET_AA else 6
-    side_legs = rank == 0 and not multi and not args.no_stream
+    side_legs = args.full and rank == 0 and not multi and not args.no_stream
     build_id = smafa_amd.build_id()
     skipped = []
 
@@ -781,22 +817,41 @@ def main() -> int:
            "n_frac": args.n_frac, "prefilter": args.prefilter, "mode": args.mode, "far_frac": args.far_frac,
            "kth_k": args.kth_k, "kth_bounded": bool(args.kth_bounded)}
 
-    B = Bench(torch, dev, stream, local_rank, cap)
-
-    # ---- result checks (outside the timed region)
-    checks = {}
-    if args.mode == "kth":
+    # ---- what the last timed step returned: rows (n, 3) [query, subject, dist] ordered (query, dist, subject)
+    if call_mode:
         rows = rows3(step.rows)
         n_rows = len(rows)
+    else:
+        last = (it[0] - 1) % len(bufs)
+        d_hits, d_count = bufs[last][HEAD:], bufs[last][:2].view(torch.int64)
+        n_rows = int(d_count.item())
+        rows = sorted_rows(d_hits[: 3 * min(n_rows, cap)].cpu().numpy().view(np.uint32).reshape(-1, 3))
+    if args.dump_outputs and rank == 0:
+        out_rows, out_total = rows, n_rows
+        if multi and not call_mode and gathered[last] is not None:
+            # what rank 0 received: every rank's rows, numbered by the query's place in the whole batch
+            g, blocks, out_total = gathered[last].view(world, width[0]), [], 0
+            for r in range(world):
+                c = int(g[r][:2].cpu().numpy().view(np.int64)[0])  # (a block may start at an odd int32: no torch view)
+                blk = g[r][HEAD: HEAD + 3 * min(c, (width[0] - HEAD) // 3)].cpu().numpy().view(np.uint32).reshape(-1, 3).copy()
+                blk[:, 0] += r * Q
+                blocks.append(blk)
+                out_total += c
+            out_rows = sorted_rows(np.concatenate(blocks))
+        dump_outputs(args.dump_outputs, out_rows, out_total)
+
+    B = Bench(torch, dev, stream, local_rank, cap) if args.full else None
+
+    # ---- result checks (--full; outside the timed region)
+    checks = {}
+    if args.full and args.mode == "kth":
         if rank == 0:
             import oracle
 
             oracle.build()
         checks["kth_rows_ok_incl_oracle_sample"] = kth_rows_ok(np, subj, my_q, rows, call_k, call_bound, np.array([0, Q // 2, Q - 1]))
         checks["oracle_sample_queries"] = 3
-    elif args.mode == "besthit":
-        rows = rows3(step.rows)
-        n_rows = len(rows)
+    elif args.full and args.mode == "besthit":
         rec = (subj[rows[:, 1]] != my_q[rows[:, 0]]).sum(axis=1)
         checks["distances_recomputed"] = bool((rec == rows[:, 2]).all())
         checks["every_query_has_a_best_hit"] = len(np.unique(rows[:, 0])) == Q
@@ -822,11 +877,7 @@ def main() -> int:
             got[:, 0] = remap[got[:, 0]]
             checks["oracle_sample_identical"] = sorted_rows(got).tobytes() == want_a.tobytes()
             checks["oracle_sample_queries"] = int(len(pick))
-    else:
-        last = (it[0] - 1) % len(bufs)
-        d_hits, d_count = bufs[last][HEAD:], bufs[last][:2].view(torch.int64)
-        n_rows = int(d_count.item())
-        rows = sorted_rows(d_hits[: 3 * min(n_rows, cap)].cpu().numpy().view(np.uint32).reshape(-1, 3))
+    elif args.full:
         checks["rows_fit"] = n_rows <= cap
         if multi:
             checks["rows_fit_gathered_width"] = n_rows * 3 + HEAD <= width[0]
@@ -835,7 +886,7 @@ def main() -> int:
                 # buffer's head, every rank's count within the gathered width
                 g = gathered[last].view(world, width[0])
                 checks["gather_block_is_own_buffer"] = bool(torch.equal(g[rank], bufs[last][: width[0]]))
-                counts_g = [int(g[r][:2].view(torch.int64).item()) for r in range(world)]
+                counts_g = [int(g[r][:2].cpu().numpy().view(np.int64)[0]) for r in range(world)]
                 checks["gather_counts_in_range"] = all(0 <= c and c * 3 + HEAD <= width[0] for c in counts_g)
                 checks["gathered_rows_total"] = int(sum(counts_g))
         # (1) soundness + (2) recall of the planted rows
@@ -861,8 +912,8 @@ def main() -> int:
                                              np.random.default_rng(5).integers(0, Q, size=4)]))[:8]
             checks["oracle_sample_identical"] = oracle_sample(np, subj, my_q, rows, D, pick)
             checks["oracle_sample_queries"] = int(len(pick))
-    ok = all(v for k, v in checks.items() if isinstance(v, bool))
-    if multi:
+    ok = all(v for k, v in checks.items() if isinstance(v, bool)) if args.full else None  # a plain run checks nothing
+    if multi and args.full:
         flag = torch.tensor([1 if ok else 0], device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         ok = bool(flag.item())
@@ -1138,7 +1189,7 @@ def main() -> int:
 
     # ---- CPU baselines: the oracle's port of the reference's per-query loop, bounded samples
     cpu = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi and not args.no_cpu_baseline:
         b = cpu_baselines(N, L, D, args.alphabet, subj, my_q, args.cpu_seconds)
         cpu = {
             "value": b["b1"]["value"], "unit": "query seqs/s", "cores": 1, "kind": "port",
@@ -1401,7 +1452,7 @@ def main() -> int:
             "run_s": round(elapsed(), 1),
             "skipped_for_time": skipped,
         }
-        emit(out, args.full_record)
+        emit(out, args.full_record or (FULL_RECORD_DEFAULT if args.full else None))
     if multi:
         dist.destroy_process_group()
     return 0

@@ -311,8 +311,8 @@ def test_bench_line_contract_on_a_small_workload(tmp_path):
     import json
 
     full_path = str(tmp_path / "bench_full.json")
-    r = _bench("--steps", "3", "--warmup", "1", "--db-rows", "300000", "--queries", "2048", "--cpu-seconds", "0.3", "--no-related",
-               "--configs-scale", "0.01", "--full-record", full_path)
+    r = _bench("--full", "--steps", "3", "--warmup", "1", "--db-rows", "300000", "--queries", "2048", "--cpu-seconds", "0.3",
+               "--no-related", "--configs-scale", "0.01", "--full-record", full_path)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
     assert lines and lines[-1].startswith("{") and len([l for l in lines if l.startswith("{")]) == 1
@@ -349,13 +349,52 @@ def test_bench_line_contract_on_a_small_workload(tmp_path):
     assert all(v["verified"] for v in full["configs"].values())
 
 
+def _dumped(out_dir):
+    return {k: np.load(os.path.join(out_dir, k + ".npy")) for k in ("query", "subject", "dist", "count")}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_rows(tmp_path):
+    """A plain run (no --full): the contract's fields for exactly --steps timed steps and nothing else (no check, no side leg, no
+    CPU baseline, no full record).  --dump-outputs holds the rows of the last timed step: the oracle's rows for the same seeded
+    workload, and the same bytes from a second run."""
+    import json
+
+    from smafa_amd import synth
+
+    n, q, d = 100_000, 512, 5
+    dumps = []
+    for i in range(2):
+        out_dir = str(tmp_path / ("out%d" % i))
+        r = _bench("--steps", "4", "--warmup", "1", "--db-rows", str(n), "--queries", str(q), "--dump-outputs", out_dir)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert lines and len([l for l in lines if l.startswith("{")]) == 1 and len(lines[-1]) <= 4096
+        out = json.loads(lines[-1])
+        assert out["steps"] == 4 and out["warmup"] == 1 and out["n_gpus"] == 1 and out["unit"] == "query seqs/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "u32" and out["metric"].startswith("query seqs/sec")
+        assert abs(out["value"] - q / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-4
+        assert out["verified"] is None and out["cpu_baseline"] is None and out["full_record"] is None and not out["legs"]
+        dumps.append(_dumped(out_dir))
+        assert all(a.dtype == np.float64 for a in dumps[-1].values())
+        assert int(dumps[-1]["count"][0]) == len(dumps[-1]["query"]) == out["rows_per_step"]
+    for k in dumps[0]:
+        assert dumps[0][k].tobytes() == dumps[1][k].tobytes(), k
+    subj = synth.subjects(n, 60, 1, seed=1)
+    qry = synth.queries(subj, q, 1, seed=3, max_subs=10)[0]
+    want = oracle.scan_codes(subj, qry, d)
+    got = np.stack([dumps[0][k] for k in ("query", "subject", "dist")], axis=1).astype(np.uint32)
+    assert len(want) > 0 and got.tobytes() == np.stack([want["query"], want["subject"], want["dist"]], axis=1).tobytes()
+
+
 @pytest.mark.gpu
 def test_bench_self_launch_two_ranks_one_gpu_gloo(tmp_path):
     import json
 
     full_path = str(tmp_path / "bench_full.json")
-    r = _bench("--gpus", "2", "--single-device", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--db-rows", "200000",
-               "--queries", "512", "--no-cpu-baseline", "--no-related", "--full-record", full_path)
+    r = _bench("--full", "--gpus", "2", "--single-device", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--db-rows",
+               "200000", "--queries", "512", "--no-cpu-baseline", "--no-related", "--full-record", full_path,
+               "--dump-outputs", str(tmp_path / "two"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) <= 4096, r.stdout[-2000:]
@@ -370,6 +409,13 @@ def test_bench_self_launch_two_ranks_one_gpu_gloo(tmp_path):
     rows = out["checks"]["gathered_rows_total"] / 2
     assert out["checks"]["rows_fit_gathered_width"] is True
     assert 16 + 12 * rows <= out["gathered_bytes_per_rank_per_step"] <= 16 + 12 * (2.0 * rows + 128), out["gathered_bytes_per_rank_per_step"]
+    # what rank 0 gathered is the whole batch's rows: those of one rank with both shards (the same seeded 1 024 queries)
+    r = _bench("--steps", "2", "--warmup", "1", "--db-rows", "200000", "--queries", "1024", "--dump-outputs", str(tmp_path / "one"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    two, one = _dumped(str(tmp_path / "two")), _dumped(str(tmp_path / "one"))
+    assert int(two["count"][0]) == out["checks"]["gathered_rows_total"] and len(two["query"]) > 0
+    for k in one:
+        assert two[k].tobytes() == one[k].tobytes(), k
 
 
 @pytest.mark.gpu
@@ -402,7 +448,7 @@ def test_rccl_rehearsal_world_of_one(tmp_path):
     assert open(out).read() == want.stdout and want.stdout
     for collective in ("gather", "all_gather"):
         full_path = str(tmp_path / ("bench_%s.json" % collective))
-        r = _bench("--gpus", "1", "--rehearse-collectives", "--collective", collective, "--steps", "3", "--warmup", "2",
+        r = _bench("--full", "--gpus", "1", "--rehearse-collectives", "--collective", collective, "--steps", "3", "--warmup", "2",
                    "--db-rows", "200000", "--queries", "512", "--full-record", full_path)
         assert r.returncode == 0, r.stderr[-3000:]
         assert len(r.stdout.splitlines()[-1]) <= 4096

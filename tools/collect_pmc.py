@@ -3,7 +3,7 @@
 
     python3 tools/collect_pmc.py [--tag NAME] [-- extra bench.py flags]
 
-  1. `rocprofv3 --kernel-trace --stats` of `python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-stream`
+  1. `rocprofv3 --kernel-trace --stats` of `python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-stream`
      -> per-kernel average durations (must agree with the HIP-event average of the bench line);
   2. four separate `--pmc` passes of the same command (counters never share a run with a trace other than the
      kernel trace, and FETCH_SIZE / WRITE_SIZE cannot share a pass — MI355X_MICROARCH.md, PMC slots):
@@ -114,7 +114,7 @@ def main():
     out = os.path.join(ROOT, "gpurun_out", a.tag)
     os.makedirs(out, exist_ok=True)
     os.environ.setdefault("TMPDIR", "/tmp")
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "2", "--no-cpu-baseline",
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--full", "--steps", str(a.steps), "--warmup", "2", "--no-cpu-baseline",
              "--no-stream", *a.bench_args]
     prof = "/opt/rocm/bin/rocprofv3"
     if a.cluster:

@@ -60,7 +60,7 @@ json.dump({"records": recs}, open(E + "/r04_pmc.json", "w"), indent=1)
 shutil.copy(E + "/r04_pmc.json", "profiles/r04_pmc.json")  # on the box: the bench line below looks it up
 PY
   python3 tools/stream_pmc.py > $E/stream_pmc.log 2>&1 && cp gpurun_out/r04_stream_pmc.json $E/r04_stream_pmc.json && cp $E/r04_stream_pmc.json profiles/r04_stream_pmc.json
-  python3 bench.py --steps 20 --warmup 5 --full-record $E/r04_bench_full.json > $E/r04_bench.json 2> $E/bench.err || exit 1
+  python3 bench.py --full --steps 20 --warmup 5 --full-record $E/r04_bench_full.json > $E/r04_bench.json 2> $E/bench.err || exit 1
   wc -c $E/r04_bench.json
   python3 - <<'PY'
 import json
