@@ -192,6 +192,12 @@ int smafa_last_scan_plan(smafa_db *db, uint32_t *filter_plane_resident, uint32_t
 /* Name of the scan kernel instantiation the most recent launch on this handle used, spelled the way rocprofv3
  * lists it (e.g. "smafa::scan_lazy_kernel<5, 5, 2, 4, false>"), so that a bench line and a profile can be matched. */
 int smafa_last_scan_kernel(smafa_db *db, char *name, uint64_t cap);
+/* Every distinct kernel instantiation the most recent smafa_scan_hits, smafa_scan_launch, smafa_scan_each or smafa_distances
+ * call on this handle launched from the scan family (seed passes, near-hit ladder steps, k-th counting and append passes,
+ * index probes), spelled as the demangled template-id ("smafa::scan_kernel<5, 5, 2, 1, false, 1>"), newline-separated
+ * in first-launch order and NUL-terminated.  A scan_wide_kernel launch with its zone level on adds the marker line
+ * "<template-id> (zone level on)" after the template-id.  SMAFA_ERR_CAPACITY if the list needs more than cap bytes. */
+int smafa_last_call_kernels(smafa_db *db, char *names, uint64_t cap);
 /* Tuning knob: queries per workgroup pass (0 = automatic). */
 int smafa_set_query_block(smafa_db *db, uint32_t queries_per_block);
 /* 1 (default): the scan evaluates an exact lower bound first and runs the full comparison only where it can

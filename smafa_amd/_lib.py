@@ -27,7 +27,7 @@ EXPORTS = [
     "smafa_db_create", "smafa_db_append", "smafa_db_save", "smafa_db_load", "smafa_db_info", "smafa_db_set_stream", "smafa_db_destroy",
     "smafa_scan_hits", "smafa_distances", "smafa_qset_create", "smafa_qset_destroy", "smafa_scan_launch",
     "smafa_scan_each", "smafa_last_call_stats", "smafa_launch_device",
-    "smafa_sync", "smafa_last_scan_ms", "smafa_last_scan_plan", "smafa_last_scan_kernel", "smafa_build_id", "smafa_hbm_read_probe", "smafa_set_query_block", "smafa_set_prefilter", "smafa_set_zone_level", "smafa_db_build_index", "smafa_db_drop_index", "smafa_index_info", "smafa_set_index", "smafa_select_rows", "smafa_write_rows",
+    "smafa_sync", "smafa_last_scan_ms", "smafa_last_scan_plan", "smafa_last_scan_kernel", "smafa_last_call_kernels", "smafa_build_id", "smafa_hbm_read_probe", "smafa_set_query_block", "smafa_set_prefilter", "smafa_set_zone_level", "smafa_db_build_index", "smafa_db_drop_index", "smafa_index_info", "smafa_set_index", "smafa_select_rows", "smafa_write_rows",
     "smafa_dbfile_write", "smafa_dbfile_read", "smafa_fastx_load", "smafa_fastx_load_partial", "smafa_fastx_load_part", "smafa_free",
     "smafa_group_create", "smafa_group_load", "smafa_group_append", "smafa_group_scan_hits", "smafa_group_build_index", "smafa_group_size",
     "smafa_group_member", "smafa_group_destroy",
@@ -112,6 +112,7 @@ def lib() -> C.CDLL:
     l.smafa_last_scan_ms.argtypes = [vp, C.POINTER(C.c_float), u32p]
     l.smafa_last_scan_plan.argtypes = [vp, u32p, u32p, u32p]
     l.smafa_last_scan_kernel.argtypes = [vp, C.c_char_p, C.c_uint64]
+    l.smafa_last_call_kernels.argtypes = [vp, C.c_char_p, C.c_uint64]
     l.smafa_build_id.restype = C.c_char_p
     l.smafa_hbm_read_probe.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_double)]
     l.smafa_set_query_block.argtypes = [vp, C.c_uint32]

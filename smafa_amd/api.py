@@ -223,6 +223,19 @@ class SubjectStore:
         check(lib().smafa_last_scan_kernel(self._h, buf, 128))
         return buf.value.decode()
 
+    def last_call_kernels(self) -> list[str]:
+        """every distinct scan-family instantiation the most recent scan / get_distances call launched, in first-launch
+        order (smafa_last_call_kernels)"""
+        cap = 4096
+        while True:
+            buf = C.create_string_buffer(cap)
+            rc = lib().smafa_last_call_kernels(self._h, buf, cap)
+            if rc == _lib.ERR_CAPACITY:
+                cap *= 4
+                continue
+            check(rc)
+            return buf.value.decode().split("\n") if buf.value else []
+
     def close(self):
         if self._h:
             lib().smafa_db_destroy(self._h)

@@ -97,6 +97,7 @@ struct smafa_db {
     // (the captured kernel nodes bake in the set's device record buffer: the key names the set by its serial and that pointer,
     // not by its host address alone — a destroyed set's address is handed out again by the next `new`)
     struct EachKey { const void *qs, *qrec, *hits, *counts; uint64_t qs_serial, cap, nq, generation; uint32_t max_div, qb; int zone; bool filter; } each_key{};
+    std::vector<std::string> each_kernels;  // ... and the instantiations its capture launched (a replay names them again)
     uint32_t qb_override = 0;
     bool use_filter = true;  // exact lower-bound prefilter in the scan kernel (SMAFA_FILTER=0 disables)
     uint32_t tiles_override = 0;  // SMAFA_TILES
@@ -106,6 +107,9 @@ struct smafa_db {
     // what the last launch used (smafa_last_scan_plan)
     uint32_t plan_lazy = 0, plan_tiles = 1, plan_qblocks = 1;
     char plan_kernel[96] = "";  // the instantiation of the last launch, as rocprofv3 names it (smafa_last_scan_kernel)
+    // every distinct instantiation the current call launched, in first-launch order (smafa_last_call_kernels); reset by
+    // smafa_scan_hits, smafa_scan_launch, smafa_scan_each and smafa_distances
+    std::vector<std::string> call_kernels;
     int n_cu = 256;
     // scratch of the host-buffer API, kept across calls
     DevBuf upload;            // staging for code rows on their way to the pack kernel
@@ -460,13 +464,18 @@ static int qset_fill(smafa_qset *qs, smafa_db *db, const uint8_t *query_codes, u
     return pack_rows(db, query_codes, 0, n_queries, qs->qrec.as<uint32_t>(), 1);
 }
 
-// remember which instantiation ran, spelled the way rocprofv3 lists it
+// remember which instantiation ran, spelled the way rocprofv3 lists it, and add it to the call's list (first launch only)
+static void note_call_kernel(const smafa_db *db, const char *name) {
+    auto &names = const_cast<smafa_db *>(db)->call_kernels;
+    if (std::find(names.begin(), names.end(), name) == names.end()) names.emplace_back(name);
+}
 static void note_kernel(const smafa_db *db, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 static void note_kernel(const smafa_db *db, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(const_cast<smafa_db *>(db)->plan_kernel, sizeof db->plan_kernel, fmt, ap);
     va_end(ap);
+    note_call_kernel(db, db->plan_kernel);
 }
 
 template <int PS, int PQ, int W, int T>
@@ -659,8 +668,11 @@ static void launch_wide_t(const smafa_db *db, const uint32_t *d_qrec, const Scan
     const uint32_t wc = (db->W == 3 || db->W == 4) ? db->W : 0u;  // compile-time word count: register-resident dense walk
 #define SMAFA_WIDE(FW_, WC_)                                                                                     \
     if (fw == FW_ && wc == WC_) {                                                                               \
-        note_kernel(db, "smafa::scan_wide_kernel<%d, %d, %s, %d, %d>%s", PS, PQ, seed ? "true" : "false", FW_, WC_, \
-                    a.zone_on ? " (zone level on)" : "");                                                       \
+        note_kernel(db, "smafa::scan_wide_kernel<%d, %d, %s, %d, %d>", PS, PQ, seed ? "true" : "false", FW_, WC_);    \
+        if (a.zone_on) { /* (the call's list names the zone-level form as a marker of its own, after the template-id) */ \
+            const std::string id = db->plan_kernel;                                                             \
+            note_kernel(db, "%s (zone level on)", id.c_str());                                                  \
+        }                                                                                                       \
         if (seed)                                                                                               \
             hipLaunchKernelGGL((scan_wide_kernel<PS, PQ, true, FW_, WC_>), dim3(grid), dim3(256), 0, db->stream, \
                                planes, d_qrec, a, db->W);                                                       \
@@ -869,8 +881,6 @@ static int index_probe(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t 
     x.bound = thr0;
     x.L = db->L;
     x.QS = db->QS;
-    x.q_begin = q_begin;
-    x.q_end = q_end;
     for (uint32_t j = 0; j < (uint32_t)kIndexMaxBlocks; j++) {
         x.probe_block[j] = j <= thr0 ? probe_block[j] : 0;
         x.probe_cols[j] = (uint32_t)ix.col_begin[x.probe_block[j]] | ((uint32_t)ix.col_begin[x.probe_block[j] + 1] << 16);
@@ -881,31 +891,40 @@ static int index_probe(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t 
     a.cap = rows_cap;
     a.count = d_count;  // zeroed by the caller; rows are reserved straight from it and it IS the result
     a.order = db->d_order;
-    const uint64_t groups = (uint64_t)(q_end - q_begin) * x.n_probes;
-    const uint64_t grid = (groups * kIndexGroup + kIndexWg - 1u) / kIndexWg;
-    if (grid > 0x7fffffffull) return set_error(SMAFA_ERR_INVALID, "index probe grid too large (%llu workgroups)", (unsigned long long)grid);
     int cur_dev = -1;
     if (hipGetDevice(&cur_dev) == hipSuccess) {
         db->launch_device = cur_dev;
         if (cur_dev != db->device) db->launches_off_device++;
     }
     const uint32_t *qrec = qs->qrec.as<uint32_t>();
-    bool launched = false;
+    // One dispatch holds fewer than 2^32 work-items (its grid size is 32 bits: a launch of 2^32 + 2^23 of them probed only the
+    // first queries, with no error), and the kernel numbers its (query, probe) groups from a 32-bit thread index: a batch of
+    // more than 2^31 / kIndexGroup groups is probed in query ranges that each stay below that (rows go to one list).
+    const uint32_t per_launch = (uint32_t)((1ull << 31) / kIndexGroup / x.n_probes);
+    for (uint32_t qb = q_begin; qb < q_end;) {
+        const uint32_t qe = q_end - qb > per_launch ? qb + per_launch : q_end;
+        x.q_begin = qb;
+        x.q_end = qe;
+        const uint64_t groups = (uint64_t)(qe - qb) * x.n_probes;
+        const uint64_t grid = (groups * kIndexGroup + kIndexWg - 1u) / kIndexWg;
+        bool launched = false;
 #define SMAFA_PROBE(PS_, PQ_, W_)                                                                                             \
     if (!launched && db->P == PS_ && db->PQ == PQ_ && db->W == W_) {                                                          \
         hipLaunchKernelGGL((index_probe_kernel<PS_, PQ_, W_>), dim3((uint32_t)grid), dim3(kIndexWg), 0, db->stream, db->d_planes, qrec, x, a); \
         note_kernel(db, "smafa::index_probe_kernel<%d, %d, %d>", PS_, PQ_, W_);                                               \
         launched = true;                                                                                                      \
     }
-    SMAFA_PROBE(2, 3, 1) SMAFA_PROBE(3, 3, 1) SMAFA_PROBE(5, 5, 1) SMAFA_PROBE(2, 3, 2) SMAFA_PROBE(3, 3, 2) SMAFA_PROBE(5, 5, 2)
-    SMAFA_PROBE(2, 3, 3) SMAFA_PROBE(3, 3, 3) SMAFA_PROBE(5, 5, 3) SMAFA_PROBE(2, 3, 4) SMAFA_PROBE(3, 3, 4) SMAFA_PROBE(5, 5, 4)
+        SMAFA_PROBE(2, 3, 1) SMAFA_PROBE(3, 3, 1) SMAFA_PROBE(5, 5, 1) SMAFA_PROBE(2, 3, 2) SMAFA_PROBE(3, 3, 2) SMAFA_PROBE(5, 5, 2)
+        SMAFA_PROBE(2, 3, 3) SMAFA_PROBE(3, 3, 3) SMAFA_PROBE(5, 5, 3) SMAFA_PROBE(2, 3, 4) SMAFA_PROBE(3, 3, 4) SMAFA_PROBE(5, 5, 4)
 #undef SMAFA_PROBE
-    if (!launched) return set_error(SMAFA_ERR_INVALID, "no index probe for %u/%u planes x %u words", db->P, db->PQ, db->W);
-    HIP_TRY(hipGetLastError());
+        if (!launched) return set_error(SMAFA_ERR_INVALID, "no index probe for %u/%u planes x %u words", db->P, db->PQ, db->W);
+        HIP_TRY(hipGetLastError());
+        db->last_launches++;
+        qb = qe;
+    }
     db->plan_lazy = 0;
     db->plan_tiles = 0;
     db->plan_qblocks = 1;
-    db->last_launches++;
     db->index_probes++;
     return SMAFA_OK;
 }
@@ -1114,6 +1133,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         uint32_t *thr = qs->thr.as<uint32_t>();
 #define SMAFA_SEED(PS_, PQ_, W_)                                                                                              \
     if (db->P == PS_ && db->PQ == PQ_ && db->W == W_) {                                                                       \
+        note_kernel(db, "smafa::kth_seed_kernel<%d, %d, %d>", PS_, PQ_, W_);                                                  \
         hipLaunchKernelGGL((kth_seed_kernel<PS_, PQ_, W_>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ,    \
                            db->W, tiles, (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt,      \
                            (uint32_t)cnt_stride);                                                                             \
@@ -1122,6 +1142,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         SMAFA_SEED(2, 3, 1) SMAFA_SEED(3, 3, 1) SMAFA_SEED(5, 5, 1) SMAFA_SEED(2, 3, 2) SMAFA_SEED(3, 3, 2) SMAFA_SEED(5, 5, 2)
         SMAFA_SEED(2, 3, 3) SMAFA_SEED(3, 3, 3) SMAFA_SEED(5, 5, 3) SMAFA_SEED(2, 3, 4) SMAFA_SEED(3, 3, 4) SMAFA_SEED(5, 5, 4)
 #undef SMAFA_SEED
+        note_kernel(db, "smafa::kth_seed_kernel<0, 0, 0>");
         hipLaunchKernelGGL((kth_seed_kernel<0, 0, 0>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ, db->W, tiles,
                            (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt, (uint32_t)cnt_stride);
     };
@@ -1951,6 +1972,21 @@ int smafa_last_scan_kernel(smafa_db *db, char *name, uint64_t cap) try {
     return smafa::exception_code("smafa_last_scan_kernel");
 }
 
+int smafa_last_call_kernels(smafa_db *db, char *names, uint64_t cap) try {
+    if (!db || !names || cap == 0) return set_error(SMAFA_ERR_INVALID, "smafa_last_call_kernels: NULL argument");
+    std::string all;
+    for (const std::string &k : db->call_kernels) all += (all.empty() ? "" : "\n") + k;
+    if (all.size() + 1 > cap) {
+        names[0] = '\0';
+        return set_error(SMAFA_ERR_CAPACITY, "kernel list too long: %zu bytes needed, capacity %llu", all.size() + 1,
+                         (unsigned long long)cap);
+    }
+    memcpy(names, all.c_str(), all.size() + 1);
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_last_call_kernels");
+}
+
 int smafa_hbm_read_probe(int device, uint64_t bytes, double *gb_per_s) try {
     if (!gb_per_s) return set_error(SMAFA_ERR_INVALID, "smafa_hbm_read_probe: NULL argument");
     *gb_per_s = 0.0;
@@ -2117,6 +2153,7 @@ void smafa_qset_destroy(smafa_qset *qs) {
 int smafa_scan_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, uint32_t max_num_hits, void *d_hits,
                       uint64_t cap, void *d_count) try {
     if (!db || !qs || !d_count || (!d_hits && cap)) return set_error(SMAFA_ERR_INVALID, "smafa_scan_launch: NULL argument");
+    db->call_kernels.clear();
     if (qs->db != db) return set_error(SMAFA_ERR_INVALID, "query set was packed for a different store");
     if (max_num_hits == 0) max_num_hits = SMAFA_NONE;
     int rc = use_device(db);
@@ -2139,6 +2176,7 @@ int smafa_scan_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, uint32_t m
 int smafa_scan_each(smafa_db *db, smafa_qset *qs, uint32_t max_div, void *d_hits, uint64_t cap_per_query, void *d_counts,
                     int use_graph) try {
     if (!db || !qs || !d_counts || (!d_hits && cap_per_query)) return set_error(SMAFA_ERR_INVALID, "smafa_scan_each: NULL argument");
+    db->call_kernels.clear();
     if (qs->db != db) return set_error(SMAFA_ERR_INVALID, "query set was packed for a different store");
     int rc = use_device(db);
     if (rc) return rc;
@@ -2201,7 +2239,9 @@ int smafa_scan_each(smafa_db *db, smafa_qset *qs, uint32_t max_div, void *d_hits
             return set_error(SMAFA_ERR_DEVICE, "graph instantiation failed: %s", hipGetErrorString(e));
         }
         memcpy(&db->each_key, &key, sizeof key);
+        db->each_kernels = db->call_kernels;
     }
+    db->call_kernels = db->each_kernels;
     db->last_launches = nq;
     HIP_TRY(hipEventRecord(db->ev0, db->stream));
     HIP_TRY(hipGraphLaunch(db->each_graph, db->stream));
@@ -2255,6 +2295,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
                     uint32_t max_num_hits, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
     if (!db || !n_out || (!query_codes && n_queries) || (!out && cap))
         return set_error(SMAFA_ERR_INVALID, "smafa_scan_hits: NULL argument");
+    db->call_kernels.clear();
     if (max_num_hits == 0) max_num_hits = SMAFA_NONE;
     // fingerprint of the request: the query bytes, their count, the bounds and the state of the store
     uint64_t key = 0x9e3779b97f4a7c15ull ^ db->generation;
@@ -2302,6 +2343,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {
     if (!db || !query_codes || (!distances && db->n)) return set_error(SMAFA_ERR_INVALID, "smafa_distances: NULL argument");
+    db->call_kernels.clear();
     if (db->n == 0) return SMAFA_OK;
     int rc = use_device(db);
     if (rc) return rc;

@@ -267,3 +267,31 @@ def test_product_cli_answers_from_the_index_when_told_to(index_env, tmp_path):
         forced = subprocess.run([_lib.CLI_PATH, "query", "-d", db, "-q", qf, "-v", *flags], capture_output=True, text=True, env=env)
         assert forced.returncode == 0 and forced.stdout == want.stdout, flags
         assert "block index of 30000 rows" in forced.stderr, forced.stderr[-400:]
+
+
+def test_index_probe_past_2_30_query_probe_pairs(index_env):
+    """(query, probe) groups are numbered from a 32-bit thread index: at nq * (bound + 1) >= 2^30 one launch would wrap it,
+    skip the probes of the high queries and probe the low ones twice.  2^25 + 2^16 queries x 32 probes, all of them N-only
+    (every probe empty) except six planted ones at both ends and around 2^25: exactly the oracle's rows of those six."""
+    index_env["SMAFA_INDEX_MAX_RUN"] = "100000000"
+    index_env["SMAFA_INDEX_CAND"] = "100"
+    rng = np.random.default_rng(30)
+    L, n, D = 60, 3000, 31
+    s = rng.integers(0, 4, size=(n, L), dtype=np.uint8)
+    nq = (1 << 25) + (1 << 16)
+    at = np.array([0, 1, (1 << 25) - 1, 1 << 25, (1 << 25) + 1, nq - 1])
+    real = queries_from(rng, s, len(at), 4, 8)
+    q = np.full((nq, L), 4, dtype=np.uint8)  # ~2 GB of N
+    q[at] = real
+    store = smafa_amd.SubjectStore(L, 0)
+    store.push(s)
+    assert store.info().planes == 2
+    assert store.build_index(D)["max_div_served"] == D
+    got = store.scan(q, max_divergence=D)
+    del q
+    assert store.last_call_kernels() == ["smafa::index_probe_kernel<2, 3, 2>"], store.last_call_kernels()
+    want = oracle.scan_codes(s, real, D)
+    want["query"] = at[want["query"]]
+    assert len(want) >= len(at)
+    assert got.tobytes() == want.tobytes(), (len(got), len(want), np.unique(got["query"]).tolist()[:12])
+    store.close()
