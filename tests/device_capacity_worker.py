@@ -1,5 +1,8 @@
 """Worker for tests/test_gpu_layout.py::test_device_launch_counts_are_exact_at_any_capacity (torch supplies the device
-buffers, as in bench.py, and is imported first)."""
+buffers, as in bench.py, and is imported first).
+
+`--census SWITCHES`: the same contract for every dense census case of one switch set (tests/kernel_census_table.py) with a
+bound and k = 0 — tests/test_gpu_kernel_census.py::test_device_launch_capacity_of_every_fixed_bound_instantiation."""
 import os
 import sys
 
@@ -82,5 +85,67 @@ def main():
     print("device capacity ok")
 
 
+def census(switches):
+    """every dense census case of the switch set with a bound and k = 0, at its census nq (more than 64 queries: the ticket path)
+    and — neither zone nor index cases, whose kernel and plan change with the query count — at its first 64 queries too
+    (the own-counter path of the same kernel); caps around the exact total, a third of it, 1, and 0 without a buffer"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_kernel_census import PARAMS, _store_key, open_stores  # noqa: E402
+
+    oracle.build()
+    smafa_amd.build()
+    d_count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    keys = sorted({_store_key(c) for _, _, c in PARAMS if c["switches"] == switches})
+    n_cases = 0
+    for key in keys:
+        cases = [(name, c) for name, _, c in PARAMS if _store_key(c) == key and c["D"] is not None and not c["k"]]
+        if not cases:
+            continue
+        stores = open_stores(key, dense=True)  # (sets the switches for the handles it creates, then restores them)
+        for name, c in cases:
+            want_kernel = name + (" (%s)" % c["marker"] if c["marker"] else "")
+            for store, p in stores:
+                store.set_prefilter(c["prefilter"])
+                store.set_zone_level(c["zone"])
+                if c["index"] and not store.index_info()["current"]:
+                    assert store.build_index(c["D"])["max_div_served"] == c["D"]
+                s = p.subjects()
+                q_all = p.queries(c["E"], c["nq"], 0, c["spread"])
+                for nq in [c["nq"]] + ([64] if c["nq"] > 64 and not c["zone"] and not c["index"] else []):
+                    q = np.ascontiguousarray(q_all[:nq])
+                    qset = smafa_amd.QuerySet(store, q)
+                    want = oracle.scan_codes(s, q, c["D"])
+                    total = len(want)
+                    keys_want = set(zip(want["query"].tolist(), want["subject"].tolist(), want["dist"].tolist()))
+                    for cap in sorted({total, total + 1, max(total - 1, 0), total // 3, 1, 0}, reverse=True):
+                        where = "%s (%s, n=%d) nq=%d cap=%d" % (want_kernel, c, p.n, nq, cap)
+                        d_hits = torch.full((max(cap, 1) * 3 + 3,), -1, dtype=torch.int32, device="cuda")
+                        for _ in range(2):  # twice: the kernel leaves its internal counters at zero for the next launch
+                            store.scan_launch(qset, c["D"], None, d_hits.data_ptr() if cap else 0, cap, d_count.data_ptr())
+                            store.sync()
+                            assert want_kernel in store.last_call_kernels(), (where, store.last_call_kernels())
+                            assert int(d_count.item()) == total, (where, int(d_count.item()), total)
+                        kept = min(cap, total)
+                        h = d_hits.cpu().numpy()
+                        assert (h[3 * kept:] == -1).all(), ("wrote past the capacity", where)
+                        rows = h[: 3 * kept].view(np.uint32).reshape(-1, 3)
+                        order = np.lexsort((rows[:, 1], rows[:, 2], rows[:, 0]))
+                        got = np.ascontiguousarray(rows[order]).view(smafa_amd.HIT_DTYPE).reshape(-1)
+                        if cap >= total:
+                            assert got.tobytes() == want.tobytes(), where
+                        else:  # any cap rows of the answer, each at most once
+                            mine = list(zip(got["query"].tolist(), got["subject"].tolist(), got["dist"].tolist()))
+                            assert len(set(mine)) == len(mine) == kept and set(mine) <= keys_want, where
+                    qset.close()
+            n_cases += 1
+        for store, _ in stores:
+            store.close()
+    assert n_cases > 0, switches
+    print("device capacity ok: census switch set %s (%d cases)" % (switches, n_cases))
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) == 3 and sys.argv[1] == "--census":
+        census(sys.argv[2])
+    else:
+        main()

@@ -14,6 +14,13 @@ Queries of a case:
   differ in one plane and pairs that differ in several both occur;
 - k modes: queries with k - 1, k and k + 1 subjects tied at distance E (and one more at E + 1);
 - fillers: planted pairs at distances spread over [0, spread] (the near-hit ladder then finishes some queries at every step).
+
+Dense stores (Planter(..., dense_bounds=...)) keep all of the above and add a FAMILY: copies of one base row, at least 40 % of
+the store, in both appends.  The first append holds only exact copies (the layout is not known before it is fixed); the
+second one also holds members 1 .. E + 1 substitutions away for every bound E of the store, their columns placed the four
+ways above and their letters cycling over every letter difference.  The dense queries are the base and the base with 1-2
+substitutions: 32 of them in every 64-query chunk, then the planted queries and the homopolymers.  So every
+workgroup and chunk appends far more rows than its LDS stage parks, and the k modes see ties far past k.
 """
 from __future__ import annotations
 
@@ -74,13 +81,24 @@ def packed_columns(alphabet, L, first):
 class Planter:
     """rows of one store and the queries planted against it"""
 
-    def __init__(self, kind, L, n, seed):
+    def __init__(self, kind, L, n, seed, dense_bounds=None):
         self.kind, self.L, self.n = kind, L, n
         self.alphabet, self.planes, _ = KINDS[kind]
         self.rng = np.random.default_rng(seed)
         self.sl, self.ql = store_letters(kind), query_letters(kind)
         first_letters = 4 if kind == "nt3" else self.sl  # the three-plane store: its first N arrives with the second append
         self.first = self.rng.integers(0, first_letters, size=(1024, L), dtype=np.uint8)
+        self.dense, self.sealed = dense_bounds is not None, False
+        if self.dense:
+            self.base = self.rng.integers(0, first_letters, size=L, dtype=np.uint8)  # (no N: it is in the first append too)
+            self.first[self.rng.choice(1024, size=620, replace=False)] = self.base
+            self.member_d = sorted(set(range(1, 8)) | {d for E in dense_bounds for d in (E, E + 1)})
+            self.dense_pool = [self.base]
+            while len(self.dense_pool) < 128:  # the base with 1-2 substitutions
+                q = self.base.copy()
+                for c in self.rng.choice(L, size=min(L, 1 + len(self.dense_pool) % 2), replace=False):
+                    q[c] = (int(q[c]) + 1 + int(self.rng.integers(0, self.ql - 1))) % self.ql
+                self.dense_pool.append(q)
         self.perm = packed_columns(self.alphabet, L, self.first)
         self.second = self.rng.integers(0, self.sl, size=(n - 1024, L), dtype=np.uint8)
         self.free = list(self.rng.permutation(n - 1024))
@@ -94,6 +112,7 @@ class Planter:
 
     def _place(self, row):
         assert self.free, "no room left for planted subjects"
+        assert not self.sealed, "planted after the family filled the store"
         self.second[self.free.pop(0)] = row
 
     def _pair(self):
@@ -166,8 +185,50 @@ class Planter:
             self.sets[key] = np.array(qs, dtype=np.uint8)
         return self.sets[key]
 
+    def seal(self):
+        """dense stores: the family's rows in the second append, in every free row but a fifth (call after every plant())"""
+        if not self.dense or self.sealed:
+            return
+        keep = len(self.free) // 5
+        deltas = itertools.cycle(range(1, self.sl))
+        dists, places = itertools.cycle(self.member_d), itertools.cycle(PLACEMENTS)
+        for i, slot in enumerate(self.free[: len(self.free) - keep]):
+            row = self.base.copy()
+            if i % 2:  # every other one a member 1 .. E + 1 substitutions away; the rest exact copies
+                d = min(next(dists), self.L)
+                cols = None
+                while cols is None:
+                    cols = self.columns(d, next(places))
+                for c in cols:
+                    row[c] = (int(row[c]) + next(deltas)) % self.sl
+            self.second[slot] = row
+        self.free = self.free[len(self.free) - keep:]
+        self.sealed = True
+
+    def dense_queries(self, E, nq, k=0, spread=0):
+        """dense stores: nq queries and the mask of the dense ones (the base and the base with 1-2 substitutions) — 32 of every
+        64-query chunk (all of a chunk of fewer than 32), then the planted queries and the homopolymers, repeated as often as
+        the chunks need; a single query is the base.
+        (The near-hit ladder steps on only while 16 or more queries are open: with the dense queries finished by its first
+        step, the planted ones must be that many for the later steps — and their instantiations — to run, as on a sparse store.)"""
+        assert self.dense
+        if nq == 1:
+            return np.ascontiguousarray(self.base[None, :]), np.ones(1, dtype=bool)
+        homo = np.repeat(np.arange(self.ql, dtype=np.uint8)[:, None], self.L, axis=1)
+        extra = itertools.cycle(list(np.concatenate([self.plant(E, k, spread), homo])))
+        pool = itertools.cycle(self.dense_pool)
+        qs, mask = [], []
+        for lo in range(0, nq, 64):
+            size = min(64, nq - lo)
+            n_dense = 32 if size >= 32 else size
+            qs += [next(pool) for _ in range(n_dense)] + [next(extra) for _ in range(size - n_dense)]
+            mask += [True] * n_dense + [False] * (size - n_dense)
+        return np.ascontiguousarray(np.array(qs, dtype=np.uint8)), np.array(mask)
+
     def queries(self, E, nq, k=0, spread=0):
         """nq queries for a launch of bound E: the planted ones first, then homopolymers, then fillers drawn from the store"""
+        if self.dense:
+            return self.dense_queries(E, nq, k, spread)[0]
         if nq == 1:
             return self.plant(E, k, spread)[:1]
         homo = np.repeat(np.arange(self.ql, dtype=np.uint8)[:, None], self.L, axis=1)

@@ -42,17 +42,14 @@ def planted(rng, n, L, n_letters, q, max_subs, dup=True):
 
 def expected_with_k(all_hits, k):
     """apply "dist <= k-th smallest distance of the query" to an ordered complete hit list"""
-    out = []
-    i = 0
-    while i < len(all_hits):
-        j = i
-        while j < len(all_hits) and all_hits[j]["query"] == all_hits[i]["query"]:
-            j += 1
-        grp = all_hits[i:j]
-        kth = grp[k - 1]["dist"] if len(grp) >= k else 0xFFFFFFFF
-        out.append(grp[grp["dist"] <= kth])
-        i = j
-    return np.concatenate(out) if out else all_hits[:0]
+    n = len(all_hits)
+    if n == 0:
+        return all_hits[:0]
+    q = all_hits["query"]
+    starts = np.r_[0, np.nonzero(q[1:] != q[:-1])[0] + 1]
+    sizes = np.diff(np.r_[starts, n])
+    kth = np.where(sizes >= k, all_hits["dist"][np.minimum(starts + k - 1, n - 1)], np.uint32(0xFFFFFFFF))
+    return all_hits[all_hits["dist"] <= np.repeat(kth, sizes)]
 
 
 # ------------------------------------------------------------------------------ scan vs oracle
@@ -319,18 +316,147 @@ def test_grow_and_retry_is_never_stale():
 
 
 def test_dense_hits_overflow_path():
-    """every pair qualifies: more rows than the device scratch holds -> query range is split"""
+    """every pair qualifies: 7M rows do not fit the 4M-row list, so collect_range grows the list to the exact count the
+    fixed-bound scan reported and scans once more (7M <= 2^27: no split of the query range)"""
     rng = np.random.default_rng(8)
     s = rng.integers(0, 4, size=(70000, 16), dtype=np.uint8)
     q = rng.integers(0, 4, size=(100, 16), dtype=np.uint8)
     store = smafa_amd.SubjectStore(16, 0)
     store.push(s)
-    got = store.scan(q, max_divergence=16)  # 7M rows > 4M scratch rows
-    assert len(got) == 70000 * 100
-    d = (s[got["subject"][::997]] != q[got["query"][::997]]).sum(axis=1)
-    assert (d == got["dist"][::997]).all()
-    key = got["query"].astype(np.int64) << 40 | got["dist"].astype(np.int64) << 32 | got["subject"]
-    assert (np.diff(key) > 0).all()
+    got = store.scan(q, max_divergence=16)  # 7M rows > 4M list rows
+    assert store.last_call_stats()["scans"] == 2  # the scan that overflowed, the scan into the grown list
+    want = oracle.scan_codes(s, q, 16)
+    assert len(want) == 70000 * 100
+    assert got.tobytes() == want.tobytes()
+    store.close()
+
+
+# Host answers to a full row list (engine.hip collect_range / scan_to_host / filter_rows_kernel) at their real sizes: the list
+# starts at 2^22 rows, the tightening scratch holds max(2 cap, min(nq * 128, 2^27)) rows.  The buffers only grow on a handle,
+# so each scenario has a fresh store.  Every scenario proves its path by the number of scans of the call.
+LIST = 1 << 22
+
+
+def _family_store(L, alphabet, n_letters, family, others, rng, switches=()):
+    """a store of `family` copies of one row and `others` random rows, shuffled; -> (store, rows, base)"""
+    base = rng.integers(0, n_letters, size=L, dtype=np.uint8)
+    s = np.concatenate([np.tile(base, (family, 1)), rng.integers(0, n_letters, size=(others, L), dtype=np.uint8)])
+    s = s[rng.permutation(len(s))]
+    old = {k: os.environ.get(k) for k, _ in switches}
+    os.environ.update(dict(switches))
+    try:
+        store = smafa_amd.SubjectStore(L, alphabet)  # (switches are read when the handle is created)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    store.push(s)
+    return store, s, base
+
+
+def _best_hit_equals_oracle(store, s, q, D=None):
+    """best hit, ONE smafa_scan_hits call with room for the oracle's answer (SubjectStore.scan would retry a call whose rows did
+    not fit its first buffer from the kept rows, which names no kernels); -> (rows, scans of the call)"""
+    want = expected_with_k(oracle.scan_codes(s, q, s.shape[1] if D is None else D), 1)
+    got = np.zeros(len(want) + 1, dtype=smafa_amd.HIT_DTYPE)
+    n_out = C.c_uint64(0)
+    rc = _lib.lib().smafa_scan_hits(store._h, q.ctypes.data, len(q), _lib.NONE if D is None else D, 1, got.ctypes.data,
+                                    len(got), C.byref(n_out))
+    assert rc == 0, (rc, _lib.lib().smafa_last_error())
+    got = got[: n_out.value]
+    assert len(got) == len(want) and got.tobytes() == want.tobytes(), (len(got), len(want))
+    return got, store.last_call_stats()["scans"]
+
+
+def test_k_mode_overflowing_scratch_halves_the_query_range():
+    """100 queries equal to 100k identical subjects, best hit without a bound: 10M ties at distance 0"""
+    rng = np.random.default_rng(31)
+    store, s, base = _family_store(16, 0, 4, 100_000, 3_000, rng)
+    q = np.tile(base, (100, 1))
+    got, scans = _best_hit_equals_oracle(store, s, q)
+    assert len(got) == 100 * 100_000 > LIST
+    # 1: the ladder's first step (bound 2) appends 10M rows to its 2^23-row scratch: filter_rows_kernel reports cap + 1, the
+    #    step breaks to the full path;
+    # 1: the full path's tightening scan [0, 100) overflows its scratch in the same way: halved;
+    # 3: [0, 50) fits its scratch but keeps 5M > 2^22 rows: halved again, [0, 25) and [25, 50) fit (the latter sorted on the
+    #    device with q_begin = 25);
+    # 3: the same for [50, 100)
+    assert scans == 8, scans
+    store.close()
+
+
+def test_one_query_with_more_rows_than_the_list():
+    """2^22 + 2^16 subjects, all but 1000 identical, and three queries equal to them, best hit: ~4.26M ties per query"""
+    rng = np.random.default_rng(32)
+    n = LIST + (1 << 16)
+    store, s, base = _family_store(16, 0, 4, n - 1000, 1000, rng)
+    q = np.tile(base, (3, 1))
+    got, scans = _best_hit_equals_oracle(store, s, q)
+    assert len(got) == 3 * (n - 1000) and n - 1000 > LIST
+    # (three queries: no ladder)
+    # 1: [0, 3) appends 12.8M rows to a 2^23-row scratch: cap + 1, halved;
+    # 2: [0, 1) keeps 4.26M > 2^22 rows and is one query: the list grows to max(count, n) = n rows, and it is scanned again;
+    # 3: [1, 3) keeps 2 x 4.26M > n rows: halved, [1, 2) and [2, 3) fit the grown list
+    assert scans == 6, scans
+    store.close()
+
+
+def test_fixed_first_attempt_overflows_while_the_k_attempt_fits():
+    """bound L and k = 1: every pair qualifies (8 x 600k rows), few tie at the minimum"""
+    rng = np.random.default_rng(33)
+    store, s, base = _family_store(16, 0, 4, 1000, 599_000, rng)
+    q = np.concatenate([np.tile(base, (4, 1)), s[rng.integers(0, len(s), size=4)]])
+    got, scans = _best_hit_equals_oracle(store, s, q, D=16)
+    assert len(oracle.scan_codes(s, q[:1], 16)) * len(q) > LIST and len(got) < LIST
+    # (eight queries: no ladder) 1: the fixed-bound attempt counts 4.8M rows > 2^22; 1: the k attempt fits
+    assert scans == 2, scans
+    store.close()
+
+
+@pytest.mark.parametrize("alphabet,n_letters", [(0, 4), (1, 20)])
+def test_ladder_index_step_overflowing_continues(alphabet, n_letters):
+    """a current block index answers the ladder's first step and finds more rows than the list holds: the ladder goes on to
+    its tightening steps.  100 queries equal to 50k identical subjects, best hit without a bound"""
+    rng = np.random.default_rng(34 + alphabet)
+    # (the index may probe a block whose runs are as long as the family, as in the census's `index` switch set)
+    switches = (("SMAFA_INDEX_MAX_RUN", "100000000"), ("SMAFA_INDEX_CAND", "100"))
+    store, s, base = _family_store(60, alphabet, n_letters, 50_000, 10_000, rng, switches)
+    info = store.build_index(6)
+    assert info["current"] and info["max_div_served"] >= 6, info
+    q = np.tile(base, (100, 1))
+    got, scans = _best_hit_equals_oracle(store, s, q)
+    assert len(got) == 100 * 50_000 > LIST
+    assert any("index_probe_kernel" in k for k in store.last_call_kernels()), store.last_call_kernels()
+    # 1: the index step (every pair within the served bound: 5M rows > 2^22) -> continue;
+    # 1: the tightening step at 12 keeps 5M > 2^22 rows -> break to the full path;
+    # 3: the full path's [0, 100) does not fit, its halves do
+    assert scans == 5, scans
+    store.close()
+
+
+@pytest.mark.parametrize("subs", [0, 8], ids=["queries_equal_the_family", "queries_8_to_10_away"])
+def test_ladder_sampled_probes_too_dense(subs):
+    """2048 amino-acid queries, best hit, a family of 17k identical subjects: a 256-query sample alone has 4.35M > 2^22 rows.
+    subs = 0: the first step's probe sample is too dense to look at: the step runs (its scratch overflows) and breaks to the
+    full path.  subs = 8: the probe at bound 5 finishes nobody, so the step is skipped and the later steps are planned from a
+    sample at bound 30, which is too dense to look at (its k-th distances are taken as 0)."""
+    rng = np.random.default_rng(35 + subs)
+    L, family = 60, 17_000
+    store, s, base = _family_store(L, 1, 20, family, 3_000, rng)
+    q = np.tile(base, (2048, 1))
+    for r in q if subs else ():
+        for c in rng.choice(L, size=int(rng.integers(subs, subs + 3)), replace=False):
+            r[c] = (int(r[c]) + 1 + int(rng.integers(0, 19))) % 20
+    got, scans = _best_hit_equals_oracle(store, s, q)
+    assert len(got) == 2048 * family
+    # the full path: [0, 2048) halved down to ranges of 128 queries (256 x 17k rows > 2^22, 128 x 17k fit): 1 + 2 + 4 + 8 + 16
+    tree = 31
+    if subs == 0:
+        assert scans == 1 + 1 + tree, scans  # the probe sample, the step at 5 (scratch overflow), the full path
+    else:
+        assert scans == 1 + 1 + 1 + tree, scans  # the probe, the plan's sample, the step at 12 (scratch overflow), the full path
     store.close()
 
 
