@@ -150,6 +150,7 @@ struct smafa_db {
     uint32_t count_first_k = 3;  // smallest k whose loose-bound scans count first and append second (SMAFA_COUNT_FIRST_K)
     bool ladder_probe = true;    // the ladder's first step is asked of a 256-query sample before the whole batch pays for it (SMAFA_LADDER_PROBE=0)
     bool zone_direct = true;     // fixed-bound zone launches without LDS staging and barriers (SMAFA_ZONE_DIRECT=0: the staged form)
+    int zone_key_gate = -1;      // ScanArgs::key_gate (SMAFA_ZONE_KEY_GATE; 65: no key test); -1: by alphabet (kernels.hip.h)
     bool lazy_fold = true;       // the filter-plane-resident kernel also at the bounds only its level 2 rejects at (SMAFA_LAZY_FOLD=0)
     bool kth_hist_seed = true;   // k >= 2: the seed bound from an LDS histogram over the first tiles (SMAFA_KTH_HIST_SEED=0: a counting launch)
     uint32_t kth_sample_min_tiles = 4096;  // stores below this many wave tiles (1M subjects) count everything first (SMAFA_KTH_SAMPLE_MIN_TILES)
@@ -842,7 +843,10 @@ static double index_cand_limit(const smafa_db *db, uint32_t thr0) {
     double per_subject = db->index_cand_per_subject;
     if (per_subject < 0.0) {
         const bool prunes = prefilter_prunes(db, thr0);
-        const double scan_s = db->W <= 4 && use_zone(db, thr0, prunes) ? 8e-14 * std::min(1.0, std::max(0.02, zone_pass_share(db, thr0)))
+        // (two-word amino-acid stores: the zone kernel's key test cuts its time per pass-share to ~1/3, 2.7e-14 —
+        // 10M x 10k bound 5: 1.69 -> 0.56 ms, profiles/r05_zone_keys.txt; nucleotides at bound 3: 2.69 -> 2.54 ms, kept at 8e-14)
+        const double zone_s = db->W == 2 && db->alphabet == SMAFA_ALPHABET_AA ? 2.7e-14 : 8e-14;
+        const double scan_s = db->W <= 4 && use_zone(db, thr0, prunes) ? zone_s * std::min(1.0, std::max(0.02, zone_pass_share(db, thr0)))
                               : fold_rejects(db, thr0) || prunes        ? 8e-14
                                                                         : 1.2e-13;
         per_subject = 0.45 * scan_s / 0.025e-9;
@@ -978,6 +982,17 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
     a.order = db->d_order;
     a.zone = db->d_zone;
     a.zone_on = (wide && !zone && !seed && db->W > 4 && zone_pays(db, thr0, true)) ? 1u : 0u;
+    // the key sets of scan_zone_kernel<.., DIRECT> (two-word stores): X and Z split filter word 1's L - 32 columns, KB each where
+    // they fit (60 columns, KB = 12: X = columns 32..43, Z = 44..55); Y, word 0's last KB columns, is fixed
+    {
+        const uint32_t n1 = db->L > 32u ? std::min(db->L - 32u, 32u) : 0u, kb = (uint32_t)SMAFA_ZONE_KEY_BITS;
+        const uint32_t xw = n1 >= 2u * kb ? kb : n1 / 2u;
+        a.key_xmask = xw ? (uint32_t)((1ull << xw) - 1ull) : 0u;
+        a.key_zlo = xw;
+        a.key_gate = db->zone_key_gate >= 0                  ? (uint32_t)db->zone_key_gate
+                     : db->alphabet == SMAFA_ALPHABET_AA ? (uint32_t)SMAFA_ZONE_KEY_GATE
+                                                         : (uint32_t)SMAFA_ZONE_KEY_GATE_NT;
+    }
     const uint64_t n_qblocks = (q_end - q_begin + a.qb_size - 1) / a.qb_size;
     // non-temporal loads (scan_lazy_kernel's filter words, scan_kernel's tiles): where a cached copy is never read again — one
     // query block, or more bytes per query block than the 256 MiB Infinity Cache holds until the next one comes round
@@ -1792,6 +1807,7 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *cv = getenv("SMAFA_COUNT_FIRST_K")) db->count_first_k = (uint32_t)std::max(2, atoi(cv));
     if (const char *lp = getenv("SMAFA_LADDER_PROBE")) db->ladder_probe = atoi(lp) != 0;
     if (const char *zd = getenv("SMAFA_ZONE_DIRECT")) db->zone_direct = atoi(zd) != 0;
+    if (const char *kg = getenv("SMAFA_ZONE_KEY_GATE")) db->zone_key_gate = std::min(65, std::max(0, atoi(kg)));
     if (const char *lf = getenv("SMAFA_LAZY_FOLD")) db->lazy_fold = atoi(lf) != 0;
     if (const char *ks = getenv("SMAFA_KTH_HIST_SEED")) db->kth_hist_seed = atoi(ks) != 0;
     if (const char *ks = getenv("SMAFA_KTH_SAMPLE")) db->kth_sample_div = (uint32_t)std::max(0, atoi(ks));

@@ -119,6 +119,10 @@ struct ScanArgs {
     const uint4 *zone;          // per wave tile: {bits all its subjects share in filter word 0, which bits those are,
                                 //                 the same for word 1} — see zone_kernel
     uint32_t zone_on;           // scan_wide_kernel: apply the zone level (the store is sorted well enough for it to pay)
+    // scan_zone_kernel<.., DIRECT>, two-word stores: the key sets of the pigeonhole test behind the zone level (see
+    // zone_key_sets).  Set X = filter word 1 & key_xmask, set Z = bits key_zlo.. of word 1; key_gate: the test runs for a
+    // (chunk, tile) with at least this many zone survivors (65: never)
+    uint32_t key_xmask, key_zlo, key_gate;
     uint32_t stream_once;       // the launch has ONE query block (every store byte it touches is read once), or what a query
                                 // block reads is too big for the Infinity Cache to keep until the next one: scan_lazy_kernel
                                 // then loads its filter words (scan_kernel: its tiles) with the non-temporal hint (no cache line is kept for a
@@ -995,6 +999,35 @@ constexpr int kFewTiles = SMAFA_FEW_TILES;  // wave tiles per wave in scan_zone_
 #ifndef SMAFA_ZONE_WAVES_DIRECT_AA
 #define SMAFA_ZONE_WAVES_DIRECT_AA 7  // the unstaged five-plane two-word kernel (see zone_tiles)
 #endif
+// Pigeonhole key test between the zone level and level 1 (unstaged two-word kernels).  The zone level counts k columns in
+// which every subject of a tile mismatches the query; a hit in that tile then has at most b = bound - k mismatches in the
+// other columns.  Take disjoint column sets of the filter plane — Y: word 0 bits 32-KB..31, X: word 1 & key_xmask, Z: word
+// 1 bits key_zlo..key_zlo+KB-1 (ScanArgs; bits past the row length are zero in subjects and queries alike) — and let a key be
+// a subject's filter bits on one set.  A hit matches the query exactly on at least NS - b of the NS sets, once the query's
+// bits on the columns the tile shares are replaced by the tile's own (q ^ ((q ^ common) & shared): the zone level's masked
+// word, already at hand).  So with one 2^KB-bit bitmap per (tile, set) of the keys its subjects have — built per wave in LDS
+// in the prologue — a survivor whose found sets and budget b add up to less than NS cannot have a hit in the tile.  Lane per
+// query like the zone level: 64 queries at a time, one LDS gather per set, instead of level 1's serial iteration per survivor.
+// Extra keys in a bitmap (padding rows of the last tile) only let more through: the row list is the same set.
+#ifndef SMAFA_ZONE_KEYS
+#define SMAFA_ZONE_KEYS 3  // key sets: 0 (no key test), 2 (Y and X) or 3 (Y, X and Z)
+#endif
+#ifndef SMAFA_ZONE_KEY_BITS
+#define SMAFA_ZONE_KEY_BITS 12  // bits per key: 2^KB-bit bitmaps (12: 512 bytes per tile and set)
+#endif
+// ScanArgs::key_gate by alphabet (run-time: SMAFA_ZONE_KEY_GATE, for both; 65 turns the test off).  Same box, ms per launch
+// (profiles/r05_zone_keys.txt): aa 10M x 10k bound 5, gate 0 / 1 / 2 / 3 / 5: 0.566 / 0.562 / 0.575 / 0.564 / 0.570 (no test: 1.67);
+// nt 10M x 100k bound 3, gate 1 / 2 / 3 / 6 / off: 2.73 / 2.54 / 2.69 / 3.19 / 3.24 (no test in the kernel: 2.69)
+#ifndef SMAFA_ZONE_KEY_GATE
+#define SMAFA_ZONE_KEY_GATE 3  // amino acids
+#endif
+#ifndef SMAFA_ZONE_KEY_GATE_NT
+#define SMAFA_ZONE_KEY_GATE_NT 2  // nucleotides
+#endif
+__host__ __device__ constexpr int zone_key_sets(int w, bool direct) { return direct && w == 2 ? SMAFA_ZONE_KEYS : 0; }
+static_assert(SMAFA_ZONE_KEYS == 0 || SMAFA_ZONE_KEYS == 2 || SMAFA_ZONE_KEYS == 3, "SMAFA_ZONE_KEYS: 0, 2 or 3");
+static_assert(SMAFA_ZONE_KEY_BITS >= 8 && SMAFA_ZONE_KEY_BITS <= 16, "SMAFA_ZONE_KEY_BITS: 8..16");
+
 __host__ __device__ constexpr int zone_min_waves(int ps, int w, bool direct = false) {
     return (direct && ps == 5 && w == 2 && SMAFA_ZONE_TILES == 4) ? SMAFA_ZONE_WAVES_DIRECT_AA
            : ps * w <= 4 ? SMAFA_ZONE_WAVES_4 : (ps == 3 && w == 2) ? SMAFA_ZONE_WAVES_6 : ps * w <= 10 ? SMAFA_ZONE_WAVES_10 : 4;
@@ -1025,12 +1058,18 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     __shared__ uint4 stage[2][kChunk * RV];
     __shared__ uint32_t nu_lds[2][kChunk];  // !FIXED: ~bound of the staged queries
     __shared__ RowStageT<(WGW == 1 ? 64 : kStageRows)> rs;
+    // DIRECT, two words: per wave, one bitmap of the subjects' keys per (tile slot, key set) — see zone_key_sets
+    constexpr int NS = zone_key_sets(W, DIRECT);
+    constexpr int KB = SMAFA_ZONE_KEY_BITS;
+    constexpr int KW = (1 << KB) / 32;  // u32 words per bitmap
+    __shared__ uint4 keymap[NS ? WGW * T * NS * KW / 4 : 1];
     int buf = 0;  // LDS buffer of the chunk being computed = parity of the row stage it appends to
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     const uint32_t wave = tid >> 6;
-    if (tid == 0) rs.n[0] = rs.n[1] = 0;  // published by the barrier in front of the chunk loop
+    if ((!DIRECT || NS == 0) && tid == 0) rs.n[0] = rs.n[1] = 0;  // published by the barrier in front of the chunk loop (the key
+                                                                   // test's kernels leave the unused row stage out of LDS)
     const uint32_t wg_tile = blockIdx.x % a.n_wg_tiles;
     const uint32_t qblock = blockIdx.x / a.n_wg_tiles;
     const uint32_t tile0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.tile_begin + (wg_tile * WGW + wave) * T));
@@ -1073,6 +1112,48 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
         if (kMaskInVgpr) asm volatile("v_mov_b32 %0, %1" : "=v"(zmv[t]) : "s"(zm0[t]));
     }
     const bool zone_w1 = W > 1 && __ballot(vz.w != 0u) != 0ull;
+    // (with the key test: word 1's zone words in scalar registers too — vz then dies here instead of being spilled)
+    uint32_t zc1s[T], zm1s[T];
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        zc1s[t] = NS > 0 ? (uint32_t)__builtin_amdgcn_readlane((int)vz.z, t) : 0u;
+        zm1s[t] = NS > 0 ? (uint32_t)__builtin_amdgcn_readlane((int)vz.w, t) : 0u;
+    }
+
+    // the keys of a filter word pair (word 0, word 1) — subjects as they are, queries with the tile's shared bits substituted
+    auto key_y = [&](uint32_t w0) -> uint32_t { return w0 >> (32 - KB); };
+    auto key_x = [&](uint32_t w1) -> uint32_t { return w1 & a.key_xmask; };
+    auto key_z = [&](uint32_t w1) -> uint32_t { return __builtin_amdgcn_ubfe(w1, a.key_zlo, KB); };
+    // this wave's bitmaps: u32 word j of (tile slot t, set s) at km[(t * NS + s) * KW + j]
+    uint32_t *const km = reinterpret_cast<uint32_t *>(keymap) + (size_t)__builtin_amdgcn_readfirstlane((int)wave) * (T * NS * KW);
+    if constexpr (NS > 0) {
+        // Wave-private: no barrier, only this wave's own LDS operations in order (the compiler must not move them across).
+        uint4 *const km4 = reinterpret_cast<uint4 *>(km);
+#pragma unroll
+        for (int i = 0; i < T * NS * KW / 4; i += 64)
+            if (i + 64 <= T * NS * KW / 4 || i + (int)lane < T * NS * KW / 4) km4[i + lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int t = 0; t < T; t++) {
+            const bool live = (uint32_t)t < n_live;
+            const uint4 f1 = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
+            const uint32_t w0[4] = {f0[t].x, f0[t].y, f0[t].z, f0[t].w};
+            const uint32_t w1[4] = {f1.x, f1.y, f1.z, f1.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t ky = key_y(w0[k]), kx = key_x(w1[k]);
+                atomicOr(&km[(t * NS + 0) * KW + (ky >> 5)], 1u << (ky & 31u));
+                atomicOr(&km[(t * NS + 1) * KW + (kx >> 5)], 1u << (kx & 31u));
+                if (NS > 2) {
+                    const uint32_t kz = key_z(w1[k]);
+                    atomicOr(&km[(t * NS + (NS > 2 ? 2 : 0)) * KW + (kz >> 5)], 1u << (kz & 31u));
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
 
     // Query chunks are staged by LDS-DMA (global_load_lds_dwordx4: global -> LDS with no register hop; a register
     // prefetch was being spilled across every chunk).  The records carry no bound in this kernel: FIXED takes the scalar
@@ -1200,13 +1281,36 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                     const uint32_t tile = tile0 + t;
                     const uint32_t zc = SMAFA_ZONE_SGPR_ZONE ? zc0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.x, (int)t);
                     const uint32_t zm = SMAFA_ZONE_SGPR_ZONE ? zm0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.y, (int)t);
-                    uint32_t u = __builtin_popcount((hq0 ^ zc) & (kMaskInVgpr ? zmv[t] : zm)) + hnu;
+                    const uint32_t d0 = (hq0 ^ zc) & (kMaskInVgpr ? zmv[t] : zm);  // the columns counted
+                    uint32_t u = __builtin_popcount(d0) + hnu;
+                    uint32_t d1 = 0;
                     if (zone_w1) {
-                        const uint32_t zc1 = (uint32_t)__builtin_amdgcn_readlane((int)vz.z, (int)t);
-                        const uint32_t zm1 = (uint32_t)__builtin_amdgcn_readlane((int)vz.w, (int)t);
-                        u += __builtin_popcount((hq1 ^ zc1) & zm1);
+                        const uint32_t zc1 = NS > 0 ? zc1s[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.z, (int)t);
+                        const uint32_t zm1 = NS > 0 ? zm1s[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.w, (int)t);
+                        d1 = (hq1 ^ zc1) & zm1;
+                        u += __builtin_popcount(d1);
                     }
                     unsigned long long m = __ballot((int32_t)u < 0);  // queries of the chunk this tile cannot exclude
+                    if constexpr (NS > 0) {
+                        // ---- key test (where enough queries survive for it to pay): ~u = the survivor's budget b
+                        if ((uint32_t)__builtin_popcountll(m) >= a.key_gate) {
+                            bool pass = false;
+                            if ((int32_t)u < 0) {
+                                const uint32_t s0 = hq0 ^ d0, s1 = hq1 ^ d1;  // the query, the tile's shared bits substituted
+                                const uint32_t ky = key_y(s0), kx = key_x(s1);
+                                const uint32_t vy = km[(t * NS + 0) * KW + (ky >> 5)];
+                                const uint32_t vx = km[(t * NS + 1) * KW + (kx >> 5)];
+                                uint32_t found = ((vy >> (ky & 31u)) & 1u) + ((vx >> (kx & 31u)) & 1u);
+                                if (NS > 2) {
+                                    const uint32_t kz = key_z(s1);
+                                    const uint32_t vz_ = km[(t * NS + (NS > 2 ? 2 : 0)) * KW + (kz >> 5)];
+                                    found += (vz_ >> (kz & 31u)) & 1u;
+                                }
+                                pass = found + ~u >= (uint32_t)NS;
+                            }
+                            m = __ballot(pass);
+                        }
+                    }
                     const uint4 ft = f0[t];
                     while (m != 0ull) {
                         const int i = __builtin_ctzll(m);
