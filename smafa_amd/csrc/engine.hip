@@ -843,9 +843,10 @@ static double index_cand_limit(const smafa_db *db, uint32_t thr0) {
     double per_subject = db->index_cand_per_subject;
     if (per_subject < 0.0) {
         const bool prunes = prefilter_prunes(db, thr0);
-        // (two-word amino-acid stores: the zone kernel's key test cuts its time per pass-share to ~1/3, 2.7e-14 —
-        // 10M x 10k bound 5: 1.69 -> 0.56 ms, profiles/r05_zone_keys.txt; nucleotides at bound 3: 2.69 -> 2.54 ms, kept at 8e-14)
-        const double zone_s = db->W == 2 && db->alphabet == SMAFA_ALPHABET_AA ? 2.7e-14 : 8e-14;
+        // (two-word amino-acid stores: the zone kernel's key test cuts its time per pass-share to ~0.3 of that, 2.4e-14 —
+        // 10M x 10k bound 5: 1.69 -> 0.56 ms, profiles/r05_zone_keys.txt, -> 0.50 ms with the key work hoisted per chunk,
+        // profiles/r06_zone_hoist.txt; nucleotides at bound 3: 2.69 -> 2.54 ms, kept at 8e-14)
+        const double zone_s = db->W == 2 && db->alphabet == SMAFA_ALPHABET_AA ? 2.4e-14 : 8e-14;
         const double scan_s = db->W <= 4 && use_zone(db, thr0, prunes) ? zone_s * std::min(1.0, std::max(0.02, zone_pass_share(db, thr0)))
                               : fold_rejects(db, thr0) || prunes        ? 8e-14
                                                                         : 1.2e-13;

@@ -1024,6 +1024,15 @@ constexpr int kFewTiles = SMAFA_FEW_TILES;  // wave tiles per wave in scan_zone_
 #ifndef SMAFA_ZONE_KEY_GATE_NT
 #define SMAFA_ZONE_KEY_GATE_NT 2  // nucleotides
 #endif
+// 1: a wave whose tiles share no key column (zone mask & key columns == 0 for every tile slot: the sorted 10M-row stores, whose
+// ~15 shared bits are word 0's leading columns) forms the three keys' LDS addresses and bit positions ONCE per chunk — substituting
+// the tile's shared bits is the identity on the key columns there — and runs the chunk in two phases: zone level and key test of
+// all its tiles, then the survivor loops (the hoisted values die before the first loop, whose rare levels use every register).
+// Waves with a tile that does share a key column (dense families, duplicates, small stores) keep the per-tile form.
+// 0: the per-tile form only.
+#ifndef SMAFA_ZONE_KEY_HOIST
+#define SMAFA_ZONE_KEY_HOIST 1
+#endif
 __host__ __device__ constexpr int zone_key_sets(int w, bool direct) { return direct && w == 2 ? SMAFA_ZONE_KEYS : 0; }
 static_assert(SMAFA_ZONE_KEYS == 0 || SMAFA_ZONE_KEYS == 2 || SMAFA_ZONE_KEYS == 3, "SMAFA_ZONE_KEYS: 0, 2 or 3");
 static_assert(SMAFA_ZONE_KEY_BITS >= 8 && SMAFA_ZONE_KEY_BITS <= 16, "SMAFA_ZONE_KEY_BITS: 8..16");
@@ -1124,6 +1133,16 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     auto key_y = [&](uint32_t w0) -> uint32_t { return w0 >> (32 - KB); };
     auto key_x = [&](uint32_t w1) -> uint32_t { return w1 & a.key_xmask; };
     auto key_z = [&](uint32_t w1) -> uint32_t { return __builtin_amdgcn_ubfe(w1, a.key_zlo, KB); };
+    // no tile slot of this wave shares a key column (slots past the range: zone words 0): a query's keys on this wave's tiles
+    // are then its own filter bits — see SMAFA_ZONE_KEY_HOIST
+    constexpr bool kHoist = NS > 0 && SMAFA_ZONE_KEY_HOIST;
+    bool key_hoist = false;
+    if constexpr (kHoist) {
+        uint32_t shared_keys = 0;
+#pragma unroll
+        for (int t = 0; t < T; t++) shared_keys |= key_y(zm0[t]) | key_x(zm1s[t]) | (NS > 2 ? key_z(zm1s[t]) : 0u);
+        key_hoist = shared_keys == 0u;
+    }
     // this wave's bitmaps: u32 word j of (tile slot t, set s) at km[(t * NS + s) * KW + j]
     uint32_t *const km = reinterpret_cast<uint32_t *>(keymap) + (size_t)__builtin_amdgcn_readfirstlane((int)wave) * (T * NS * KW);
     if constexpr (NS > 0) {
@@ -1276,9 +1295,8 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                 // `break` and a `continue` the compiler threaded a state variable through the four bodies: ~10 scalar
                 // instructions of pure control flow between two tiles, which counts where few queries survive a tile —
                 // nucleotides at bound 3: scalar instructions 1.5 per 1024 pairs against 1.7 vector ones.)
-                auto do_tile = [&](auto slot) {
+                auto zone_keys = [&](auto slot) -> unsigned long long {
                     constexpr uint32_t t = decltype(slot)::value;
-                    const uint32_t tile = tile0 + t;
                     const uint32_t zc = SMAFA_ZONE_SGPR_ZONE ? zc0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.x, (int)t);
                     const uint32_t zm = SMAFA_ZONE_SGPR_ZONE ? zm0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.y, (int)t);
                     const uint32_t d0 = (hq0 ^ zc) & (kMaskInVgpr ? zmv[t] : zm);  // the columns counted
@@ -1311,6 +1329,11 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                             m = __ballot(pass);
                         }
                     }
+                    return m;
+                };
+                auto survivors = [&](auto slot, unsigned long long m) {
+                    constexpr uint32_t t = decltype(slot)::value;
+                    const uint32_t tile = tile0 + t;
                     const uint4 ft = f0[t];
                     while (m != 0ull) {
                         const int i = __builtin_ctzll(m);
@@ -1372,14 +1395,81 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                     }
                 };
                 static_assert(T <= 8, "tile slots are spelled out below");
-                if (SMAFA_ZONE_NLIVE ? nl > 0u : tile0 + 0u < a.tile_end) do_tile(std::integral_constant<uint32_t, 0>{});
-                if (T > 1 && (SMAFA_ZONE_NLIVE ? nl > 1u : tile0 + 1u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 1 ? 1 : 0)>{});
-                if (T > 2 && (SMAFA_ZONE_NLIVE ? nl > 2u : tile0 + 2u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 2 ? 2 : 0)>{});
-                if (T > 3 && (SMAFA_ZONE_NLIVE ? nl > 3u : tile0 + 3u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 3 ? 3 : 0)>{});
-                if (T > 4 && (SMAFA_ZONE_NLIVE ? nl > 4u : tile0 + 4u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 4 ? 4 : 0)>{});
-                if (T > 5 && (SMAFA_ZONE_NLIVE ? nl > 5u : tile0 + 5u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 5 ? 5 : 0)>{});
-                if (T > 6 && (SMAFA_ZONE_NLIVE ? nl > 6u : tile0 + 6u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 6 ? 6 : 0)>{});
-                if (T > 7 && (SMAFA_ZONE_NLIVE ? nl > 7u : tile0 + 7u < a.tile_end)) do_tile(std::integral_constant<uint32_t, (T > 7 ? 7 : 0)>{});
+                auto each_slot = [&](auto &&f) {  // f(tile slot as a compile-time constant), slots 0 .. T - 1 in order
+                    f(std::integral_constant<uint32_t, 0>{});
+                    if constexpr (T > 1) f(std::integral_constant<uint32_t, 1>{});
+                    if constexpr (T > 2) f(std::integral_constant<uint32_t, 2>{});
+                    if constexpr (T > 3) f(std::integral_constant<uint32_t, 3>{});
+                    if constexpr (T > 4) f(std::integral_constant<uint32_t, 4>{});
+                    if constexpr (T > 5) f(std::integral_constant<uint32_t, 5>{});
+                    if constexpr (T > 6) f(std::integral_constant<uint32_t, 6>{});
+                    if constexpr (T > 7) f(std::integral_constant<uint32_t, 7>{});
+                };
+                static_assert(!kHoist || (SMAFA_ZONE_NLIVE && SMAFA_ZONE_SGPR_ZONE),
+                              "the two-phase form of the key-test kernels is written for SMAFA_ZONE_NLIVE = SMAFA_ZONE_SGPR_ZONE = 1");
+                if constexpr (kHoist) {
+                    // Two phases: zone level and key test of every tile slot first (one survivor mask per slot, in scalars),
+                    // then the survivor loops — what the first phase keeps per chunk is dead before the first loop.
+                    unsigned long long ms[T];
+                    if (key_hoist) {
+                        // the keys (v_bfe_u32 takes the low 5 bits of one as the bit position by itself) and their bitmap words' LDS
+                        // addresses from the head alone; per tile there remain 3 gathers at immediate offsets.  (The address is
+                        // formed in one opaque instruction: as plain arithmetic the compiler re-adds the base in front of every
+                        // gather.)
+                        // (Computed for every chunk, 9 VALU, also where no tile reaches the gate or the test is off, gate 65.)
+                        const uint32_t ky = key_y(hq0), kx = key_x(hq1), kz = NS > 2 ? key_z(hq1) : 0u;
+                        typedef const __attribute__((address_space(3))) uint32_t *lds_u32;
+                        const uint32_t km_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)km;
+                        auto word_of = [&](uint32_t key) -> uint32_t {  // LDS address of word key >> 5 of (tile slot 0, set 0)
+                            uint32_t at;
+                            asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(at) : "v"(key >> 5), "s"(km_lds));
+                            return at;
+                        };
+                        const uint32_t ay = word_of(ky), ax = word_of(kx), az = NS > 2 ? word_of(kz) : 0u;
+                        // lanes past the block are masked out of the ballot (scalar) instead of out of ~bound (per lane)
+                        const unsigned long long in_block = ~0ull >> (64u - nqc);
+                        auto hoisted = [&](auto with_w1) {
+                            auto one = [&](auto slot) -> unsigned long long {
+                                constexpr uint32_t t = decltype(slot)::value;
+                                uint32_t u = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
+                                if (decltype(with_w1)::value) u += __builtin_popcount((hq1 ^ zc1s[t]) & zm1s[t]);
+                                unsigned long long m = __builtin_amdgcn_ballot_w64((int32_t)u < 0) & in_block;
+                                // (This scalar branch per tile keeps the tiles' gathers apart: each tile still waits out its own
+                                // LDS latency, the 3 x T gathers do NOT issue back to back — profiles/r06_zone_hoist.txt.)
+                                if ((uint32_t)__builtin_popcountll(m) >= a.key_gate) {
+                                    // found sets + budget ~u >= NS  <=>  u - found < -NS; lanes that did not survive keep u >= 0
+                                    if ((int32_t)u < 0) {
+                                        uint32_t found = __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(ay + ((t * NS + 0) * KW) * 4u), ky, 1) +
+                                                         __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(ax + ((t * NS + 1) * KW) * 4u), kx, 1);
+                                        if (NS > 2) found += __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(az + ((t * NS + (NS > 2 ? 2 : 0)) * KW) * 4u), kz, 1);
+                                        u -= found;
+                                    }
+                                    asm("" : "+v"(u));  // (or the compare is moved into the `if` and its lane mask rebuilt behind it)
+                                    m &= __builtin_amdgcn_ballot_w64((int32_t)u < -(int32_t)NS);
+                                }
+                                return m;
+                            };
+                            each_slot([&](auto slot) {  // (an active wave's slot 0 is inside the range)
+                                constexpr uint32_t t = decltype(slot)::value;
+                                ms[t] = t == 0u || nl > t ? one(slot) : 0ull;
+                            });
+                        };
+                        // word 1's share of the zone level under a scalar branch: it is rare (zone_w1)
+                        if (zone_w1) hoisted(std::true_type{});
+                        else hoisted(std::false_type{});
+                    } else {
+                        each_slot([&](auto slot) {
+                            constexpr uint32_t t = decltype(slot)::value;
+                            ms[t] = t == 0u || nl > t ? zone_keys(slot) : 0ull;
+                        });
+                    }
+                    each_slot([&](auto slot) { survivors(slot, ms[decltype(slot)::value]); });
+                } else {
+                    each_slot([&](auto slot) {
+                        constexpr uint32_t t = decltype(slot)::value;
+                        if (SMAFA_ZONE_NLIVE ? nl > t : tile0 + t < a.tile_end) survivors(slot, zone_keys(slot));
+                    });
+                }
                 // an exact comparison from L2 costs ~60 VALU per (query, tile) pair, the dense walk below ~25 for EVERY
                 // pair of the chunk (4 tiles x nqc): switch when more than ~2/5 of the pairs got that far
                 filter_on = passes * 5u <= nqc * 8u;
