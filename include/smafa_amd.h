@@ -227,6 +227,33 @@ int smafa_index_info(const smafa_db *db, smafa_index_info_t *info);
  * time as the build would (rent or buy: at most twice the best choice in hindsight).  Results are identical in every mode. */
 int smafa_set_index(smafa_db *db, int mode);
 
+/* ---------------------------------------------------------------- the self-join */
+/*
+ * "Which of the store's own rows are near each other": every unordered pair {i, j}, i != j, of the store's subjects with
+ * distance <= max_div, exactly once, as smafa_hit{query = min(i, j), subject = max(i, j), dist} (subject numbers = append
+ * order, as everywhere else).  Not in the reference; the neighbour list behind dereplication and single-linkage clustering.
+ * Rows never visit the host: blocks of the sorted store's own bit-planes become query records on the device, each block is
+ * scanned with the fixed-bound kernels of smafa_scan_launch against the part of the store from the block's span onwards only,
+ * and a filter pass keeps each pair once.  (Only where 64 rows alone have more rows within the bound than the join's scratch
+ * list may hold — millions of near-identical subjects — the call fails: SMAFA_ERR_NOMEM, the count in smafa_last_error(); the handle stays usable.)  Equal rows (distance 0) are pairs like any other; an empty or one-row store gives
+ * none; max_div >= seq_len gives all n(n-1)/2 pairs; max_div = SMAFA_NONE is SMAFA_ERR_INVALID.
+ * smafa_set_prefilter / smafa_set_zone_level / smafa_set_index keep their meaning (a current block index answers the
+ * blocks, modes 2 / 3 may build one on the way); the rows are the same under every setting.
+ *
+ * smafa_db_self_launch: device-resident form.  d_hits = device buffer of cap rows, unordered on return; *d_count (device
+ * uint64) = the exact number of qualifying pairs at ANY capacity — only the first cap rows to arrive are stored; cap = 0 with
+ * d_hits = NULL counts only.  The call synchronises the handle's stream between its blocks (it sizes its scratch list from
+ * each block's row count) and once at its end; smafa_sync is still the documented way to wait for the results.
+ * smafa_last_scan_ms / smafa_last_call_stats then hold the device time and launches of all its blocks (record building,
+ * scans and filter passes), smafa_last_call_kernels the scan-family instantiations it launched followed by the join's own
+ * kernels (smafa_join::...).
+ *
+ * smafa_db_self_hits: host form, rows ordered by (query, dist, subject).  cap = capacity of `out` in rows; if more pairs
+ * qualify: SMAFA_ERR_CAPACITY, *n_out = rows needed — grow and retry.  Nothing is kept for the retry: it scans again.
+ */
+int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count);
+int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -358,6 +385,10 @@ int smafa_cluster_sharded(const char *input_fasta, uint32_t max_divergence, int 
  * every batch — the input is parsed and de-duplicated once for all of them, and the two exchanges per batch go through memory.
  * Output bytes do not depend on ndev (src/cluster.rs:13-94 semantics). */
 int smafa_cluster_multi(const char *input_fasta, uint32_t max_divergence, int out_fd, const int *devices, int ndev, int alphabet);
+/* `smafa pairs` (not in the reference): the DB file (version 2 / 3 or a packed store file, as smafa_query takes them) is
+ * loaded on `device`, and every pair of its subjects within max_divergence (smafa_db_self_hits) is written to out_fd as
+ * "{i}\t{j}\t{distance}\n", i < j, in (i, distance, j) order. */
+int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

@@ -194,6 +194,27 @@ class SubjectStore:
         check(lib().smafa_scan_each(self._h, qset._h, _opt(max_divergence), C.c_void_p(d_hits), cap_per_query,
                                     C.c_void_p(d_counts), 1 if use_graph else 0))
 
+    # ---- the self-join ---------------------------------------------------------------------
+    def self_pairs(self, max_divergence: int, first_cap: int = 1 << 16) -> np.ndarray:
+        """Every unordered pair of the store's own subjects within max_divergence, once, as rows (query = the smaller subject
+        number, subject = the larger, dist), ordered (query, dist, subject) — smafa_db_self_hits; `first_cap` rows are offered
+        first, and the buffer grows to what the call asks for."""
+        cap = max(int(first_cap), 0)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            n_out = C.c_uint64(0)
+            rc = lib().smafa_db_self_hits(self._h, _opt(max_divergence), out.ctypes.data, cap, C.byref(n_out))
+            if rc == _lib.ERR_CAPACITY:
+                cap = int(n_out.value)
+                continue
+            check(rc)
+            return out[: n_out.value]
+
+    def self_launch(self, max_divergence: int, d_hits: int, cap: int, d_count: int) -> None:
+        """device-resident self-join (smafa_db_self_launch): rows unordered in d_hits, the exact pair count in *d_count"""
+        check(lib().smafa_db_self_launch(self._h, _opt(max_divergence), C.c_void_p(d_hits) if d_hits else None, cap,
+                                         C.c_void_p(d_count) if d_count else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -455,3 +476,8 @@ def count(paths, out_fd: int = 1) -> None:
     """count(paths) — src/lib.rs:378-398."""
     arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
     check(lib().smafa_count(arr, len(paths), out_fd))
+
+
+def pairs(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa pairs`: every pair i < j of the DB file's own subjects within max_divergence, "i\\tj\\tdist" lines to out_fd."""
+    check(lib().smafa_pairs(os.fsencode(db_path), _opt(max_divergence), out_fd, device))

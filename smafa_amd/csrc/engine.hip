@@ -18,6 +18,7 @@
 #include "host/packed.h"
 #include "kernels.hip.h"
 #include "index.hip.h"
+#include "join.hip.h"
 
 namespace smafa {
 
@@ -144,6 +145,7 @@ struct smafa_db {
     smafa_qset scratch_q;     // query set of smafa_scan_hits / smafa_distances
     smafa_qset scratch_q2;    // the compacted batch of queries the near-hit probe did not finish
     smafa_qset scratch_q3;    // the sample of open queries the later steps of the ladder are planned from
+    smafa_qset join_q;        // the self-join's block of store rows as query records (store_records_kernel)
     bool two_phase = true;    // near-hit probe before the tightening path (SMAFA_TWO_PHASE=0 disables)
     bool fold3 = true;        // scan_kernel's all-planes-but-the-last bound for launches whose bound starts above 32 (SMAFA_FOLD3=0)
     bool stream_nt = true;    // one-query-block launches of scan_lazy_kernel load their filter words non-temporally (SMAFA_STREAM_NT=0)
@@ -185,6 +187,21 @@ struct smafa_db {
                                            // < 0: by the bound's class — index_cand_limit)
     uint64_t index_min_rows = 65536;  // mode 2 builds an index for stores of at least this many subjects (SMAFA_INDEX_MIN_ROWS)
     uint32_t index_probes = 0;      // launches answered by the index over the handle's life (smafa_index_info)
+    // ---- self-join (smafa_db_self_launch, join.hip.h)
+    struct JoinState {
+        DevBuf pos_of;  // subject number -> position, the inverse of d_order; tied to the store's state like the index
+        bool valid = false;
+        uint64_t generation = 0, n = 0;
+        uint32_t resorts = 0;
+        DevBuf out, cnt;  // rows of the host form (smafa_db_self_hits) on their way to the caller, and their counter
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin, records done, scan done, filter done
+        double rec_ms = 0, scan_ms = 0, filter_ms = 0;            // per stage, over the blocks of the last join
+        uint32_t blocks = 0, rescans = 0;
+    } join;
+    uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
+    uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
+    uint64_t join_scratch_max = 1ull << 27;  // rows the block's scratch list may grow to (1.5 GB) before the block is halved (SMAFA_JOIN_SCRATCH_MAX)
+    bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
     uint64_t hits_cap() const { return hits.cap / sizeof(smafa_hit); }
 };
@@ -1027,11 +1044,14 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
 // in segments that grow 8x per launch (bounds tighten between launches), after a seed launch over the first segment
 // that only lowers the bounds and appends nothing.  Rows are appended to a scratch list while the bounds are still
 // running; filter_rows_kernel then keeps the ones within the final bounds.
+// tile_begin (fixed-bound form only): the scan kernels start at that wave tile — the self-join's triangular cut; an index
+// probe has no tile range and answers over the whole store.
 static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q_end, uint32_t max_div,
-                      uint32_t k_tight, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count) {
+                      uint32_t k_tight, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count, uint32_t tile_begin = 0) {
     const uint32_t nq = q_end - q_begin;
     db->last_launches = 0;
     db->timed = false;
+    db->call_timed = false;
     if (nq == 0 || db->n == 0) {
         HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
         return SMAFA_OK;
@@ -1082,7 +1102,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         const bool own = nq <= 64u;
         if (own) hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, db->stream, (uint32_t *)d_count, 0u, (uint64_t)2);
         HIP_TRY(hipEventRecord(db->ev0, db->stream));
-        int rc = launch_tiles(db, qs, q_begin, q_end, 0, n_tiles, 0, thr0, d_hits, cap, own ? nullptr : d_count, false,
+        int rc = launch_tiles(db, qs, q_begin, q_end, tile_begin, n_tiles, 0, thr0, d_hits, cap, own ? nullptr : d_count, false,
                               own ? d_count : nullptr);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(db->ev1, db->stream));
@@ -1263,8 +1283,10 @@ __global__ void keys_to_rows_kernel(const unsigned long long *keys, uint64_t n, 
 
 // Sort db->hits[0..count) by (query, dist, subject) in place with a device radix sort; returns false (and leaves
 // the rows untouched) when the key does not fit 64 bits — the caller then orders them on the host.
-static int sort_rows_on_device(smafa_db *db, uint64_t count, uint32_t q_begin, uint32_t q_end, bool *sorted) {
+static int sort_rows_on_device(smafa_db *db, uint64_t count, uint32_t q_begin, uint32_t q_end, bool *sorted,
+                               smafa_hit *rows = nullptr) {
     *sorted = false;
+    if (!rows) rows = db->hits.as<smafa_hit>();  // (the self-join orders its own list)
     uint32_t dist_bits = 1;
     while ((1u << dist_bits) <= db->L) dist_bits++;
     uint32_t q_bits = 1;
@@ -1275,16 +1297,14 @@ static int sort_rows_on_device(smafa_db *db, uint64_t count, uint32_t q_begin, u
     if (rc) return rc;
     unsigned long long *ka = db->keys_a.as<unsigned long long>(), *kb = db->keys_b.as<unsigned long long>();
     const uint32_t blocks = (uint32_t)((count + 255) / 256);
-    hipLaunchKernelGGL(rows_to_keys_kernel, dim3(blocks), dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, q_begin,
-                       dist_bits, ka);
+    hipLaunchKernelGGL(rows_to_keys_kernel, dim3(blocks), dim3(256), 0, db->stream, rows, count, q_begin, dist_bits, ka);
     size_t tmp_bytes = 0;
     const int end_bit = (int)(32 + dist_bits + q_bits);
     HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ka, kb, (int)count, 0, end_bit, db->stream));
     rc = db->sort_tmp.ensure(tmp_bytes);
     if (rc) return rc;
     HIP_TRY(hipcub::DeviceRadixSort::SortKeys(db->sort_tmp.p, tmp_bytes, ka, kb, (int)count, 0, end_bit, db->stream));
-    hipLaunchKernelGGL(keys_to_rows_kernel, dim3(blocks), dim3(256), 0, db->stream, kb, count, q_begin, dist_bits,
-                       db->hits.as<smafa_hit>());
+    hipLaunchKernelGGL(keys_to_rows_kernel, dim3(blocks), dim3(256), 0, db->stream, kb, count, q_begin, dist_bits, rows);
     HIP_TRY(hipGetLastError());
     *sorted = true;
     return SMAFA_OK;
@@ -1367,6 +1387,156 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
         return collect_range(db, qs, q_begin, q_end, max_div, max_num_hits, out);
     }
     return fetch_rows(db, count, q_begin, q_end, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The self-join (smafa_db_self_launch; kernels: join.hip.h): every unordered pair of the store's subjects within max_div.
+// The store is walked in SPANS of join_stride x join_block consecutive positions.  A span's rows become query records on
+// the device (store_records_kernel), dealt round-robin into join_stride BLOCKS: block b holds the span's positions b,
+// b + S, b + 2S, ...  Per block the fixed-bound scan runs its records against the wave tiles from the span's first one to the
+// end of the store — tiles in front of the span could only repeat pairs an earlier span has found — into the handle's
+// scratch list, and join_filter_kernel moves the rows with position(query) < position(subject) to the caller's list.
+// Why interleaved: the store is sorted by filter bits, so a block of CONSECUTIVE positions is 65 536 rows that all pass the
+// zone level on the same few tiles and fail it on the rest — the surviving work of a launch sits in a few workgroups
+// (measured: profiles/r07_self_join.txt, stride 1 against 16).  Rows a whole span apart differ in all but its few leading bits.
+// The host waits for each block's scan to learn its row count: a piece that overflowed the scratch list is scanned again with
+// the list grown to that count (exact at any capacity), or cut in half once the list would pass join_scratch_max rows; the
+// reduced piece size is kept until a piece's count falls under a quarter of that ceiling.
+static bool join_inverse_current(const smafa_db *db) {
+    const auto &j = db->join;
+    return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
+}
+
+static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count) {
+    auto &J = db->join;
+    db->call_kernels.clear();
+    db->call_ms = 0.f;
+    db->call_launches = db->call_scans = 0;
+    db->last_launches = 0;
+    db->timed = false;
+    J.rec_ms = J.scan_ms = J.filter_ms = 0.0;
+    J.blocks = J.rescans = 0;
+    int rc = use_device(db);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
+    db->call_timed = true;
+    if (db->n < 2) return SMAFA_OK;
+    rc = maybe_resort(db);  // once, in front: positions are final for the whole join
+    if (rc) return rc;
+    for (hipEvent_t &e : J.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    rc = db->count.ensure(sizeof(unsigned long long));
+    if (!rc && db->hits_cap() < (1ull << 22)) rc = db->hits.ensure((1ull << 22) * sizeof(smafa_hit));
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)db->n;
+    bool inverted = false;
+    if (!join_inverse_current(db)) {
+        J.valid = false;
+        rc = J.pos_of.ensure((size_t)n * sizeof(uint32_t));
+        if (rc) return rc;
+        hipLaunchKernelGGL(smafa_join::inverse_order_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, db->d_order, n,
+                           J.pos_of.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        J.generation = db->generation;
+        J.n = db->n;
+        J.resorts = db->resorts;
+        J.valid = true;
+        inverted = true;
+        db->call_launches++;
+    }
+    smafa_qset *qs = &db->join_q;
+    qs->db = db;
+    bool filtered = false, filter_pending = false;
+    auto take_filter_time = [&]() {  // the filter of the piece before: finished by the time a later wait returns
+        float ms = 0.f;
+        if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.filter_ms += ms;
+        filter_pending = false;
+    };
+    const uint64_t span_rows = db->join_block * db->join_stride;
+    uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
+    for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
+        const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
+        const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
+        const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
+        // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
+        const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
+        qs->nq = (uint64_t)S * R;
+        qs->serial = g_qset_serial.fetch_add(1);
+        rc = qs->qrec.ensure(padded * db->QS * sizeof(uint32_t));
+        if (!rc) rc = qs->thr.ensure(padded * sizeof(uint32_t));
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
+        const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
+        hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0, db->stream,
+                           reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0, (uint32_t)p1, S, R,
+                           qs->qrec.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+        db->call_launches++;
+        bool rec_timed = false;
+        for (uint32_t b = 0; b < S; b++) {
+            const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
+            for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
+                const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
+                rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, max_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
+                                db->count.as<unsigned long long>(), t0);
+                if (rc) return rc;
+                unsigned long long count = 0;
+                HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+                HIP_TRY(hipStreamSynchronize(db->stream));
+                take_filter_time();
+                const float before = db->call_ms;
+                note_call_scan(db);
+                const double scan_ms = db->call_ms - before;
+                J.scan_ms += scan_ms;
+                float ms = 0.f;
+                if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
+                rec_timed = true;
+                log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
+                         (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
+                if (count > db->hits_cap()) {
+                    J.rescans++;
+                    if (count <= db->join_scratch_max) {  // the count is exact: room for it, and the same piece once more
+                        rc = db->hits.ensure(count * sizeof(smafa_hit));
+                        if (rc) return rc;
+                        continue;
+                    }
+                    if (q1 - q0 > 64) {
+                        piece = std::max<uint64_t>(64, ((q1 - q0) / 2 + 63) / 64 * 64);
+                        continue;
+                    }
+                    // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
+                    return set_error(SMAFA_ERR_NOMEM,
+                                     "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
+                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, max_div, (unsigned long long)db->join_scratch_max);
+                }
+                if (count) {
+                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                    hipLaunchKernelGGL(smafa_join::join_filter_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
+                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
+                                       J.pos_of.as<uint32_t>(), d_hits, (unsigned long long)cap, d_count);
+                    HIP_TRY(hipGetLastError());
+                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                    filter_pending = filtered = true;
+                    db->call_launches++;
+                }
+                J.blocks++;
+                q0 = q1;
+                if (piece < db->join_block && count * 4 < db->join_scratch_max) piece = std::min<uint64_t>(db->join_block, piece * 2);
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(db->stream));  // the span's records are overwritten next
+        take_filter_time();
+    }
+    db->call_ms += (float)(J.rec_ms + J.filter_ms);
+    db->call_timed = true;  // (scan_range cleared it)
+    note_call_kernel(db, "smafa_join::store_records_kernel");
+    if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
+    if (filtered) note_call_kernel(db, "smafa_join::join_filter_kernel");
+    log_line(2, "self-join of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, filter %.3f ms", n,
+             max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.filter_ms);
+    return SMAFA_OK;
 }
 
 void db_life_stats(const smafa_db *db, double *kernel_ms, uint64_t *launches) {
@@ -1825,6 +1995,9 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *iv = getenv("SMAFA_INDEX_MAX_RUN")) db->index_max_run = std::max<uint64_t>(1, strtoull(iv, nullptr, 10));
     if (const char *iv = getenv("SMAFA_INDEX_CAND")) db->index_cand_per_subject = atof(iv);
     if (const char *iv = getenv("SMAFA_INDEX_MIN_ROWS")) db->index_min_rows = std::max<uint64_t>(1, strtoull(iv, nullptr, 10));
+    if (const char *jv = getenv("SMAFA_JOIN_BLOCK")) db->join_block = std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64);
+    if (const char *jv = getenv("SMAFA_JOIN_STRIDE")) db->join_stride = std::min<uint64_t>(4096, std::max<uint64_t>(1, strtoull(jv, nullptr, 10)));
+    if (const char *jv = getenv("SMAFA_JOIN_SCRATCH_MAX")) db->join_scratch_max = std::max<uint64_t>(4096, strtoull(jv, nullptr, 10));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) db->n_cu = prop.multiProcessorCount;
     hipError_t e = hipStreamCreateWithFlags(&db->own_stream, hipStreamNonBlocking);
@@ -1954,8 +2127,11 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->idx_a, &db->idx_b, &db->d_perm, &db->d_tab, &db->scratch_q.qrec,
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
-                      &db->index.stats, &db->index.rows})
+                      &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt,
+                      &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
+    for (hipEvent_t e : db->join.ev)
+        if (e) (void)hipEventDestroy(e);
     if (db->each_graph) (void)hipGraphExecDestroy(db->each_graph);
     if (db->ev0) (void)hipEventDestroy(db->ev0);
     if (db->ev1) (void)hipEventDestroy(db->ev1);
@@ -2199,6 +2375,7 @@ int smafa_scan_each(smafa_db *db, smafa_qset *qs, uint32_t max_div, void *d_hits
     if (rc) return rc;
     db->last_launches = 0;
     db->timed = false;
+    db->call_timed = false;
     const uint32_t nq = (uint32_t)qs->nq;
     if (nq == 0) return SMAFA_OK;
     if (db->n == 0) {
@@ -2299,7 +2476,11 @@ int smafa_sync(smafa_db *db) try {
 int smafa_last_scan_ms(smafa_db *db, float *ms, uint32_t *n_launches) try {
     if (!db || !ms) return set_error(SMAFA_ERR_INVALID, "smafa_last_scan_ms: NULL argument");
     *ms = 0.f;
-    if (n_launches) *n_launches = db->last_launches;
+    if (n_launches) *n_launches = db->call_timed ? db->call_launches : db->last_launches;
+    if (db->call_timed) {  // a self-join: the totals over its blocks (each block was timed and waited for as it ran)
+        *ms = db->call_ms;
+        return SMAFA_OK;
+    }
     if (!db->timed) return SMAFA_OK;
     HIP_TRY(hipEventSynchronize(db->ev1));
     HIP_TRY(hipEventElapsedTime(ms, db->ev0, db->ev1));
@@ -2356,6 +2537,60 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_scan_hits");
+}
+
+int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL handle");
+    if (!d_count) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL count");
+    if (!d_hits && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL row buffer with a capacity");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: a self-join needs a bound (max_div)");
+    return self_join(db, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_launch");
+}
+
+int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL handle");
+    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL count");
+    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL row buffer with a capacity");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: a self-join needs a bound (max_div)");
+    *n_out = 0;
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    const uint64_t all_pairs = db->n < 2 ? 0 : db->n * (db->n - 1) / 2;
+    const uint64_t room = std::min<uint64_t>(cap, all_pairs);
+    rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));
+    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
+    if (rc) return rc;
+    rc = self_join(db, max_div, J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
+    if (rc) return rc;
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    *n_out = count;
+    if (count > cap)
+        return set_error(SMAFA_ERR_CAPACITY, "hit buffer too small: %llu rows needed, capacity %llu", count, (unsigned long long)cap);
+    if (count) {
+        bool sorted = false;
+        if (count >= 4096) {
+            rc = sort_rows_on_device(db, count, 0, (uint32_t)db->n, &sorted, J.out.as<smafa_hit>());
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out, J.out.p, count * sizeof(smafa_hit), hipMemcpyDeviceToHost, db->stream));
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        if (!sorted) std::sort(out, out + count, hit_less);
+    }
+    if (J.out.cap > (512ull << 20)) J.out.release();
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    if (db->keys_a.cap > (512ull << 20)) {
+        db->keys_a.release();
+        db->keys_b.release();
+        db->sort_tmp.release();
+    }
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_hits");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -140,6 +140,16 @@ int expect_fastx(int rc, const char *what) {
 
 namespace {
 
+// does the DB file start like a packed store file (host/packed.cpp)?  Unreadable files are left to the reader that follows.
+bool db_file_is_packed(const char *db_path) {
+    uint8_t head[8] = {0};
+    FILE *f = fopen(db_path, "rb");
+    if (!f) return false;
+    const size_t got = fread(head, 1, sizeof head, f);
+    fclose(f);
+    return is_packed_file(head, got);
+}
+
 struct DbGuard {
     smafa_db *db = nullptr;
     ~DbGuard() { smafa_db_destroy(db); }
@@ -384,16 +394,7 @@ int smafa_query_multi(const char *db_path, const char *query_fasta, uint32_t max
     } warm(devices, ndev);
     log_line(1, "Decoding db file \"%s\"", db_path);  // src/lib.rs:206
     PackedStore pk;  // a packed store file is mapped, not decoded (host/packed.cpp)
-    bool packed = false;
-    {
-        uint8_t head[8] = {0};
-        FILE *f = fopen(db_path, "rb");
-        if (f) {
-            const size_t got = fread(head, 1, sizeof head, f);
-            fclose(f);
-            packed = is_packed_file(head, got);
-        }
-    }
+    const bool packed = db_file_is_packed(db_path);
     int rc;
     if (packed) {
         rc = pk.open(db_path);
@@ -583,6 +584,69 @@ int smafa_query(const char *db_path, const char *query_fasta, uint32_t max_diver
     return smafa_query_multi(db_path, query_fasta, max_divergence, max_num_hits, limit_per_sequence, out_fd, &device, 1);
 } catch (...) {
     return smafa::exception_code("smafa_query");
+}
+
+// -------------------------------------------------------------------------------------- pairs
+// The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair.
+int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    std::thread warm(warm_device, device);  // device bring-up overlaps the file read
+    struct Join {
+        std::thread &t;
+        ~Join() {
+            if (t.joinable()) t.join();
+        }
+    } warm_guard{warm};
+    log_line(1, "Decoding db file \"%s\"", db_path);
+    const bool packed = db_file_is_packed(db_path);
+    DbGuard store;
+    int rc;
+    if (packed) {
+        warm.join();
+        rc = smafa_db_load(&store.db, device, db_path);
+        if (rc) return rc;
+    } else {
+        int alphabet = 0;
+        uint64_t n = 0;
+        uint32_t L = 0;
+        FreeGuard codes;
+        uint8_t *rows = nullptr;
+        rc = smafa_dbfile_read(db_path, &alphabet, &rows, &n, &L);
+        if (rc) return rc;
+        codes.p = rows;
+        warm.join();
+        if (n == 0) return SMAFA_OK;  // an empty DB has no length to make a store of, and no pairs
+        rc = smafa_db_create(&store.db, device, alphabet, L);
+        if (!rc) rc = smafa_db_append(store.db, rows, n);
+        if (rc) return rc;
+    }
+    std::vector<smafa_hit> pairs((size_t)1 << 16);
+    uint64_t count = 0;
+    while ((rc = smafa_db_self_hits(store.db, max_divergence, pairs.data(), pairs.size(), &count)) == SMAFA_ERR_CAPACITY)
+        pairs.resize(count);
+    if (rc) return rc;
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // rows per write
+    for (size_t b0 = 0; b0 < count; b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(count, b0 + block); i < e; i++) {
+            append_u32(text, pairs[i].query);
+            text.push_back('\t');
+            append_u32(text, pairs[i].subject);
+            text.push_back('\t');
+            append_u32(text, pairs[i].dist);
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu pairs within %u, took %llu seconds", (unsigned long long)count, max_divergence,
+             (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_pairs");
 }
 
 // ------------------------------------------------------------------------------------ cluster

@@ -5,6 +5,7 @@
 //           [--limit-per-sequence INT]
 //   cluster -i/--input FILE  -d/--max-divergence INT
 //   count   -i/--input FILE...
+//   pairs   -d/--database FILE  --max-divergence INT   (this build only: every pair of the DB's own subjects within the bound)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -38,7 +39,9 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        Output columns (tab-separated): query number (0-indexed), subject number (0-indexed),\n"
             "        divergence, subject sequence (dashes and degenerate bases shown as N)\n"
             "cluster -i, --input <FILE>  -d, --max-divergence <INT>  [--alphabet nt|aa] [--device <N> | --gpus <N> | --devices <a,b,..>]\n"
-            "count   -i, --input <FILE>...\n");
+            "count   -i, --input <FILE>...\n"
+            "pairs   -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: every pair i < j of the\n"
+            "        database's own sequences within the bound, one \"i<TAB>j<TAB>divergence\" line each)\n");
     return 2;
 }
 
@@ -168,6 +171,10 @@ int main(int argc, char **argv) {
         }
         if (devices.empty()) devices.push_back((int)device);
         rc = smafa_cluster_multi(input, max_div, 1, devices.data(), (int)devices.size(), alphabet);
+    } else if (cmd == "pairs") {
+        if (!database) return usage("pairs needs --database");
+        if (!have_max_div) return usage("pairs needs --max-divergence");
+        rc = smafa_pairs(database, max_div, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);

@@ -94,6 +94,21 @@ while time.time() < t_end:
             print("MISMATCH round", rounds - 1, "seed", seed0, dict(alphabet=alphabet, n_letters=n_letters, L=L, n=n, nq=nq, mode=mode, D=D, k=k, handles=handles,
                   env=env, got=len(got), want=len(want), plan=None if handles else store.last_scan_plan()), flush=True)
             sys.exit(1)
+    if not handles and len(s) <= 4097 and rng.random() < 0.5:
+        # a self-join draw against brute force: every pair i < j within D, ordered (i, dist, j); small stores only (the
+        # brute force is len(s)^2 / 2 row comparisons), in blocks small enough that the join takes several
+        D = int(rng.integers(0, min(L, 9) + 1))
+        dist = (s[:, None, :] != s[None, :, :]).sum(axis=2) if len(s) <= 1000 else np.stack([(s != r).sum(axis=1) for r in s])
+        i, j = np.nonzero(np.triu(dist <= D, 1))
+        order = np.lexsort((j, dist[i, j], i))
+        want = np.zeros(len(order), dtype=smafa_amd.HIT_DTYPE)
+        want["query"], want["subject"], want["dist"] = i[order], j[order], dist[i, j][order]
+        got = store.self_pairs(D, first_cap=int(rng.choice([0, 1000, 1 << 20])))
+        scans += 1
+        if got.tobytes() != want.tobytes():
+            print("SELF-JOIN MISMATCH round", rounds - 1, "seed", seed0, dict(alphabet=alphabet, n_letters=n_letters, L=L, n=len(s), mode=mode,
+                  D=D, env=env, got=len(got), want=len(want), kernels=store.last_call_kernels()), flush=True)
+            sys.exit(1)
     store.close()
     if time.time() - t_note > 60:  # a line a minute: a silent run is taken for a hung one on the GPU box
         t_note = time.time()
