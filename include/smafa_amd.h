@@ -254,6 +254,40 @@ int smafa_set_index(smafa_db *db, int mode);
 int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count);
 int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out);
 
+/* ------------------------------------------------- single-linkage components of the store */
+/*
+ * "Which of the store's rows belong together at bound max_div": the graph whose vertices are the store's subjects (numbered in
+ * append order) and whose edges are the pairs at distance <= max_div — the self-join's pairs — and per subject i
+ * labels[i] = the SMALLEST subject number in i's connected component.  So labels[i] <= i, labels[labels[i]] == labels[i], the
+ * rows with labels[i] == i are the representatives (the first-appended member of each component) and *n_components is their
+ * number.  Not in the reference (`smafa cluster` is greedy and order-dependent; this is transitive and canonical).  The
+ * labels are fully determined by the store and max_div: the same bytes under smafa_set_prefilter / smafa_set_zone_level /
+ * smafa_set_index and every SMAFA_JOIN_* setting.
+ * The pairs never leave the device and are never listed for the caller: the self-join's blocks are scanned as for
+ * smafa_db_self_launch, and each block's scratch list is consumed in place by a concurrent union-find over one uint32 per
+ * subject (handle-owned scratch, 4 B per subject), the larger root hooked under the smaller; a last pass writes the labels.
+ * Output is n_subjects labels, however many pairs there are.  No filter pass and no inverse order map run.
+ * Equal rows (distance 0) are joined at any bound; an empty store gives 0 components and writes no label; one row gives
+ * labels = {0}, 1 component; max_div >= seq_len gives all zeros and 1 component (n >= 1; nothing is scanned);
+ * max_div = SMAFA_NONE is SMAFA_ERR_INVALID.  A NULL handle, labels or count is SMAFA_ERR_INVALID, and smafa_last_error()
+ * names the argument.  The self-join's one failure is inherited unchanged: where 64 rows alone have more rows within the
+ * bound than the scratch list may hold, SMAFA_ERR_NOMEM, and the handle stays usable.
+ *
+ * smafa_db_self_components_launch: device-resident form.  d_labels = device buffer of n_subjects uint32 (smafa_db_info),
+ * *d_n_components = device uint64.  Synchronisation as for smafa_db_self_launch: the call synchronises the handle's stream
+ * between its blocks and at its end; smafa_sync is still the documented way to wait for the results.
+ * smafa_last_scan_ms / smafa_last_call_stats then hold the device time and launches of record building, scans, link
+ * passes and the flatten pass; smafa_last_call_kernels lists the scan-family instantiations first, then
+ * smafa_join::store_records_kernel, then the smafa_cc:: kernels that ran.
+ *
+ * smafa_db_self_components: host form.  cap = capacity of `labels` in entries; cap < n_subjects is SMAFA_ERR_INVALID (the
+ * caller knows n_subjects from smafa_db_info; there is nothing to grow and retry).
+ */
+/* device form: d_labels = device buffer of n_subjects uint32; d_n_components = device uint64 */
+int smafa_db_self_components_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components);
+/* host form: cap = capacity of labels in entries, must be >= n_subjects */
+int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -389,6 +423,10 @@ int smafa_cluster_multi(const char *input_fasta, uint32_t max_divergence, int ou
  * loaded on `device`, and every pair of its subjects within max_divergence (smafa_db_self_hits) is written to out_fd as
  * "{i}\t{j}\t{distance}\n", i < j, in (i, distance, j) order. */
 int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa components` (not in the reference): the DB file (version 2 / 3 or a packed store file), loaded on `device` as for
+ * smafa_pairs, and per subject its label (smafa_db_self_components: the smallest subject number of its single-linkage
+ * component at max_divergence) as "{i}\t{label}\n", in subject order, to out_fd.  An empty DB writes nothing. */
+int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

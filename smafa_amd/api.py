@@ -215,6 +215,23 @@ class SubjectStore:
         check(lib().smafa_db_self_launch(self._h, _opt(max_divergence), C.c_void_p(d_hits) if d_hits else None, cap,
                                          C.c_void_p(d_count) if d_count else None))
 
+    # ---- single-linkage components ---------------------------------------------------------
+    def self_components(self, max_divergence: int) -> tuple[np.ndarray, int]:
+        """(labels, n_components): labels[i] = the smallest subject number in i's connected component of the graph whose edges
+        are the store's pairs within max_divergence (uint32, one per subject) — smafa_db_self_components.  The pairs stay
+        on the device."""
+        n = self.info().n_subjects
+        labels = np.zeros(max(n, 1), dtype=np.uint32)
+        count = C.c_uint64(0)
+        check(lib().smafa_db_self_components(self._h, _opt(max_divergence), labels.ctypes.data, n, C.byref(count)))
+        return labels[:n], int(count.value)
+
+    def self_components_launch(self, max_divergence: int, d_labels: int, d_n_components: int) -> None:
+        """device-resident form (smafa_db_self_components_launch): n_subjects uint32 labels in d_labels, the number of
+        components in *d_n_components (device uint64)"""
+        check(lib().smafa_db_self_components_launch(self._h, _opt(max_divergence), C.c_void_p(d_labels) if d_labels else None,
+                                                    C.c_void_p(d_n_components) if d_n_components else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -481,3 +498,9 @@ def count(paths, out_fd: int = 1) -> None:
 def pairs(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
     """`smafa pairs`: every pair i < j of the DB file's own subjects within max_divergence, "i\\tj\\tdist" lines to out_fd."""
     check(lib().smafa_pairs(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def components(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa components`: "i\\tlabel" per subject of the DB file, label = the smallest subject number of i's single-linkage
+    component at max_divergence, to out_fd."""
+    check(lib().smafa_components(os.fsencode(db_path), _opt(max_divergence), out_fd, device))

@@ -19,6 +19,7 @@
 #include "kernels.hip.h"
 #include "index.hip.h"
 #include "join.hip.h"
+#include "components.hip.h"
 
 namespace smafa {
 
@@ -194,8 +195,10 @@ struct smafa_db {
         uint64_t generation = 0, n = 0;
         uint32_t resorts = 0;
         DevBuf out, cnt;  // rows of the host form (smafa_db_self_hits) on their way to the caller, and their counter
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin, records done, scan done, filter done
+        DevBuf parent;    // components (components.hip.h): the union-find's parent[], 4 B per subject, live for one call
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin, records done, scan done, filter / link done
         double rec_ms = 0, scan_ms = 0, filter_ms = 0;            // per stage, over the blocks of the last join
+        double link_ms = 0, flatten_ms = 0;                       // components: init + link passes, the flatten launch
         uint32_t blocks = 0, rescans = 0;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
@@ -1402,35 +1405,60 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 // The host waits for each block's scan to learn its row count: a piece that overflowed the scratch list is scanned again with
 // the list grown to that count (exact at any capacity), or cut in half once the list would pass join_scratch_max rows; the
 // reduced piece size is kept until a piece's count falls under a quarter of that ceiling.
+// The driver has two consumers of a finished piece's list.  d_labels == nullptr: the join as above.  d_labels != nullptr
+// (smafa_db_self_components_launch): link_rows_kernel unites the two subjects of every row in J.parent (components.hip.h)
+// — no pos_of[], no filter, no rows for the caller — and after the last piece flatten_labels_kernel writes labels[i] = the
+// smallest subject number of i's component and counts the representatives into *d_count.  Spans, records, scans, the
+// wait for each count, the re-scan of an overflowing piece (a truncated list is never linked), the halving and the
+// SMAFA_ERR_NOMEM case are the same code for both.
 static bool join_inverse_current(const smafa_db *db) {
     const auto &j = db->join;
     return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
 }
 
-static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count) {
+static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count,
+                     uint32_t *d_labels = nullptr) {
     auto &J = db->join;
+    const bool linking = d_labels != nullptr;
     db->call_kernels.clear();
     db->call_ms = 0.f;
     db->call_launches = db->call_scans = 0;
     db->last_launches = 0;
     db->timed = false;
-    J.rec_ms = J.scan_ms = J.filter_ms = 0.0;
+    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = 0.0;
     J.blocks = J.rescans = 0;
     int rc = use_device(db);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
     db->call_timed = true;
-    if (db->n < 2) return SMAFA_OK;
-    rc = maybe_resort(db);  // once, in front: positions are final for the whole join
-    if (rc) return rc;
+    if (db->n < (linking ? 1u : 2u)) return SMAFA_OK;
+    // components of one row, or at a bound no two rows can exceed: nothing to scan (the second would list all n^2 pairs to
+    // learn "one component")
+    const bool no_scans = linking && (db->n < 2 || max_div >= db->L);
+    if (!no_scans) {
+        rc = maybe_resort(db);  // once, in front: positions are final for the whole join
+        if (rc) return rc;
+    }
     for (hipEvent_t &e : J.ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     rc = db->count.ensure(sizeof(unsigned long long));
-    if (!rc && db->hits_cap() < (1ull << 22)) rc = db->hits.ensure((1ull << 22) * sizeof(smafa_hit));
+    if (!rc && !no_scans && db->hits_cap() < (1ull << 22)) rc = db->hits.ensure((1ull << 22) * sizeof(smafa_hit));
     if (rc) return rc;
     const uint32_t n = (uint32_t)db->n;
     bool inverted = false;
-    if (!join_inverse_current(db)) {
+    if (linking) {  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
+        rc = J.parent.ensure((size_t)n * sizeof(uint32_t));
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+        if (max_div >= db->L) {
+            HIP_TRY(hipMemsetAsync(J.parent.p, 0, (size_t)n * sizeof(uint32_t), db->stream));
+        } else {
+            hipLaunchKernelGGL(smafa_cc::init_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n);
+            HIP_TRY(hipGetLastError());
+            db->call_launches++;
+        }
+        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+    } else if (!join_inverse_current(db)) {
         J.valid = false;
         rc = J.pos_of.ensure((size_t)n * sizeof(uint32_t));
         if (rc) return rc;
@@ -1446,15 +1474,18 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     }
     smafa_qset *qs = &db->join_q;
     qs->db = db;
-    bool filtered = false, filter_pending = false;
-    auto take_filter_time = [&]() {  // the filter of the piece before: finished by the time a later wait returns
+    bool filtered = false, linked = false, filter_pending = linking;  // (linking: the initialisation of parent[] is pending)
+    auto take_filter_time = [&]() {  // the filter / link pass of the piece before: finished by the time a later wait returns
         float ms = 0.f;
-        if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.filter_ms += ms;
+        if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) {
+            (linking ? J.link_ms : J.filter_ms) += ms;
+            if (linking) log_line(3, "components: parent[] %s, %.3f ms", linked ? "linked with a piece's rows" : "initialised", ms);
+        }
         filter_pending = false;
     };
     const uint64_t span_rows = db->join_block * db->join_stride;
     uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
-    for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
+    for (uint64_t p0 = 0; p0 < db->n && !no_scans; p0 += span_rows) {
         const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
         const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
         const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
@@ -1511,7 +1542,16 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
                                      "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
                                      "hold (%llu rows)", (unsigned long long)(q1 - q0), count, max_div, (unsigned long long)db->join_scratch_max);
                 }
-                if (count) {
+                if (count && linking) {  // (count <= capacity here: a truncated list was scanned again above)
+                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                    hipLaunchKernelGGL(smafa_cc::link_rows_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
+                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
+                                       J.parent.as<uint32_t>());
+                    HIP_TRY(hipGetLastError());
+                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                    filter_pending = linked = true;
+                    db->call_launches++;
+                } else if (count) {
                     HIP_TRY(hipEventRecord(J.ev[2], db->stream));
                     hipLaunchKernelGGL(smafa_join::join_filter_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
                                        dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
@@ -1528,6 +1568,28 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         }
         HIP_TRY(hipStreamSynchronize(db->stream));  // the span's records are overwritten next
         take_filter_time();
+    }
+    if (linking) {  // the kernel boundary makes every hook visible: labels[i] = root(i), representatives counted
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        take_filter_time();
+        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+        hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
+                           J.parent.as<uint32_t>(), n, d_labels, d_count);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+        db->call_launches++;
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms = ms;
+        db->call_ms += (float)(J.rec_ms + J.link_ms + J.flatten_ms);
+        db->call_timed = true;  // (scan_range cleared it)
+        if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+        if (max_div < db->L) note_call_kernel(db, "smafa_cc::init_labels_kernel");
+        if (linked) note_call_kernel(db, "smafa_cc::link_rows_kernel");
+        note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
+        log_line(2, "components of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, link %.3f ms, "
+                 "flatten %.3f ms", n, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms, J.flatten_ms);
+        return SMAFA_OK;
     }
     db->call_ms += (float)(J.rec_ms + J.filter_ms);
     db->call_timed = true;  // (scan_range cleared it)
@@ -2127,7 +2189,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->idx_a, &db->idx_b, &db->d_perm, &db->d_tab, &db->scratch_q.qrec,
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
-                      &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt,
+                      &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
                       &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
@@ -2591,6 +2653,45 @@ int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t 
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_hits");
+}
+
+int smafa_db_self_components_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL handle");
+    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL labels");
+    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL count");
+    if (max_div == SMAFA_NONE)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: components need a bound (max_div)");
+    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_components, (uint32_t *)d_labels);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_components_launch");
+}
+
+int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL handle");
+    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL labels");
+    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL count");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: components need a bound (max_div)");
+    *n_components = 0;
+    if (cap < db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: labels holds %llu entries, the store has %llu subjects",
+                         (unsigned long long)cap, (unsigned long long)db->n);
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    rc = J.out.ensure(std::max<uint64_t>(db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller: 4 B per subject
+    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
+    if (rc) return rc;
+    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>());
+    if (rc) return rc;
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    *n_components = count;
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_components");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

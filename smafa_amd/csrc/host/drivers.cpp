@@ -586,12 +586,11 @@ int smafa_query(const char *db_path, const char *query_fasta, uint32_t max_diver
     return smafa::exception_code("smafa_query");
 }
 
-// -------------------------------------------------------------------------------------- pairs
-// The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair.
-int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: a bound (max_divergence) is needed");
-    const double t_start = now_seconds();
+// ------------------------------------------------------------------- pairs and components: the store
+// The DB file of smafa_pairs / smafa_components on `device`: packed store files load as they lie, version 2 / 3 files are
+// decoded and appended.  *empty: the DB holds no row (no length to make a store of); store->db stays NULL.
+static int load_db_store(const char *db_path, int device, DbGuard *store, bool *empty) {
+    *empty = false;
     std::thread warm(warm_device, device);  // device bring-up overlaps the file read
     struct Join {
         std::thread &t;
@@ -600,28 +599,38 @@ int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int de
         }
     } warm_guard{warm};
     log_line(1, "Decoding db file \"%s\"", db_path);
-    const bool packed = db_file_is_packed(db_path);
-    DbGuard store;
-    int rc;
-    if (packed) {
+    if (db_file_is_packed(db_path)) {
         warm.join();
-        rc = smafa_db_load(&store.db, device, db_path);
-        if (rc) return rc;
-    } else {
-        int alphabet = 0;
-        uint64_t n = 0;
-        uint32_t L = 0;
-        FreeGuard codes;
-        uint8_t *rows = nullptr;
-        rc = smafa_dbfile_read(db_path, &alphabet, &rows, &n, &L);
-        if (rc) return rc;
-        codes.p = rows;
-        warm.join();
-        if (n == 0) return SMAFA_OK;  // an empty DB has no length to make a store of, and no pairs
-        rc = smafa_db_create(&store.db, device, alphabet, L);
-        if (!rc) rc = smafa_db_append(store.db, rows, n);
-        if (rc) return rc;
+        return smafa_db_load(&store->db, device, db_path);
     }
+    int alphabet = 0;
+    uint64_t n = 0;
+    uint32_t L = 0;
+    FreeGuard codes;
+    uint8_t *rows = nullptr;
+    int rc = smafa_dbfile_read(db_path, &alphabet, &rows, &n, &L);
+    if (rc) return rc;
+    codes.p = rows;
+    warm.join();
+    if (n == 0) {
+        *empty = true;
+        return SMAFA_OK;
+    }
+    rc = smafa_db_create(&store->db, device, alphabet, L);
+    if (!rc) rc = smafa_db_append(store->db, rows, n);
+    return rc;
+}
+
+// -------------------------------------------------------------------------------------- pairs
+// The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair.
+int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;  // (an empty DB has no pairs)
     std::vector<smafa_hit> pairs((size_t)1 << 16);
     uint64_t count = 0;
     while ((rc = smafa_db_self_hits(store.db, max_divergence, pairs.data(), pairs.size(), &count)) == SMAFA_ERR_CAPACITY)
@@ -647,6 +656,43 @@ int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int de
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_pairs");
+}
+
+// --------------------------------------------------------------------------------- components
+// The label of every subject of a DB file (smafa_db_self_components), printed "{i}\t{label}\n" in subject order.
+int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_components: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_components: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    std::vector<uint32_t> labels((size_t)info.n_subjects);
+    uint64_t count = 0;
+    rc = smafa_db_self_components(store.db, max_divergence, labels.data(), labels.size(), &count);
+    if (rc) return rc;
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // rows per write
+    for (size_t b0 = 0; b0 < labels.size(); b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(labels.size(), b0 + block); i < e; i++) {
+            append_u32(text, (uint32_t)i);
+            text.push_back('\t');
+            append_u32(text, labels[i]);
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu components of %llu sequences within %u, took %llu seconds", (unsigned long long)count,
+             (unsigned long long)labels.size(), max_divergence, (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_components");
 }
 
 // ------------------------------------------------------------------------------------ cluster

@@ -6,6 +6,7 @@
 //   cluster -i/--input FILE  -d/--max-divergence INT
 //   count   -i/--input FILE...
 //   pairs   -d/--database FILE  --max-divergence INT   (this build only: every pair of the DB's own subjects within the bound)
+//   components -d/--database FILE  --max-divergence INT   (this build only: the single-linkage component of every subject)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -41,7 +42,10 @@ static int usage(const char *msg, FILE *to = stderr) {
             "cluster -i, --input <FILE>  -d, --max-divergence <INT>  [--alphabet nt|aa] [--device <N> | --gpus <N> | --devices <a,b,..>]\n"
             "count   -i, --input <FILE>...\n"
             "pairs   -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: every pair i < j of the\n"
-            "        database's own sequences within the bound, one \"i<TAB>j<TAB>divergence\" line each)\n");
+            "        database's own sequences within the bound, one \"i<TAB>j<TAB>divergence\" line each)\n"
+            "components -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: single-linkage\n"
+            "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
+            "        smallest sequence number of its component)\n");
     return 2;
 }
 
@@ -175,6 +179,10 @@ int main(int argc, char **argv) {
         if (!database) return usage("pairs needs --database");
         if (!have_max_div) return usage("pairs needs --max-divergence");
         rc = smafa_pairs(database, max_div, 1, (int)device);
+    } else if (cmd == "components") {
+        if (!database) return usage("components needs --database");
+        if (!have_max_div) return usage("components needs --max-divergence");
+        rc = smafa_components(database, max_div, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);
