@@ -288,6 +288,38 @@ int smafa_db_self_components_launch(smafa_db *db, uint32_t max_div, void *d_labe
 /* host form: cap = capacity of labels in entries, must be >= n_subjects */
 int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
 
+/* ------------------------------------------------- single-linkage levels: the components at every bound 0 .. max_div */
+/*
+ * "At which bound do the store's rows belong together": the partitions of smafa_db_self_components at EVERY bound
+ * t = 0, 1, .. max_div, from one self-join.  labels is level-major, (max_div + 1) x n_subjects uint32:
+ * labels[t * n_subjects + i] = the smallest subject number in i's component of the graph whose edges are the pairs at
+ * distance <= t.  Row t is, byte for byte, what smafa_db_self_components(db, t) writes, and n_components[t]
+ * (max_div + 1 uint64) is what it counts.  The rows nest: labels[t+1][i] <= labels[t][i],
+ * labels[t+1][labels[t][i]] == labels[t+1][i], and the counts never increase with t.  Not in the reference.
+ * The join at the largest bound lists every pair within it together with its distance, so the partitions at the smaller
+ * bounds are in the same rows: the store is joined ONCE, at bound min(max_div, seq_len - 1), and each piece's scratch
+ * list is consumed in place by one union-find per scanned level (handle-owned scratch, 4 B x n_subjects x
+ * (min(max_div, seq_len - 1) + 1)); a row at distance d is united at every level from d upwards.  Levels t >= seq_len are
+ * all zeros with 1 component and are written without a scan.  The pairs never leave the device.
+ * The answer is a function of the store and max_div alone: the same bytes under smafa_set_prefilter /
+ * smafa_set_zone_level / smafa_set_index and every SMAFA_JOIN_* setting.
+ * An empty store writes no label and counts of 0; one row gives labels all 0 and counts all 1; max_div = SMAFA_NONE, a NULL
+ * handle, NULL labels or a NULL count is SMAFA_ERR_INVALID, and smafa_last_error() names the argument.  The self-join's one
+ * failure is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list; the handle stays usable),
+ * and a failed allocation of the levelled scratch is an error code like any other allocation of the handle's.
+ *
+ * smafa_db_self_levels_launch: device-resident form.  d_labels = device buffer of (max_div + 1) x n_subjects uint32,
+ * d_n_components = device buffer of max_div + 1 uint64.  Synchronisation as for smafa_db_self_components_launch.
+ * smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of record building, scans, link passes
+ * (the initialisation included) and the flatten pass; smafa_last_call_kernels lists the scan-family instantiations first,
+ * then smafa_join::store_records_kernel, then the smafa_lv:: kernels that ran.  No smafa_cc:: kernel is launched.
+ *
+ * smafa_db_self_levels: host form.  cap = capacity of `labels` in entries; cap < (max_div + 1) * n_subjects is
+ * SMAFA_ERR_INVALID.  n_components holds max_div + 1 entries.
+ */
+int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components);
+int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -427,6 +459,10 @@ int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int de
  * smafa_pairs, and per subject its label (smafa_db_self_components: the smallest subject number of its single-linkage
  * component at max_divergence) as "{i}\t{label}\n", in subject order, to out_fd.  An empty DB writes nothing. */
 int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa components --levels` (not in the reference): the same DB, and per subject its label at every bound 0 ..
+ * max_divergence (smafa_db_self_levels), "{i}\t{label_0}\t...\t{label_N}\n" in subject order.  Column t + 1 is the label
+ * column of smafa_components at bound t.  An empty DB prints nothing. */
+int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

@@ -34,6 +34,7 @@ EXPORTS = [
     "smafa_qsession_open", "smafa_qsession_info", "smafa_qsession_scan_part", "smafa_qsession_write", "smafa_qsession_close",
     "smafa_db_self_launch", "smafa_db_self_hits", "smafa_pairs",
     "smafa_db_self_components_launch", "smafa_db_self_components", "smafa_components",
+    "smafa_db_self_levels_launch", "smafa_db_self_levels", "smafa_component_levels",
     "smafa_makedb", "smafa_makedb_packed", "smafa_query", "smafa_query_multi", "smafa_cluster", "smafa_cluster_multi", "smafa_cluster_sharded", "smafa_count",
 ]
 
@@ -165,6 +166,9 @@ def lib() -> C.CDLL:
     l.smafa_db_self_components_launch.argtypes = [vp, C.c_uint32, vp, vp]
     l.smafa_db_self_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
     l.smafa_components.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.c_int]
+    l.smafa_db_self_levels_launch.argtypes = [vp, C.c_uint32, vp, vp]
+    l.smafa_db_self_levels.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
+    l.smafa_component_levels.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.c_int]
     l.smafa_count.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_int]
     _lib = l
     return l

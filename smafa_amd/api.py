@@ -232,6 +232,24 @@ class SubjectStore:
         check(lib().smafa_db_self_components_launch(self._h, _opt(max_divergence), C.c_void_p(d_labels) if d_labels else None,
                                                     C.c_void_p(d_n_components) if d_n_components else None))
 
+    # ---- single-linkage levels -------------------------------------------------------------
+    def self_component_levels(self, max_divergence: int) -> tuple[np.ndarray, list[int]]:
+        """(labels, counts): labels[t, i] = the label self_components(t) gives subject i, for every t = 0 .. max_divergence
+        (uint32, shape (max_divergence + 1, n_subjects)), counts[t] = its number of components — smafa_db_self_levels: one
+        join at the largest bound, one union-find per level.  The pairs stay on the device."""
+        n = self.info().n_subjects
+        levels = int(max_divergence) + 1 if max_divergence is not None and 0 <= int(max_divergence) < _lib.NONE else 1
+        labels = np.zeros(max(levels * n, 1), dtype=np.uint32)
+        counts = (C.c_uint64 * levels)()
+        check(lib().smafa_db_self_levels(self._h, _opt(max_divergence), labels.ctypes.data, levels * n, counts))
+        return labels[: levels * n].reshape(levels, n), [int(c) for c in counts]
+
+    def self_component_levels_launch(self, max_divergence: int, d_labels: int, d_n_components: int) -> None:
+        """device-resident form (smafa_db_self_levels_launch): (max_divergence + 1) x n_subjects uint32 labels in d_labels,
+        max_divergence + 1 component counts in d_n_components (device uint64 each)"""
+        check(lib().smafa_db_self_levels_launch(self._h, _opt(max_divergence), C.c_void_p(d_labels) if d_labels else None,
+                                                C.c_void_p(d_n_components) if d_n_components else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -504,3 +522,9 @@ def components(db_path: str, max_divergence: int, out_fd: int = 1, device: int =
     """`smafa components`: "i\\tlabel" per subject of the DB file, label = the smallest subject number of i's single-linkage
     component at max_divergence, to out_fd."""
     check(lib().smafa_components(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def component_levels(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa components --levels`: "i\\tlabel_0\\t...\\tlabel_N" per subject of the DB file, label_t = its label at bound t, to
+    out_fd."""
+    check(lib().smafa_component_levels(os.fsencode(db_path), _opt(max_divergence), out_fd, device))

@@ -20,6 +20,7 @@
 #include "index.hip.h"
 #include "join.hip.h"
 #include "components.hip.h"
+#include "levels.hip.h"
 
 namespace smafa {
 
@@ -195,7 +196,8 @@ struct smafa_db {
         uint64_t generation = 0, n = 0;
         uint32_t resorts = 0;
         DevBuf out, cnt;  // rows of the host form (smafa_db_self_hits) on their way to the caller, and their counter
-        DevBuf parent;    // components (components.hip.h): the union-find's parent[], 4 B per subject, live for one call
+        DevBuf parent;    // components (components.hip.h): the union-find's parent[], 4 B per subject, live for one call;
+                          // levels (levels.hip.h): one per scanned level, level-major
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin, records done, scan done, filter / link done
         double rec_ms = 0, scan_ms = 0, filter_ms = 0;            // per stage, over the blocks of the last join
         double link_ms = 0, flatten_ms = 0;                       // components: init + link passes, the flatten launch
@@ -1411,15 +1413,22 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 // smallest subject number of i's component and counts the representatives into *d_count.  Spans, records, scans, the
 // wait for each count, the re-scan of an overflowing piece (a truncated list is never linked), the halving and the
 // SMAFA_ERR_NOMEM case are the same code for both.
+// A third consumer, n_levels != 0 (smafa_db_self_levels_launch; levels.hip.h): d_labels is n_levels x n, d_count n_levels
+// counters, J.parent one union-find per SCANNED level (E = min(max_div, L - 1) + 1 of them; the levels above are all zeros
+// and need no scan), the join runs once at bound E - 1 and hook_levels_kernel unites the subjects of a row at every level
+// from its distance upwards; flatten_levels_kernel writes every level in one launch.  Everything between is the shared path.
 static bool join_inverse_current(const smafa_db *db) {
     const auto &j = db->join;
     return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
 }
 
 static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count,
-                     uint32_t *d_labels = nullptr) {
+                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0) {
     auto &J = db->join;
-    const bool linking = d_labels != nullptr;
+    const bool linking = d_labels != nullptr, levelled = n_levels != 0;
+    // levels: the union-finds that are scanned for, and the one bound the join runs at
+    const uint32_t E = levelled ? (uint32_t)std::min<uint64_t>(n_levels, std::max<uint32_t>(db->L, 1u)) : 0u;
+    const uint32_t scan_div = levelled ? E - 1u : max_div;
     db->call_kernels.clear();
     db->call_ms = 0.f;
     db->call_launches = db->call_scans = 0;
@@ -1429,12 +1438,12 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     J.blocks = J.rescans = 0;
     int rc = use_device(db);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
+    HIP_TRY(hipMemsetAsync(d_count, 0, (levelled ? (size_t)n_levels : 1u) * sizeof(unsigned long long), db->stream));
     db->call_timed = true;
     if (db->n < (linking ? 1u : 2u)) return SMAFA_OK;
     // components of one row, or at a bound no two rows can exceed: nothing to scan (the second would list all n^2 pairs to
     // learn "one component")
-    const bool no_scans = linking && (db->n < 2 || max_div >= db->L);
+    const bool no_scans = linking && (db->n < 2 || (!levelled && max_div >= db->L));
     if (!no_scans) {
         rc = maybe_resort(db);  // once, in front: positions are final for the whole join
         if (rc) return rc;
@@ -1447,10 +1456,14 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     const uint32_t n = (uint32_t)db->n;
     bool inverted = false;
     if (linking) {  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
-        rc = J.parent.ensure((size_t)n * sizeof(uint32_t));
+        rc = J.parent.ensure((size_t)n * (levelled ? E : 1u) * sizeof(uint32_t));
         if (rc) return rc;
         HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (max_div >= db->L) {
+        if (levelled) {
+            hipLaunchKernelGGL(smafa_lv::init_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, E);
+            HIP_TRY(hipGetLastError());
+            db->call_launches++;
+        } else if (max_div >= db->L) {
             HIP_TRY(hipMemsetAsync(J.parent.p, 0, (size_t)n * sizeof(uint32_t), db->stream));
         } else {
             hipLaunchKernelGGL(smafa_cc::init_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n);
@@ -1479,7 +1492,8 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         float ms = 0.f;
         if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) {
             (linking ? J.link_ms : J.filter_ms) += ms;
-            if (linking) log_line(3, "components: parent[] %s, %.3f ms", linked ? "linked with a piece's rows" : "initialised", ms);
+            if (linking)
+                log_line(3, "%s: parent[] %s, %.3f ms", levelled ? "levels" : "components", linked ? "linked with a piece's rows" : "initialised", ms);
         }
         filter_pending = false;
     };
@@ -1510,7 +1524,7 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
             const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
             for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
                 const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
-                rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, max_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
+                rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
                                 db->count.as<unsigned long long>(), t0);
                 if (rc) return rc;
                 unsigned long long count = 0;
@@ -1540,9 +1554,18 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
                     // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
                     return set_error(SMAFA_ERR_NOMEM,
                                      "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
-                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, max_div, (unsigned long long)db->join_scratch_max);
+                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
                 }
-                if (count && linking) {  // (count <= capacity here: a truncated list was scanned again above)
+                if (count && levelled) {  // (count <= capacity here: a truncated list was scanned again above)
+                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                    hipLaunchKernelGGL(smafa_lv::hook_levels_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
+                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
+                                       J.parent.as<uint32_t>(), n, E);
+                    HIP_TRY(hipGetLastError());
+                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                    filter_pending = linked = true;
+                    db->call_launches++;
+                } else if (count && linking) {
                     HIP_TRY(hipEventRecord(J.ev[2], db->stream));
                     hipLaunchKernelGGL(smafa_cc::link_rows_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
                                        dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
@@ -1573,8 +1596,12 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         HIP_TRY(hipStreamSynchronize(db->stream));
         take_filter_time();
         HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
-                           J.parent.as<uint32_t>(), n, d_labels, d_count);
+        if (levelled)
+            hipLaunchKernelGGL(smafa_lv::flatten_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
+                               J.parent.as<uint32_t>(), n, E, n_levels, d_labels, d_count);
+        else
+            hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
+                               J.parent.as<uint32_t>(), n, d_labels, d_count);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(J.ev[3], db->stream));
         db->call_launches++;
@@ -1584,6 +1611,15 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         db->call_ms += (float)(J.rec_ms + J.link_ms + J.flatten_ms);
         db->call_timed = true;  // (scan_range cleared it)
         if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+        if (levelled) {
+            note_call_kernel(db, "smafa_lv::init_levels_kernel");
+            if (linked) note_call_kernel(db, "smafa_lv::hook_levels_kernel");
+            note_call_kernel(db, "smafa_lv::flatten_levels_kernel");
+            log_line(2, "levels 0..%u of %u rows, joined at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, "
+                     "link %.3f ms, flatten %.3f ms", n_levels - 1u, n, scan_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms,
+                     J.link_ms, J.flatten_ms);
+            return SMAFA_OK;
+        }
         if (max_div < db->L) note_call_kernel(db, "smafa_cc::init_labels_kernel");
         if (linked) note_call_kernel(db, "smafa_cc::link_rows_kernel");
         note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
@@ -2692,6 +2728,47 @@ int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, u
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_components");
+}
+
+int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL handle");
+    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL labels");
+    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL count");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: levels need a bound (max_div)");
+    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_components, (uint32_t *)d_labels, max_div + 1u);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_levels_launch");
+}
+
+int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL handle");
+    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL labels");
+    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL count");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: levels need a bound (max_div)");
+    const uint64_t T = (uint64_t)max_div + 1u;
+    // (n_subjects < 2^32 and T <= 2^32 - 1: the product cannot wrap)
+    if (cap < T * db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: labels holds %llu entries, %llu levels of %llu subjects need %llu",
+                         (unsigned long long)cap, (unsigned long long)T, (unsigned long long)db->n, (unsigned long long)(T * db->n));
+    std::fill(n_components, n_components + T, (uint64_t)0);
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    rc = J.out.ensure(std::max<uint64_t>(T * db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller
+    if (!rc) rc = J.cnt.ensure(T * sizeof(unsigned long long));
+    if (rc) return rc;
+    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), (uint32_t)T);
+    if (rc) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
+    HIP_TRY(hipMemcpyAsync(n_components, J.cnt.p, T * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
+    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, T * db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    if (J.out.cap > (512ull << 20)) J.out.release();
+    if (J.parent.cap > (512ull << 20)) J.parent.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_levels");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -695,6 +695,46 @@ int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, i
     return smafa::exception_code("smafa_components");
 }
 
+// The labels of every subject of a DB file at every bound 0 .. max_divergence (smafa_db_self_levels), printed
+// "{i}\t{label_0}\t...\t{label_N}\n" in subject order.
+int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_component_levels: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_component_levels: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    const size_t n = (size_t)info.n_subjects, T = (size_t)max_divergence + 1;
+    std::vector<uint32_t> labels(n * T);
+    std::vector<uint64_t> counts(T);
+    rc = smafa_db_self_levels(store.db, max_divergence, labels.data(), labels.size(), counts.data());
+    if (rc) return rc;
+    std::string text;
+    const size_t block = std::max<size_t>(1, ((size_t)1 << 18) / T);  // rows per write
+    for (size_t b0 = 0; b0 < n; b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(n, b0 + block); i < e; i++) {
+            append_u32(text, (uint32_t)i);
+            for (size_t t = 0; t < T; t++) {
+                text.push_back('\t');
+                append_u32(text, labels[t * n + i]);
+            }
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu components of %llu sequences within 0, %llu within %u, took %llu seconds", (unsigned long long)counts[0],
+             (unsigned long long)n, (unsigned long long)counts[T - 1], max_divergence, (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_component_levels");
+}
+
 // ------------------------------------------------------------------------------------ cluster
 //
 // The reference handles one record at a time: skip exact duplicates, scan the record against the

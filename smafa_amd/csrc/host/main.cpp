@@ -6,7 +6,8 @@
 //   cluster -i/--input FILE  -d/--max-divergence INT
 //   count   -i/--input FILE...
 //   pairs   -d/--database FILE  --max-divergence INT   (this build only: every pair of the DB's own subjects within the bound)
-//   components -d/--database FILE  --max-divergence INT   (this build only: the single-linkage component of every subject)
+//   components -d/--database FILE  --max-divergence INT  [--levels]   (this build only: the single-linkage component of
+//           every subject; --levels: at every bound 0 .. INT)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -43,9 +44,10 @@ static int usage(const char *msg, FILE *to = stderr) {
             "count   -i, --input <FILE>...\n"
             "pairs   -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: every pair i < j of the\n"
             "        database's own sequences within the bound, one \"i<TAB>j<TAB>divergence\" line each)\n"
-            "components -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: single-linkage\n"
+            "components -d, --database <FILE>  --max-divergence <INT>  [--levels] [--device <N>]  (not in the reference: single-linkage\n"
             "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
-            "        smallest sequence number of its component)\n");
+            "        smallest sequence number of its component; --levels: one label column per bound 0 .. <INT>,\n"
+            "        \"i<TAB>label_0<TAB>...<TAB>label_INT\", from one join)\n");
     return 2;
 }
 
@@ -86,7 +88,7 @@ int main(int argc, char **argv) {
     const char *input = nullptr, *database = nullptr, *query = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0;
-    bool have_max_div = false, packed = false, no_gpu = false;
+    bool have_max_div = false, packed = false, no_gpu = false, levels = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
     int verbosity = 1;  // the reference logs at info level unless told otherwise (bird_tool_utils set_log_level)
@@ -119,6 +121,8 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &device)) return usage("--device needs an unsigned integer");
         } else if (a == "--packed") {
             packed = true;
+        } else if (a == "--levels" && cmd == "components") {
+            levels = true;
         } else if (a == "--no-gpu") {
             no_gpu = true;
         } else if (a == "--gpus") {
@@ -182,7 +186,7 @@ int main(int argc, char **argv) {
     } else if (cmd == "components") {
         if (!database) return usage("components needs --database");
         if (!have_max_div) return usage("components needs --max-divergence");
-        rc = smafa_components(database, max_div, 1, (int)device);
+        rc = levels ? smafa_component_levels(database, max_div, 1, (int)device) : smafa_components(database, max_div, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);
