@@ -952,8 +952,11 @@ constexpr int kZoneTiles = SMAFA_ZONE_TILES;
 // 50M x 125k (profiles/r04_zone_variants.txt): 5 waves x 4 tiles 1.795 / 53.5, 5 x 6 1.77 / 52.0, 6 x 3 1.71 / 50.6, 6 x 2 1.72 /
 // 51.5, **7 x 2 1.68 / 49.3**, 7 x 3 1.76 / 64.6 (spills), 8 x 2 1.78 / 78.4 (spills), 4 x 6 1.95, 6 x 4 2.01.  Nucleotides keep 4
 // tiles (3: 2.80, 6: 3.12 vs 2.70 ms).  SMAFA_ZONE_TILES != 4 overrides for every shape.
+#ifndef SMAFA_ZONE_TILES_DIRECT_AA
+#define SMAFA_ZONE_TILES_DIRECT_AA 2  // tiles per wave of the unstaged five-plane two-word kernel alone (nucleotide shapes keep theirs)
+#endif
 __host__ __device__ constexpr int zone_tiles(int ps, int w, bool direct) {
-    return SMAFA_ZONE_TILES != 4 ? SMAFA_ZONE_TILES : (direct && ps == 5 && w == 2 ? 2 : 4);
+    return SMAFA_ZONE_TILES != 4 ? SMAFA_ZONE_TILES : (direct && ps == 5 && w == 2 ? SMAFA_ZONE_TILES_DIRECT_AA : 4);
 }
 #ifndef SMAFA_ZONE_WG_WAVES
 #define SMAFA_ZONE_WG_WAVES 2
@@ -1033,6 +1036,34 @@ constexpr int kFewTiles = SMAFA_FEW_TILES;  // wave tiles per wave in scan_zone_
 #ifndef SMAFA_ZONE_KEY_HOIST
 #define SMAFA_ZONE_KEY_HOIST 1
 #endif
+// 1: level 2 of the key-test kernels (two filter words) touches neither global nor scalar memory.  The query's filter word 1 is the
+// head word lane i already holds (v_readlane, like word 0), the tile's filter word 1 — loaded once in the prologue for the bitmaps —
+// stays with the wave (zone_f1_home), and the query record is read behind level 2's rejections, for level 3 alone.
+// 0: the record through scalar loads and the tile's word 1 from L2 in front of level 2, one serial round trip per level-2 entry.
+#ifndef SMAFA_ZONE_L2_LANES
+#define SMAFA_ZONE_L2_LANES 1
+#endif
+// Where the tile's filter word 1 lives between the prologue and level 2 — 0: nowhere (read from L2 per entry), 1: LDS, one uint4
+// per lane and tile slot, lane-linear (conflict-free ds_read_b128; 1 KB per slot and wave), 2: registers (4 VGPRs per slot, fetched
+// again behind the dense walk like word 0).  Amino acids, 2 tiles at 7 waves per SIMD: 6144 B of bitmaps + 4096 B per two-wave
+// workgroup, 14 workgroups = 140 KB of the CU's 160 KB.  The nucleotide shapes' 4 tiles x 3 bitmaps already take 12288 B per
+// workgroup, 12 workgroups at 6 waves per SIMD = 144 KB: another 8 KB each does not fit, and their register budget is spent — L2.
+#ifndef SMAFA_ZONE_F1_HOME_AA
+#define SMAFA_ZONE_F1_HOME_AA 1
+#endif
+#ifndef SMAFA_ZONE_F1_HOME_NT
+#define SMAFA_ZONE_F1_HOME_NT 0
+#endif
+__host__ __device__ constexpr int zone_f1_home(int ps, int w, bool direct) {
+    return !(SMAFA_ZONE_L2_LANES && direct && w == 2 && SMAFA_ZONE_KEYS > 0) ? 0 : ps == 5 ? SMAFA_ZONE_F1_HOME_AA : SMAFA_ZONE_F1_HOME_NT;
+}
+// 1: the hoisted form runs the zone level of ALL tile slots first, then the 3 x T bitmap gathers back to back under their slots'
+// survivor masks, ONE wait, then the T key tails: one LDS latency per chunk instead of one per tile slot.  The gate is one decision
+// per chunk — every slot is tested if any slot has key_gate survivors (0: always, 65: never, as before).
+// 0: slot by slot behind a gate branch each, which keeps the slots' gathers apart.
+#ifndef SMAFA_ZONE_KEY_BATCH
+#define SMAFA_ZONE_KEY_BATCH 1
+#endif
 __host__ __device__ constexpr int zone_key_sets(int w, bool direct) { return direct && w == 2 ? SMAFA_ZONE_KEYS : 0; }
 static_assert(SMAFA_ZONE_KEYS == 0 || SMAFA_ZONE_KEYS == 2 || SMAFA_ZONE_KEYS == 3, "SMAFA_ZONE_KEYS: 0, 2 or 3");
 static_assert(SMAFA_ZONE_KEY_BITS >= 8 && SMAFA_ZONE_KEY_BITS <= 16, "SMAFA_ZONE_KEY_BITS: 8..16");
@@ -1072,6 +1103,10 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     constexpr int KB = SMAFA_ZONE_KEY_BITS;
     constexpr int KW = (1 << KB) / 32;  // u32 words per bitmap
     __shared__ uint4 keymap[NS ? WGW * T * NS * KW / 4 : 1];
+    // ... and where level 2 finds the tile's filter word 1 (see zone_f1_home)
+    constexpr int kF1Home = NS > 0 ? zone_f1_home(PS, W, DIRECT) : 0;
+    constexpr bool kL2Lanes = NS > 0 && W == 2 && SMAFA_ZONE_L2_LANES;
+    __shared__ uint4 f1_lds[kF1Home == 1 ? WGW * T * 64 : 1];
     int buf = 0;  // LDS buffer of the chunk being computed = parity of the row stage it appends to
 
     const uint32_t tid = threadIdx.x;
@@ -1091,11 +1126,13 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
 
     // word 0 of the filter plane of this lane's 16 subjects; tile slots past the range copy tile_begin (valid memory)
     uint4 f0[T];
+    uint4 f1_reg[kF1Home == 2 ? T : 1];  // word 1 likewise, where its home is registers
     auto load_filter = [&]() {
 #pragma unroll
         for (int t = 0; t < T; t++) {
             const bool live = SMAFA_ZONE_NLIVE ? (uint32_t)t < n_live : tile0 + t < a.tile_end;
             f0[t] = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W) * 64 + lane];
+            if constexpr (kF1Home == 2) f1_reg[t] = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
         }
     };
     load_filter();
@@ -1145,6 +1182,8 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     }
     // this wave's bitmaps: u32 word j of (tile slot t, set s) at km[(t * NS + s) * KW + j]
     uint32_t *const km = reinterpret_cast<uint32_t *>(keymap) + (size_t)__builtin_amdgcn_readfirstlane((int)wave) * (T * NS * KW);
+    // this wave's share of f1_lds: tile slot t's word 1 of lane l at f1_home[t * 64 + l] (written once, below, and only read after)
+    uint4 *const f1_home = f1_lds + (kF1Home == 1 ? (size_t)__builtin_amdgcn_readfirstlane((int)wave) * (T * 64) : 0);
     if constexpr (NS > 0) {
         // Wave-private: no barrier, only this wave's own LDS operations in order (the compiler must not move them across).
         uint4 *const km4 = reinterpret_cast<uint4 *>(km);
@@ -1156,7 +1195,10 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
 #pragma unroll
         for (int t = 0; t < T; t++) {
             const bool live = (uint32_t)t < n_live;
-            const uint4 f1 = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
+            uint4 f1;
+            if constexpr (kF1Home == 2) f1 = f1_reg[t];
+            else f1 = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
+            if constexpr (kF1Home == 1) f1_home[t * 64 + lane] = f1;
             const uint32_t w0[4] = {f0[t].x, f0[t].y, f0[t].z, f0[t].w};
             const uint32_t w1[4] = {f1.x, f1.y, f1.z, f1.w};
 #pragma unroll
@@ -1363,8 +1405,32 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
 #else
 #define SMAFA_ZONE_BUF buf
 #endif
-                        // ---- level 2 (rare): the filter plane folded over all its words, words 1.. from L2/HBM
                         uint32_t qw[RS];
+                        if constexpr (kL2Lanes) {
+                            // ---- level 2, two filter words, no memory but the wave's own: the query's word 1 out of lane i like
+                            // word 0, the tile's word 1 from its home; the record is read behind it, for level 3
+                            const uint32_t q1w = (uint32_t)__builtin_amdgcn_readlane((int)hq1, i);
+                            uint4 v;
+                            if constexpr (kF1Home == 1) v = f1_home[t * 64 + lane];
+                            else if constexpr (kF1Home == 2) v = f1_reg[t];
+                            else v = planes[(size_t)tile_r * (PS * W * 64) + (FP * W + 1) * 64 + lane];
+                            const uint32_t m0 = or_xor(ft.x ^ q0w, v.x, q1w), m1 = or_xor(ft.y ^ q0w, v.y, q1w);
+                            const uint32_t m2 = or_xor(ft.z ^ q0w, v.z, q1w), m3 = or_xor(ft.w ^ q0w, v.w, q1w);
+                            if (kPair) {  // two subjects per popcount first (see scan_kernel)
+                                const uint32_t sign = (__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu);
+                                if (__ballot((int32_t)sign < 0) == 0ull) continue;
+                            }
+                            const uint32_t each = or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
+                                                      __builtin_popcount(m2) + nu) |
+                                                  (__builtin_popcount(m3) + nu);
+                            if (__ballot((int32_t)each < 0) == 0ull) continue;
+                            read_record(reinterpret_cast<const uint4 *>(qrec + (size_t)(qc + (uint32_t)i) * RS), qw);
+                            qw[BS] = nu;
+                            passes++;
+                            stream_compare(tile_r, qw, qc + (uint32_t)i, SMAFA_ZONE_BUF);
+                            continue;
+                        }
+                        // ---- level 2 (rare): the filter plane folded over all its words, words 1.. from L2/HBM
                         if (DIRECT) read_record(reinterpret_cast<const uint4 *>(qrec + (size_t)(qc + (uint32_t)i) * RS), qw);
                         else read_record(&stage[SMAFA_ZONE_BUF][(uint32_t)i * RV], qw);
                         qw[BS] = nu;  // the staged record carries no bound
@@ -1429,6 +1495,41 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                         // lanes past the block are masked out of the ballot (scalar) instead of out of ~bound (per lane)
                         const unsigned long long in_block = ~0ull >> (64u - nqc);
                         auto hoisted = [&](auto with_w1) {
+                            if constexpr (SMAFA_ZONE_KEY_BATCH) {
+                                // zone level of every slot; slots past the range keep an empty mask (an active wave's slot 0 is
+                                // inside it) and, in the last wave alone, gather from their own bitmaps for nothing
+                                uint32_t u[T];
+                                bool test = false;
+                                each_slot([&](auto slot) {
+                                    constexpr uint32_t t = decltype(slot)::value;
+                                    u[t] = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
+                                    if (decltype(with_w1)::value) u[t] += __builtin_popcount((hq1 ^ zc1s[t]) & zm1s[t]);
+                                    const unsigned long long m = __builtin_amdgcn_ballot_w64((int32_t)u[t] < 0) & in_block;
+                                    ms[t] = t == 0u || nl > t ? m : 0ull;
+                                    test = test || (uint32_t)__builtin_popcountll(ms[t]) >= a.key_gate;
+                                });
+                                if (test) {
+                                    // all gathers under their slots' survivors, nothing between them that waits; lanes that did not
+                                    // survive keep 0 = nothing found, so their u stays >= 0 below
+                                    uint32_t g[T][3];
+                                    each_slot([&](auto slot) {
+                                        constexpr uint32_t t = decltype(slot)::value;
+                                        g[t][0] = g[t][1] = g[t][2] = 0u;
+                                        if ((int32_t)u[t] < 0) {
+                                            g[t][0] = *(lds_u32)(uintptr_t)(ay + ((t * NS + 0) * KW) * 4u);
+                                            g[t][1] = *(lds_u32)(uintptr_t)(ax + ((t * NS + 1) * KW) * 4u);
+                                            if (NS > 2) g[t][2] = *(lds_u32)(uintptr_t)(az + ((t * NS + (NS > 2 ? 2 : 0)) * KW) * 4u);
+                                        }
+                                    });
+                                    // found sets + budget ~u >= NS  <=>  u - found < -NS
+                                    each_slot([&](auto slot) {
+                                        constexpr uint32_t t = decltype(slot)::value;
+                                        uint32_t found = __builtin_amdgcn_ubfe(g[t][0], ky, 1) + __builtin_amdgcn_ubfe(g[t][1], kx, 1);
+                                        if (NS > 2) found += __builtin_amdgcn_ubfe(g[t][2], kz, 1);
+                                        ms[t] &= __builtin_amdgcn_ballot_w64((int32_t)(u[t] - found) < -(int32_t)NS);
+                                    });
+                                }
+                            } else {
                             auto one = [&](auto slot) -> unsigned long long {
                                 constexpr uint32_t t = decltype(slot)::value;
                                 uint32_t u = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
@@ -1453,6 +1554,7 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
                                 constexpr uint32_t t = decltype(slot)::value;
                                 ms[t] = t == 0u || nl > t ? one(slot) : 0ull;
                             });
+                            }
                         };
                         // word 1's share of the zone level under a scalar branch: it is rare (zone_w1)
                         if (zone_w1) hoisted(std::true_type{});
