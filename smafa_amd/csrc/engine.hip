@@ -188,6 +188,7 @@ struct smafa_db {
     double index_cand_per_subject = -1.0;  // candidates per query the probes may expect, per stored subject (SMAFA_INDEX_CAND;
                                            // < 0: by the bound's class — index_cand_limit)
     uint64_t index_min_rows = 65536;  // mode 2 builds an index for stores of at least this many subjects (SMAFA_INDEX_MIN_ROWS)
+    uint32_t index_fail_builds = 0;   // tests: the next builds of this handle fail at their sort scratch (SMAFA_INDEX_FAIL_BUILDS)
     uint32_t index_probes = 0;      // launches answered by the index over the handle's life (smafa_index_info)
     // ---- self-join (smafa_db_self_launch, join.hip.h)
     struct JoinState {
@@ -779,8 +780,7 @@ static void index_drop(smafa_db *db) {
     for (DevBuf *b : {&db->index.kp, &db->index.dir, &db->index.stats, &db->index.rows}) b->release();
 }
 
-// Build (or rebuild) the index with `blocks` blocks: serves every fixed bound up to blocks - 1.
-static int index_build(smafa_db *db, uint32_t blocks) {
+static int index_build_steps(smafa_db *db, uint32_t blocks) {
     auto &ix = db->index;
     ix.valid = false;
     if (db->W > (uint32_t)kIndexMaxWords)
@@ -803,7 +803,10 @@ static int index_build(smafa_db *db, uint32_t blocks) {
     if (!rc) rc = ix.rows.ensure((size_t)n * row_bytes);
     if (!rc) rc = ix.dir.ensure((size_t)blocks * dir_entries * sizeof(uint32_t));
     if (!rc) rc = ix.stats.ensure((size_t)kIndexMaxBlocks * 2 * sizeof(unsigned long long));
-    if (!rc) rc = db->keys_a.ensure((size_t)n * sizeof(uint32_t));
+    // (SMAFA_INDEX_FAIL_BUILDS, tests: a size no device has — hipMalloc says out of memory at once, as where HBM has run out)
+    const bool fail = db->index_fail_builds > 0;
+    if (fail) db->index_fail_builds--;
+    if (!rc) rc = db->keys_a.ensure(fail ? (size_t)1 << 60 : (size_t)n * sizeof(uint32_t));
     if (!rc) rc = db->keys_b.ensure((size_t)n * sizeof(uint32_t));
     if (!rc) rc = db->idx_a.ensure((size_t)n * sizeof(uint32_t));
     if (!rc) rc = db->idx_b.ensure((size_t)n * sizeof(uint32_t));
@@ -851,6 +854,19 @@ static int index_build(smafa_db *db, uint32_t blocks) {
     log_line(2, "block index of %u rows: %u blocks, %.1f MB, built on the device in %.2f ms", n, blocks,
              (double)(ix.kp.cap + ix.dir.cap + ix.rows.cap) / 1e6, ix.build_ms);
     return SMAFA_OK;
+}
+
+// Build (or rebuild) the index with `blocks` blocks: serves every fixed bound up to blocks - 1.
+// A build that fails leaves nothing behind: the runtime keeps a failed hipMalloc as the thread's last error until somebody
+// reads it — the next launch's HIP_TRY(hipGetLastError()) would take it for its own, and the scan that was to fall back to the
+// scan kernels would fail with the build's error — and the sort scratch, 16 bytes per subject and more, is given back.
+static int index_build(smafa_db *db, uint32_t blocks) {
+    const int rc = index_build_steps(db, blocks);
+    if (rc) {
+        (void)hipGetLastError();
+        for (DevBuf *b : {&db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b, &db->sort_tmp}) b->release();
+    }
+    return rc;
 }
 
 // Candidates per query the probes of a scan with this bound may expect before the scan kernels are the better choice.
@@ -2093,6 +2109,7 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *iv = getenv("SMAFA_INDEX_MAX_RUN")) db->index_max_run = std::max<uint64_t>(1, strtoull(iv, nullptr, 10));
     if (const char *iv = getenv("SMAFA_INDEX_CAND")) db->index_cand_per_subject = atof(iv);
     if (const char *iv = getenv("SMAFA_INDEX_MIN_ROWS")) db->index_min_rows = std::max<uint64_t>(1, strtoull(iv, nullptr, 10));
+    if (const char *iv = getenv("SMAFA_INDEX_FAIL_BUILDS")) db->index_fail_builds = (uint32_t)std::max(0, atoi(iv));
     if (const char *jv = getenv("SMAFA_JOIN_BLOCK")) db->join_block = std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64);
     if (const char *jv = getenv("SMAFA_JOIN_STRIDE")) db->join_stride = std::min<uint64_t>(4096, std::max<uint64_t>(1, strtoull(jv, nullptr, 10)));
     if (const char *jv = getenv("SMAFA_JOIN_SCRATCH_MAX")) db->join_scratch_max = std::max<uint64_t>(4096, strtoull(jv, nullptr, 10));
