@@ -196,7 +196,9 @@ int smafa_last_scan_kernel(smafa_db *db, char *name, uint64_t cap);
  * call on this handle launched from the scan family (seed passes, near-hit ladder steps, k-th counting and append passes,
  * index probes), spelled as the demangled template-id ("smafa::scan_kernel<5, 5, 2, 1, false, 1>"), newline-separated
  * in first-launch order and NUL-terminated.  A scan_wide_kernel launch with its zone level on adds the marker line
- * "<template-id> (zone level on)" after the template-id.  SMAFA_ERR_CAPACITY if the list needs more than cap bytes. */
+ * "<template-id> (zone level on)" after the template-id; a kth_seed_kernel launch that counts a whole sample of the store
+ * into the per-query counts (not only the seed bound of the first tiles) adds "<template-id> (sample counts)" in the same
+ * way.  SMAFA_ERR_CAPACITY if the list needs more than cap bytes. */
 int smafa_last_call_kernels(smafa_db *db, char *names, uint64_t cap);
 /* Tuning knob: queries per workgroup pass (0 = automatic). */
 int smafa_set_query_block(smafa_db *db, uint32_t queries_per_block);

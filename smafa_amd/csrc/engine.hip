@@ -159,6 +159,7 @@ struct smafa_db {
     bool kth_hist_seed = true;   // k >= 2: the seed bound from an LDS histogram over the first tiles (SMAFA_KTH_HIST_SEED=0: a counting launch)
     uint32_t kth_sample_min_tiles = 4096;  // stores below this many wave tiles (1M subjects) count everything first (SMAFA_KTH_SAMPLE_MIN_TILES)
     uint32_t kth_sample_div = 32;  // ... counting only the first 1/32 of the tiles, the rest counted and appended in one pass (SMAFA_KTH_SAMPLE=0: count everything first)
+    uint32_t kth_groups = 0;  // test switch: at most this many tile groups per query chunk when kth_seed_kernel counts a sample (SMAFA_KTH_GROUPS; 0: automatic)
     // rows of a smafa_scan_hits call that ended in SMAFA_ERR_CAPACITY, kept for the caller's "grow and retry":
     // the retry with the same arguments against the same store is answered without scanning again
     std::vector<smafa_hit> retry_rows;
@@ -1183,7 +1184,14 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         const uint32_t n_chunks = (nq + kSeedQueries - 1) / kSeedQueries;
         const uint32_t steps = (tiles + kWgWaves - 1) / kWgWaves;
         // enough workgroups to fill the chip (8 per CU), never more tile groups than 4-tile steps
-        const uint32_t n_groups = d_cnt ? std::max(1u, std::min(steps, ((uint32_t)db->n_cu * 8u + n_chunks - 1) / n_chunks)) : 1u;
+        uint32_t n_groups = d_cnt ? std::max(1u, std::min(steps, ((uint32_t)db->n_cu * 8u + n_chunks - 1) / n_chunks)) : 1u;
+        if (d_cnt && db->kth_groups) n_groups = std::min(n_groups, db->kth_groups);  // (1: one workgroup per chunk walks every step)
+        // (the call's list names the counting form as a marker of its own, after the template-id — as scan_wide_kernel's zone level)
+        auto note_counts = [&]() {
+            if (!d_cnt) return;
+            const std::string id = db->plan_kernel;
+            note_kernel(db, "%s (sample counts)", id.c_str());
+        };
         const dim3 grid(n_chunks * n_groups), block(256);
         const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
         const uint32_t *qrec = qs->qrec.as<uint32_t>();
@@ -1191,6 +1199,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
 #define SMAFA_SEED(PS_, PQ_, W_)                                                                                              \
     if (db->P == PS_ && db->PQ == PQ_ && db->W == W_) {                                                                       \
         note_kernel(db, "smafa::kth_seed_kernel<%d, %d, %d>", PS_, PQ_, W_);                                                  \
+        note_counts();                                                                                                        \
         hipLaunchKernelGGL((kth_seed_kernel<PS_, PQ_, W_>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ,    \
                            db->W, tiles, (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt,      \
                            (uint32_t)cnt_stride);                                                                             \
@@ -1200,6 +1209,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         SMAFA_SEED(2, 3, 3) SMAFA_SEED(3, 3, 3) SMAFA_SEED(5, 5, 3) SMAFA_SEED(2, 3, 4) SMAFA_SEED(3, 3, 4) SMAFA_SEED(5, 5, 4)
 #undef SMAFA_SEED
         note_kernel(db, "smafa::kth_seed_kernel<0, 0, 0>");
+        note_counts();
         hipLaunchKernelGGL((kth_seed_kernel<0, 0, 0>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ, db->W, tiles,
                            (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt, (uint32_t)cnt_stride);
     };
@@ -2097,6 +2107,7 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *ks = getenv("SMAFA_KTH_HIST_SEED")) db->kth_hist_seed = atoi(ks) != 0;
     if (const char *ks = getenv("SMAFA_KTH_SAMPLE")) db->kth_sample_div = (uint32_t)std::max(0, atoi(ks));
     if (const char *ks = getenv("SMAFA_KTH_SAMPLE_MIN_TILES")) db->kth_sample_min_tiles = (uint32_t)std::max(1, atoi(ks));
+    if (const char *ks = getenv("SMAFA_KTH_GROUPS")) db->kth_groups = (uint32_t)std::max(0, atoi(ks));
     if (const char *ov = getenv("SMAFA_WIDE_ONE")) db->wide_one = atoi(ov) != 0;
     if (const char *wv = getenv("SMAFA_WIDE_FROM")) db->wide_from = (uint32_t)std::max(3, atoi(wv));
     if (const char *zv = getenv("SMAFA_ZONE")) db->zone = std::min(2, std::max(0, atoi(zv)));

@@ -6,7 +6,8 @@ existing test that runs it.  tests/test_kernel_census.py checks that the two tog
 
 A case: the switches read when the handle is created, the store kind (nt2: nucleotides on two planes, nt3: on three, aa:
 amino acids on five), the row length L, the bound D (None: none) and k (0: every row within D), the number of queries, the
-prefilter, the zone level (0 off, 2 forced), whether a block index is built, E — the bound its edge pairs are planted at
+prefilter, the zone level (0 off, 2 forced), whether a block index is built, `marker` (the note the call's kernel list adds after
+the template-id for one form of the kernel: "zone level on", "sample counts"), E — the bound its edge pairs are planted at
 (tests/kernel_edges.py) — and `spread` (fillers at distances 0..spread, so every step of the near-hit ladder finishes some).
 """
 from __future__ import annotations
@@ -19,6 +20,8 @@ SWITCHES = {
     "wide_from3": (("SMAFA_WIDE_FROM", "3"),),
     "zone_staged": (("SMAFA_ZONE_DIRECT", "0"),),
     "index": (("SMAFA_INDEX_MAX_RUN", "100000000"), ("SMAFA_INDEX_CAND", "100")),
+    # the k-th modes count a sample (half of the census stores' 6 and 8 tiles) first, no near-hit ladder in front
+    "kth_sample": (("SMAFA_KTH_SAMPLE", "2"), ("SMAFA_KTH_SAMPLE_MIN_TILES", "4"), ("SMAFA_TWO_PHASE", "0")),
 }
 KINDS = ("nt2", "nt3", "aa")
 PSPQ = {"nt2": (2, 3), "nt3": (3, 3), "aa": (5, 5)}
@@ -87,7 +90,9 @@ def _census():
             add(zk % ("true", "false"), case("zone_staged", kind, L2, 5, nq=129, zone=2))
             add(zk % ("false", "false"), best_hit("default", kind, L2, zone=2))
             add("smafa::scan_zone_few_kernel<%d, %d, %d>" % (ps, pq, W), case("default", kind, L2, 5, nq=64, zone=2))
-            add("smafa::kth_seed_kernel<%d, %d, %d>" % (ps, pq, W), case("default", kind, L2, None, 3, 65, E=5))
+            # the seed bound of the first tiles, and the counting form over a whole sample (marker "sample counts")
+            add("smafa::kth_seed_kernel<%d, %d, %d>" % (ps, pq, W), case("default", kind, L2, None, 3, 65, E=5),
+                case("kth_sample", kind, L2, None, 3, 65, E=5, marker="sample counts"))
             add("smafa::index_probe_kernel<%d, %d, %d>" % (ps, pq, W), case("index", kind, L2, 5, index=True))
         # scan_wide_kernel: one-word stores, stores of more than four words, and three / four words under SMAFA_WIDE_FROM=3
         wk = "smafa::scan_wide_kernel<%d, %d, %%s, %%d, %%d>" % (ps, pq)
@@ -104,7 +109,8 @@ def _census():
                 add(sk % ("false", 0), case("tiles4", kind, L, 10))
                 if W == 2:
                     add(sk % ("false", 1), case("tiles4", kind, L, 15))
-    add("smafa::kth_seed_kernel<0, 0, 0>", case("default", "aa", L_WIDE, None, 3, 65, E=5))
+    add("smafa::kth_seed_kernel<0, 0, 0>", case("default", "aa", L_WIDE, None, 3, 65, E=5),
+        case("kth_sample", "aa", L_WIDE, None, 3, 65, E=5, marker="sample counts"))
     add("smafa::scan_generic_kernel", case("default", "aa", L_WIDE, 20))
     return c
 
@@ -123,8 +129,8 @@ EXEMPT = {
     "smafa::permute_rows_kernel": "tests/test_gpu_layout.py::test_store_grown_by_small_appends_is_sorted_again",
     "smafa::distances_kernel": "tests/test_gpu_parity.py::test_get_distances_equals_oracle",
     "smafa::fill_u32_kernel": "tests/test_gpu_parity.py::test_kth_bound_modes",
-    "smafa::filter_rows_kernel": "tests/test_gpu_parity.py::test_kth_bound_modes",
-    "smafa::kth_from_counts_kernel": "tests/test_gpu_parity.py::test_kth_modes_counting_a_sample_first",
+    "smafa::filter_rows_kernel": "tests/test_gpu_kth_sample.py::test_sampled_counts_of_every_shape",
+    "smafa::kth_from_counts_kernel": "tests/test_gpu_kth_sample.py::test_sampled_counts_of_every_shape",
     "smafa::rows_to_keys_kernel": "tests/test_gpu_parity.py::test_dense_hits_overflow_path",
     "smafa::keys_to_rows_kernel": "tests/test_gpu_parity.py::test_dense_hits_overflow_path",
     "smafa::index_rows_kernel": "tests/test_gpu_index.py::test_index_rows_equal_scan_rows_and_oracle",

@@ -174,6 +174,8 @@ def _check_case(stores, name, c):
     assert want in kernels, "%s not launched by %s; launched: %s" % (want, c, sorted(kernels))
     if name.startswith("smafa::scan_wide_kernel") and not c["marker"] and c["zone"] == 0:
         assert name + " (zone level on)" not in kernels, sorted(kernels)
+    if name.startswith("smafa::kth_seed_kernel") and not c["marker"]:  # the seed form only: nothing counted a sample
+        assert name + " (sample counts)" not in kernels, sorted(kernels)
 
 
 @pytest.mark.parametrize("name,i,c", PARAMS, ids=["%s#%d" % (n, i) for n, i, _ in PARAMS])
@@ -187,7 +189,7 @@ def test_census_case_dense(dense_stores, name, i, c):
     _check_case(dense_stores, name, c)
 
 
-@pytest.mark.parametrize("switches", sorted(SWITCHES))
+@pytest.mark.parametrize("switches", sorted({c["switches"] for _, _, c in PARAMS if c["D"] is not None and not c["k"]}))
 def test_device_launch_capacity_of_every_fixed_bound_instantiation(switches):
     """smafa_scan_launch's capacity contract for every dense census case of a switch set with a bound and k = 0 — every
     instantiation but the seed forms, which write no rows (tests/device_capacity_worker.py --census, a process of its own:

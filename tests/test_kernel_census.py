@@ -93,6 +93,21 @@ def test_census_cases_are_well_formed():
         m = re.match(r"smafa::scan_wide_kernel<\d, \d, false, 3, 0>", name)
         if m:
             assert sorted(c["marker"] or "" for c in cases) == ["", "zone level on"], name
+    # the k-th seed kernel: every instantiation has its seed form (no marker) and its counting form over a sample, once each
+    seeds = [name for name in CENSUS if name.startswith("smafa::kth_seed_kernel<")]
+    assert len(seeds) == 13, seeds
+    for name in seeds:
+        cases = CENSUS[name]
+        assert sorted(c["marker"] or "" for c in cases) == ["", "sample counts"], name
+        plain, counts = sorted(cases, key=lambda c: c["marker"] or "")
+        assert counts["switches"] == "kth_sample" and plain["switches"] == "default", name
+        assert all(plain[f] == counts[f] for f in ("kind", "L", "D", "k", "nq", "E")) and plain["k"] == 3 and plain["nq"] == 65, name
+    # no other marker, and none anywhere else
+    for name, cases in CENSUS.items():
+        for c in cases:
+            assert c["marker"] in (None, "zone level on", "sample counts"), (name, c)
+            assert c["marker"] != "zone level on" or name.startswith("smafa::scan_wide_kernel<"), name
+            assert c["marker"] != "sample counts" or name.startswith("smafa::kth_seed_kernel<"), name
 
 
 def test_exempt_tests_exist():
