@@ -322,6 +322,58 @@ int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, u
 int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components);
 int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
 
+/* ------------------------------------------------- density clusters of the store (DBSCAN over the self-join) */
+/*
+ * "Which of the store's rows belong together at bound max_div, where enough rows agree": single linkage chains — one sparse
+ * run of rows, each one substitution from the next, fuses two abundant families into one component.  Here a row may extend
+ * a cluster only if enough rows lie within the bound of it: DBSCAN with eps = max_div over the scan's distance.  Subjects
+ * are numbered in append order; min_pts >= 1, and 0 is taken as 1.
+ *   degree[i]  = the number of OTHER subjects j != i with distance(i, j) <= max_div.  Equal rows at different subject
+ *                numbers count: abundance counts.
+ *   core       i is a core row iff degree[i] + 1 >= min_pts (the row counts itself, as in the textbook and in
+ *                scikit-learn's min_samples).
+ *   clusters   the connected components of the graph on the CORE rows whose edges are the core-core pairs within the bound.
+ *                A cluster's label is the smallest CORE subject number in it.
+ *   border     a non-core row with at least one core row within the bound.  Its label is the label of its
+ *                smallest-NUMBERED core neighbour (textbook DBSCAN leaves this to the visiting order; here it is canonical).
+ *   noise      every other row: label SMAFA_NONE.
+ *   counts[3]  = {clusters, core rows, noise rows}.
+ * The answer is a function of the store, max_div and min_pts alone: the same bytes under smafa_set_prefilter /
+ * smafa_set_zone_level / smafa_set_index, every SMAFA_JOIN_* setting and SMAFA_DENSITY_KEEP_MAX.
+ * labels[i] <= i holds for CORE rows only: a border row may be numbered below its cluster's label (the label is a core row,
+ * the border row is not).  For core rows labels[labels[i]] == labels[i]; every label that is not SMAFA_NONE is a core row.
+ *   min_pts <= 1: every row is core, and the labels are byte for byte those of smafa_db_self_components(db, max_div),
+ *                 counts = {its n_components, n_subjects, 0}.
+ *   min_pts == 2: the clusters are the components of size >= 2, and the singletons are noise.
+ * Not in the reference.  The pairs never leave the device.  The self-join's pieces are scanned as for smafa_db_self_launch and
+ * each piece's scratch list is consumed in place, in two phases with a kernel boundary between them (whether a row is core
+ * is known only once every pair is counted): phase 1 applies the self-join's exactly-once rule to the list, raises both
+ * degrees of every kept pair and moves the pair to a handle-owned KEPT PAIR LIST; phase 2 unites core-core pairs in a
+ * union-find over the core rows and offers every non-core end of a pair its core neighbour's number (an atomic minimum).
+ * Where the kept list held every pair, phase 2 is ONE launch over it and the store is joined once; otherwise the store is
+ * joined a second time and phase 2 reads the raw lists.  Both give the same bytes.  SMAFA_DENSITY_KEEP_MAX (environment, read
+ * when the handle is made, like SMAFA_JOIN_BLOCK) is the kept list's capacity in rows of 12 B, grown on demand; its default is
+ * the value of the join's scratch ceiling (SMAFA_JOIN_SCRATCH_MAX, 2^27 rows); 0 forces the two-join path.  Degrees are exact at
+ * any capacity.  With no core row at all phase 2 is skipped; with min_pts <= 1 and degrees == NULL nothing needs counting and
+ * the one join links directly, as the components call does.  Handle-owned scratch: 4 B x 3 per subject plus the kept list.
+ * Edges: an empty store writes nothing and counts 0 / 0 / 0.  max_div >= seq_len: no scan, every degree is n_subjects - 1, and
+ * all labels are 0 if n_subjects >= min_pts, otherwise all noise.  min_pts > n_subjects: all noise.  max_div = SMAFA_NONE, or
+ * a NULL handle, labels or counts: SMAFA_ERR_INVALID, with the argument named in smafa_last_error().  The self-join's one
+ * failure is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list; the handle stays usable).
+ *
+ * smafa_db_self_density_launch: device-resident form.  d_labels = device buffer of n_subjects uint32, d_degrees = device
+ * buffer of n_subjects uint32 or NULL, d_counts = device buffer of 3 uint64.  Synchronisation as for
+ * smafa_db_self_components_launch.  smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of record
+ * building, scans (of both joins, where two ran), count/keep passes, link passes and the flatten pass;
+ * smafa_last_call_kernels lists the scan-family instantiations first, then smafa_join::store_records_kernel, then
+ * smafa_join::inverse_order_kernel if it ran, then the smafa_dn:: kernels that ran.
+ *
+ * smafa_db_self_density: host form.  cap = capacity of `labels` (and of `degrees`, unless NULL) in entries; cap < n_subjects is
+ * SMAFA_ERR_INVALID, and nothing is written.
+ */
+int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_labels, void *d_degrees /* may be NULL */, void *d_counts /* 3 x uint64 */);
+int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t *labels, uint32_t *degrees /* may be NULL */, uint64_t cap, uint64_t counts[3]);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -465,6 +517,10 @@ int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, i
  * max_divergence (smafa_db_self_levels), "{i}\t{label_0}\t...\t{label_N}\n" in subject order.  Column t + 1 is the label
  * column of smafa_components at bound t.  An empty DB prints nothing. */
 int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa density` (not in the reference): the same DB, and per subject its density-cluster label and its degree
+ * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
+ * is printed as -1.  An empty DB prints nothing. */
+int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

@@ -250,6 +250,28 @@ class SubjectStore:
         check(lib().smafa_db_self_levels_launch(self._h, _opt(max_divergence), C.c_void_p(d_labels) if d_labels else None,
                                                 C.c_void_p(d_n_components) if d_n_components else None))
 
+    # ---- density clusters ------------------------------------------------------------------
+    def self_density(self, max_divergence: int, min_pts: int, degrees: bool = True):
+        """(labels, degrees, {"clusters", "core", "noise"}) — smafa_db_self_density: DBSCAN over the store's own rows with
+        eps = max_divergence.  degrees[i] = the number of other subjects within the bound of subject i (None with
+        degrees=False); a row is core iff degrees[i] + 1 >= min_pts; labels[i] = the smallest core subject number of i's
+        cluster, for a border row the label of its smallest-numbered core neighbour, NONE (0xFFFFFFFF) for noise.  uint32,
+        one per subject.  The pairs stay on the device."""
+        n = self.info().n_subjects
+        labels = np.zeros(max(n, 1), dtype=np.uint32)
+        degs = np.zeros(max(n, 1), dtype=np.uint32) if degrees else None
+        counts = (C.c_uint64 * 3)()
+        check(lib().smafa_db_self_density(self._h, _opt(max_divergence), int(min_pts), labels.ctypes.data,
+                                          degs.ctypes.data if degrees else None, n, counts))
+        return labels[:n], (degs[:n] if degrees else None), {"clusters": int(counts[0]), "core": int(counts[1]), "noise": int(counts[2])}
+
+    def self_density_launch(self, max_divergence: int, min_pts: int, d_labels: int, d_degrees: int, d_counts: int) -> None:
+        """device-resident form (smafa_db_self_density_launch): n_subjects uint32 labels in d_labels, as many degrees in
+        d_degrees (0: not wanted), {clusters, core rows, noise rows} in d_counts (3 device uint64)"""
+        check(lib().smafa_db_self_density_launch(self._h, _opt(max_divergence), int(min_pts), C.c_void_p(d_labels) if d_labels else None,
+                                                 C.c_void_p(d_degrees) if d_degrees else None,
+                                                 C.c_void_p(d_counts) if d_counts else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -522,6 +544,12 @@ def components(db_path: str, max_divergence: int, out_fd: int = 1, device: int =
     """`smafa components`: "i\\tlabel" per subject of the DB file, label = the smallest subject number of i's single-linkage
     component at max_divergence, to out_fd."""
     check(lib().smafa_components(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def density(db_path: str, max_divergence: int, min_pts: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa density`: "i\\tlabel\\tdegree" per subject of the DB file — its density-cluster label at max_divergence and
+    min_pts (-1 for noise) and the number of other subjects within the bound of it — to out_fd."""
+    check(lib().smafa_density(os.fsencode(db_path), _opt(max_divergence), int(min_pts), out_fd, device))
 
 
 def component_levels(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:

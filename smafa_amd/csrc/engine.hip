@@ -21,6 +21,7 @@
 #include "join.hip.h"
 #include "components.hip.h"
 #include "levels.hip.h"
+#include "density.hip.h"
 
 namespace smafa {
 
@@ -204,10 +205,18 @@ struct smafa_db {
         double rec_ms = 0, scan_ms = 0, filter_ms = 0;            // per stage, over the blocks of the last join
         double link_ms = 0, flatten_ms = 0;                       // components: init + link passes, the flatten launch
         uint32_t blocks = 0, rescans = 0;
+        // density (density.hip.h): parent holds parent[], degree[] and attach[], 4 B x 3 per subject, live for one call
+        DevBuf kept;   // the kept pair list: the rows count_keep_kernel kept, for the one link launch of a one-join call
+        DevBuf ctl;    // two uint64: the kept total, and "some row is core"
+        double count_ms = 0;  // density: init + count/keep passes
+        uint32_t joins = 0;   // density: how often the store was joined by the last call (0: no scan, 1 or 2)
+        bool kept_stuck = false;  // density: growing the kept list failed in this call; it is not tried again
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
     uint64_t join_scratch_max = 1ull << 27;  // rows the block's scratch list may grow to (1.5 GB) before the block is halved (SMAFA_JOIN_SCRATCH_MAX)
+    uint64_t density_keep_max = 1ull << 27;  // rows the density call's kept pair list may grow to; 0: never kept, the store is joined
+                                             // twice (SMAFA_DENSITY_KEEP_MAX; default: the value of join_scratch_max)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
     uint64_t hits_cap() const { return hits.cap / sizeof(smafa_hit); }
@@ -1443,28 +1452,70 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 // counters, J.parent one union-find per SCANNED level (E = min(max_div, L - 1) + 1 of them; the levels above are all zeros
 // and need no scan), the join runs once at bound E - 1 and hook_levels_kernel unites the subjects of a row at every level
 // from its distance upwards; flatten_levels_kernel writes every level in one launch.  Everything between is the shared path.
+// A fourth consumer, dn != nullptr (smafa_db_self_density_launch; density.hip.h): d_labels is n labels, d_count three
+// counters, J.parent holds parent[], degree[] and attach[].  The join runs at max_div with count_keep_kernel per piece
+// (the exactly-once rule, so pos_of[] as for the plain join), which raises both degrees of every kept pair and moves the
+// pair to J.kept while that has room; the kept total then decides: every pair is in J.kept — link_cores_kernel runs ONCE
+// over it (one join); else the store is joined a second time with link_cores_kernel reading each piece's raw list.  No
+// core row at all: no link.  min_pts <= 1 without degrees: nothing to count, the one join links directly, as components.
 static bool join_inverse_current(const smafa_db *db) {
     const auto &j = db->join;
     return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
 }
 
+struct DensityCall {
+    uint32_t min_pts;     // >= 1
+    uint32_t *d_degrees;  // device buffer of n degrees, or nullptr
+};
+
+// room in J.kept for `rows` rows, at most density_keep_max of them; the first `live` rows are carried over
+static int grow_kept(smafa_db *db, uint64_t rows, uint64_t live) {
+    DevBuf &K = db->join.kept;
+    rows = std::min<uint64_t>(rows, db->density_keep_max);
+    if (rows * sizeof(smafa_hit) <= K.cap) return SMAFA_OK;
+    const uint64_t want = std::min<uint64_t>(db->density_keep_max, std::max<uint64_t>(rows, K.cap / sizeof(smafa_hit) * 2));
+    DevBuf bigger;  // (a bare hipMalloc: a failure here is no failure of the call and leaves no text in smafa_last_error())
+    if (hipMalloc(&bigger.p, want * sizeof(smafa_hit)) == hipSuccess) bigger.cap = want * sizeof(smafa_hit);
+    if (!bigger.p) {
+        // no room for a larger list: the one there is stays as it is and overflows — counted, not stored — and the call
+        // falls back to the second join, which needs no list and gives the same bytes
+        (void)hipGetLastError();
+        db->join.kept_stuck = true;
+        log_line(2, "density: no memory for a kept pair list of %llu rows; the store will be joined twice", (unsigned long long)want);
+        return SMAFA_OK;
+    }
+    hipError_t e = hipSuccess;
+    if (live) e = hipMemcpyAsync(bigger.p, K.p, live * sizeof(smafa_hit), hipMemcpyDeviceToDevice, db->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
+    if (e != hipSuccess) {
+        bigger.release();
+        return set_error(SMAFA_ERR_DEVICE, "density: moving the kept pair list failed: %s", hipGetErrorString(e));
+    }
+    K.release();
+    K = bigger;
+    return SMAFA_OK;
+}
+
 static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count,
-                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0) {
+                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0, const DensityCall *dn = nullptr) {
     auto &J = db->join;
-    const bool linking = d_labels != nullptr, levelled = n_levels != 0;
+    const bool linking = d_labels != nullptr, levelled = n_levels != 0, density = dn != nullptr;
     // levels: the union-finds that are scanned for, and the one bound the join runs at
     const uint32_t E = levelled ? (uint32_t)std::min<uint64_t>(n_levels, std::max<uint32_t>(db->L, 1u)) : 0u;
     const uint32_t scan_div = levelled ? E - 1u : max_div;
+    // density: which consumer a piece's list goes to — 1: count_keep_kernel, 2: link_cores_kernel (0: not a density call)
+    int dn_stage = !density ? 0 : (dn->min_pts > 1u || dn->d_degrees) ? 1 : 2;
     db->call_kernels.clear();
     db->call_ms = 0.f;
     db->call_launches = db->call_scans = 0;
     db->last_launches = 0;
     db->timed = false;
-    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = 0.0;
-    J.blocks = J.rescans = 0;
+    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = 0.0;
+    J.blocks = J.rescans = J.joins = 0;
+    J.kept_stuck = false;
     int rc = use_device(db);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_count, 0, (levelled ? (size_t)n_levels : 1u) * sizeof(unsigned long long), db->stream));
+    HIP_TRY(hipMemsetAsync(d_count, 0, (levelled ? (size_t)n_levels : density ? 3u : 1u) * sizeof(unsigned long long), db->stream));
     db->call_timed = true;
     if (db->n < (linking ? 1u : 2u)) return SMAFA_OK;
     // components of one row, or at a bound no two rows can exceed: nothing to scan (the second would list all n^2 pairs to
@@ -1482,10 +1533,19 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     const uint32_t n = (uint32_t)db->n;
     bool inverted = false;
     if (linking) {  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
-        rc = J.parent.ensure((size_t)n * (levelled ? E : 1u) * sizeof(uint32_t));
+        rc = J.parent.ensure((size_t)n * (levelled ? E : density ? 3u : 1u) * sizeof(uint32_t));
+        if (!rc && density) rc = J.ctl.ensure(2 * sizeof(unsigned long long));
         if (rc) return rc;
         HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (levelled) {
+        if (density) {  // parent[] | degree[] | attach[]; every row within the bound of every other: degrees n - 1, one set
+            const bool all_near = max_div >= db->L;
+            HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
+            hipLaunchKernelGGL(smafa_dn::init_density_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
+                               J.parent.as<uint32_t>() + n, J.parent.as<uint32_t>(), J.parent.as<uint32_t>() + 2 * (size_t)n, n,
+                               all_near ? n - 1u : 0u, all_near ? 1u : 0u);
+            HIP_TRY(hipGetLastError());
+            db->call_launches++;
+        } else if (levelled) {
             hipLaunchKernelGGL(smafa_lv::init_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, E);
             HIP_TRY(hipGetLastError());
             db->call_launches++;
@@ -1497,7 +1557,8 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
             db->call_launches++;
         }
         HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-    } else if (!join_inverse_current(db)) {
+    }
+    if ((!linking || (dn_stage == 1 && !no_scans)) && !join_inverse_current(db)) {
         J.valid = false;
         rc = J.pos_of.ensure((size_t)n * sizeof(uint32_t));
         if (rc) return rc;
@@ -1513,116 +1574,180 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     }
     smafa_qset *qs = &db->join_q;
     qs->db = db;
-    bool filtered = false, linked = false, filter_pending = linking;  // (linking: the initialisation of parent[] is pending)
+    bool filtered = false, linked = false, counted = false, filter_pending = linking;  // (linking: the initialisation of parent[] is pending)
     auto take_filter_time = [&]() {  // the filter / link pass of the piece before: finished by the time a later wait returns
         float ms = 0.f;
         if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) {
-            (linking ? J.link_ms : J.filter_ms) += ms;
+            (!linking ? J.filter_ms : dn_stage == 1 ? J.count_ms : J.link_ms) += ms;
             if (linking)
-                log_line(3, "%s: parent[] %s, %.3f ms", levelled ? "levels" : "components", linked ? "linked with a piece's rows" : "initialised", ms);
+                log_line(3, "%s: parent[] %s, %.3f ms", density ? "density" : levelled ? "levels" : "components",
+                         linked ? "linked with a piece's rows" : counted ? "untouched, a piece's rows counted" : "initialised", ms);
         }
         filter_pending = false;
     };
+    // density: the three arrays of J.parent
+    uint32_t *const parent = density ? J.parent.as<uint32_t>() : nullptr, *const degree = density ? parent + n : nullptr;
+    uint32_t *const attach = density ? parent + 2 * (size_t)n : nullptr;
+    unsigned long long kept_seen = 0;  // density: the kept total as of the pieces before the one just scanned
     const uint64_t span_rows = db->join_block * db->join_stride;
-    uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
-    for (uint64_t p0 = 0; p0 < db->n && !no_scans; p0 += span_rows) {
-        const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
-        const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
-        const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
-        // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
-        const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
-        qs->nq = (uint64_t)S * R;
-        qs->serial = g_qset_serial.fetch_add(1);
-        rc = qs->qrec.ensure(padded * db->QS * sizeof(uint32_t));
-        if (!rc) rc = qs->thr.ensure(padded * sizeof(uint32_t));
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
-        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
-        const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
-        hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0, db->stream,
-                           reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0, (uint32_t)p1, S, R,
-                           qs->qrec.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
-        db->call_launches++;
-        bool rec_timed = false;
-        for (uint32_t b = 0; b < S; b++) {
-            const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
-            for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
-                const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
-                rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
-                                db->count.as<unsigned long long>(), t0);
-                if (rc) return rc;
-                unsigned long long count = 0;
-                HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-                HIP_TRY(hipStreamSynchronize(db->stream));
-                take_filter_time();
-                const float before = db->call_ms;
-                note_call_scan(db);
-                const double scan_ms = db->call_ms - before;
-                J.scan_ms += scan_ms;
-                float ms = 0.f;
-                if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
-                rec_timed = true;
-                log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
-                         (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
-                if (count > db->hits_cap()) {
-                    J.rescans++;
-                    if (count <= db->join_scratch_max) {  // the count is exact: room for it, and the same piece once more
-                        rc = db->hits.ensure(count * sizeof(smafa_hit));
-                        if (rc) return rc;
-                        continue;
+    auto join_pass = [&]() -> int {  // the whole join, every piece's list to the consumer of this call (and stage)
+        uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
+        J.joins++;
+        for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
+            const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
+            const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
+            const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
+            // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
+            const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
+            qs->nq = (uint64_t)S * R;
+            qs->serial = g_qset_serial.fetch_add(1);
+            int rc = qs->qrec.ensure(padded * db->QS * sizeof(uint32_t));
+            if (!rc) rc = qs->thr.ensure(padded * sizeof(uint32_t));
+            if (rc) return rc;
+            HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+            HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
+            const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
+            hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0, db->stream,
+                               reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0, (uint32_t)p1, S, R,
+                               qs->qrec.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+            db->call_launches++;
+            bool rec_timed = false;
+            for (uint32_t b = 0; b < S; b++) {
+                const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
+                for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
+                    const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
+                    rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
+                                    db->count.as<unsigned long long>(), t0);
+                    if (rc) return rc;
+                    unsigned long long count = 0;
+                    HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+                    if (dn_stage == 1)  // (every count/keep pass in front of this scan has ended with it)
+                        HIP_TRY(hipMemcpyAsync(&kept_seen, J.ctl.p, sizeof kept_seen, hipMemcpyDeviceToHost, db->stream));
+                    HIP_TRY(hipStreamSynchronize(db->stream));
+                    take_filter_time();
+                    const float before = db->call_ms;
+                    note_call_scan(db);
+                    const double scan_ms = db->call_ms - before;
+                    J.scan_ms += scan_ms;
+                    float ms = 0.f;
+                    if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
+                    rec_timed = true;
+                    log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
+                             (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
+                    if (count > db->hits_cap()) {
+                        J.rescans++;
+                        if (count <= db->join_scratch_max) {  // the count is exact: room for it, and the same piece once more
+                            rc = db->hits.ensure(count * sizeof(smafa_hit));
+                            if (rc) return rc;
+                            continue;
+                        }
+                        if (q1 - q0 > 64) {
+                            piece = std::max<uint64_t>(64, ((q1 - q0) / 2 + 63) / 64 * 64);
+                            continue;
+                        }
+                        // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
+                        return set_error(SMAFA_ERR_NOMEM,
+                                         "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
+                                         "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
                     }
-                    if (q1 - q0 > 64) {
-                        piece = std::max<uint64_t>(64, ((q1 - q0) / 2 + 63) / 64 * 64);
-                        continue;
+                    const dim3 list_grid((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256));
+                    if (count && dn_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
+                        // room for whatever this piece keeps on top of the rows kept so far, while the knob allows it
+                        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
+                        if (!J.kept_stuck) {
+                            rc = grow_kept(db, kept_seen + count, std::min<uint64_t>(kept_seen, have));
+                            if (rc) return rc;
+                        }
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_dn::count_keep_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), degree, dn->min_pts, J.kept.as<smafa_hit>(),
+                                           (unsigned long long)std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max),
+                                           J.ctl.as<unsigned long long>());
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = counted = true;
+                        db->call_launches++;
+                    } else if (count && dn_stage == 2) {
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_dn::link_cores_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, degree, dn->min_pts, parent, attach);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = linked = true;
+                        db->call_launches++;
+                    } else if (count && levelled) {
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_lv::hook_levels_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, J.parent.as<uint32_t>(), n, E);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = linked = true;
+                        db->call_launches++;
+                    } else if (count && linking) {
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_cc::link_rows_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, J.parent.as<uint32_t>());
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = linked = true;
+                        db->call_launches++;
+                    } else if (count) {
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_join::join_filter_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), d_hits, (unsigned long long)cap, d_count);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = filtered = true;
+                        db->call_launches++;
                     }
-                    // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
-                    return set_error(SMAFA_ERR_NOMEM,
-                                     "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
-                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
+                    J.blocks++;
+                    q0 = q1;
+                    if (piece < db->join_block && count * 4 < db->join_scratch_max) piece = std::min<uint64_t>(db->join_block, piece * 2);
                 }
-                if (count && levelled) {  // (count <= capacity here: a truncated list was scanned again above)
-                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                    hipLaunchKernelGGL(smafa_lv::hook_levels_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
-                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
-                                       J.parent.as<uint32_t>(), n, E);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                    filter_pending = linked = true;
-                    db->call_launches++;
-                } else if (count && linking) {
-                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                    hipLaunchKernelGGL(smafa_cc::link_rows_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
-                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
-                                       J.parent.as<uint32_t>());
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                    filter_pending = linked = true;
-                    db->call_launches++;
-                } else if (count) {
-                    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                    hipLaunchKernelGGL(smafa_join::join_filter_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)),
-                                       dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order,
-                                       J.pos_of.as<uint32_t>(), d_hits, (unsigned long long)cap, d_count);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                    filter_pending = filtered = true;
-                    db->call_launches++;
-                }
-                J.blocks++;
-                q0 = q1;
-                if (piece < db->join_block && count * 4 < db->join_scratch_max) piece = std::min<uint64_t>(db->join_block, piece * 2);
             }
+            HIP_TRY(hipStreamSynchronize(db->stream));  // the span's records are overwritten next
+            take_filter_time();
         }
-        HIP_TRY(hipStreamSynchronize(db->stream));  // the span's records are overwritten next
+        return SMAFA_OK;
+    };
+    if (!no_scans) {
+        rc = join_pass();
+        if (rc) return rc;
+    }
+    if (dn_stage == 1 && !no_scans) {  // every degree is final: link from the kept list, or join once more, or not at all
+        unsigned long long ctl[2] = {0, 0};  // the kept total; "some row is core"
+        HIP_TRY(hipMemcpyAsync(ctl, J.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, db->stream));
+        HIP_TRY(hipStreamSynchronize(db->stream));
         take_filter_time();
+        dn_stage = 2;
+        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
+        if (ctl[0] == 0 || (dn->min_pts > 1u && !ctl[1])) {
+            // no pair, or no core row: nothing to link, every row keeps the set and the attach[] it was given
+        } else if (ctl[0] <= have) {
+            HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+            hipLaunchKernelGGL(smafa_dn::link_cores_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (ctl[0] + 255) / 256)), dim3(256), 0,
+                               db->stream, J.kept.as<smafa_hit>(), ctl[0], 0u, 1u, 1u, (const uint32_t *)nullptr, degree, dn->min_pts, parent,
+                               attach);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+            filter_pending = linked = true;
+            db->call_launches++;
+        } else {
+            log_line(3, "density: %llu pairs, the kept list holds %llu: joining once more to link", ctl[0], (unsigned long long)have);
+            rc = join_pass();
+            if (rc) return rc;
+        }
     }
     if (linking) {  // the kernel boundary makes every hook visible: labels[i] = root(i), representatives counted
         HIP_TRY(hipStreamSynchronize(db->stream));
         take_filter_time();
         HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (levelled)
+        if (density)
+            hipLaunchKernelGGL(smafa_dn::flatten_density_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, parent, degree, attach,
+                               n, dn->min_pts, d_labels, dn->d_degrees, d_count);
+        else if (levelled)
             hipLaunchKernelGGL(smafa_lv::flatten_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
                                J.parent.as<uint32_t>(), n, E, n_levels, d_labels, d_count);
         else
@@ -1634,9 +1759,20 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         HIP_TRY(hipStreamSynchronize(db->stream));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms = ms;
-        db->call_ms += (float)(J.rec_ms + J.link_ms + J.flatten_ms);
+        db->call_ms += (float)(J.rec_ms + J.count_ms + J.link_ms + J.flatten_ms);
         db->call_timed = true;  // (scan_range cleared it)
         if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+        if (density) {
+            if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
+            note_call_kernel(db, "smafa_dn::init_density_kernel");
+            if (counted) note_call_kernel(db, "smafa_dn::count_keep_kernel");
+            if (linked) note_call_kernel(db, "smafa_dn::link_cores_kernel");
+            note_call_kernel(db, "smafa_dn::flatten_density_kernel");
+            log_line(2, "density of %u rows at bound %u, min_pts %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
+                     "count/keep %.3f ms, link %.3f ms, flatten %.3f ms", n, max_div, dn->min_pts, J.blocks + J.rescans, J.rescans, J.joins,
+                     J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms);
+            return SMAFA_OK;
+        }
         if (levelled) {
             note_call_kernel(db, "smafa_lv::init_levels_kernel");
             if (linked) note_call_kernel(db, "smafa_lv::hook_levels_kernel");
@@ -2124,6 +2260,14 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *jv = getenv("SMAFA_JOIN_BLOCK")) db->join_block = std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64);
     if (const char *jv = getenv("SMAFA_JOIN_STRIDE")) db->join_stride = std::min<uint64_t>(4096, std::max<uint64_t>(1, strtoull(jv, nullptr, 10)));
     if (const char *jv = getenv("SMAFA_JOIN_SCRATCH_MAX")) db->join_scratch_max = std::max<uint64_t>(4096, strtoull(jv, nullptr, 10));
+    db->density_keep_max = db->join_scratch_max;
+    if (const char *jv = getenv("SMAFA_DENSITY_KEEP_MAX")) {  // any number of rows, 0 included (two joins); not a number: ignored, aloud
+        char *end = nullptr;
+        const unsigned long long rows = strtoull(jv, &end, 10);
+        if (end != jv && *end == 0 && *jv != '-') db->density_keep_max = rows;
+        else log_line(0, "SMAFA_DENSITY_KEEP_MAX=\"%s\" is not a number of rows: ignored, the kept pair list may hold %llu rows", jv,
+                      (unsigned long long)db->density_keep_max);
+    }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) db->n_cu = prop.multiProcessorCount;
     hipError_t e = hipStreamCreateWithFlags(&db->own_stream, hipStreamNonBlocking);
@@ -2254,7 +2398,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
-                      &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
+                      &db->join.kept, &db->join.ctl, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
         if (e) (void)hipEventDestroy(e);
@@ -2797,6 +2941,51 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_levels");
+}
+
+int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_labels, void *d_degrees,
+                                 void *d_counts) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL handle");
+    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL labels");
+    if (!d_counts) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL counts");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: density needs a bound (max_div)");
+    const DensityCall dn = {std::max<uint32_t>(min_pts, 1u), (uint32_t *)d_degrees};
+    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_counts, (uint32_t *)d_labels, 0, &dn);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_density_launch");
+}
+
+int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t *labels, uint32_t *degrees, uint64_t cap,
+                          uint64_t counts[3]) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL handle");
+    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL labels");
+    if (!counts) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL counts");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: density needs a bound (max_div)");
+    if (cap < db->n)  // (nothing is written, the counts included)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: labels holds %llu entries, the store has %llu subjects",
+                         (unsigned long long)cap, (unsigned long long)db->n);
+    counts[0] = counts[1] = counts[2] = 0;
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // the labels, and the degrees behind them, on their way to the caller: 4 B (8 B) per subject
+    rc = J.out.ensure(std::max<uint64_t>(n, 1) * (degrees ? 2u : 1u) * sizeof(uint32_t));
+    if (!rc) rc = J.cnt.ensure(3 * sizeof(unsigned long long));
+    if (rc) return rc;
+    const DensityCall dn = {std::max<uint32_t>(min_pts, 1u), degrees ? J.out.as<uint32_t>() + n : nullptr};
+    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), 0, &dn);
+    if (rc) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
+    HIP_TRY(hipMemcpyAsync(counts, J.cnt.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    if (n && degrees) HIP_TRY(hipMemcpyAsync(degrees, J.out.as<uint32_t>() + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    if (J.kept.cap > (512ull << 20)) J.kept.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_density");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -735,6 +735,48 @@ int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out
     return smafa::exception_code("smafa_component_levels");
 }
 
+// ------------------------------------------------------------------------------------ density
+// The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
+// "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.
+int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_density: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_density: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    std::vector<uint32_t> labels((size_t)info.n_subjects), degrees((size_t)info.n_subjects);
+    uint64_t counts[3] = {0, 0, 0};
+    rc = smafa_db_self_density(store.db, max_divergence, min_pts, labels.data(), degrees.data(), labels.size(), counts);
+    if (rc) return rc;
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // rows per write
+    for (size_t b0 = 0; b0 < labels.size(); b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(labels.size(), b0 + block); i < e; i++) {
+            append_u32(text, (uint32_t)i);
+            text.push_back('\t');
+            if (labels[i] == SMAFA_NONE) text += "-1";
+            else append_u32(text, labels[i]);
+            text.push_back('\t');
+            append_u32(text, degrees[i]);
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu clusters, %llu core and %llu noise among %llu sequences within %u at min_pts %u, took %llu seconds",
+             (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)labels.size(),
+             max_divergence, min_pts, (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_density");
+}
+
 // ------------------------------------------------------------------------------------ cluster
 //
 // The reference handles one record at a time: skip exact duplicates, scan the record against the

@@ -8,6 +8,8 @@
 //   pairs   -d/--database FILE  --max-divergence INT   (this build only: every pair of the DB's own subjects within the bound)
 //   components -d/--database FILE  --max-divergence INT  [--levels]   (this build only: the single-linkage component of
 //           every subject; --levels: at every bound 0 .. INT)
+//   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
+//           number of neighbours within the bound of every subject)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -47,7 +49,11 @@ static int usage(const char *msg, FILE *to = stderr) {
             "components -d, --database <FILE>  --max-divergence <INT>  [--levels] [--device <N>]  (not in the reference: single-linkage\n"
             "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
             "        smallest sequence number of its component; --levels: one label column per bound 0 .. <INT>,\n"
-            "        \"i<TAB>label_0<TAB>...<TAB>label_INT\", from one join)\n");
+            "        \"i<TAB>label_0<TAB>...<TAB>label_INT\", from one join)\n"
+            "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
+            "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
+            "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
+            "        core sequence number of its cluster, for a non-core sequence that of its smallest core neighbour, -1 for noise)\n");
     return 2;
 }
 
@@ -87,7 +93,8 @@ int main(int argc, char **argv) {
     const bool is_cluster = cmd == "cluster";
     const char *input = nullptr, *database = nullptr, *query = nullptr;
     std::vector<const char *> count_paths;
-    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0;
+    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0;
+    bool have_min_pts = false;
     bool have_max_div = false, packed = false, no_gpu = false, levels = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
@@ -121,6 +128,9 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &device)) return usage("--device needs an unsigned integer");
         } else if (a == "--packed") {
             packed = true;
+        } else if (a == "--min-pts" && cmd == "density") {
+            if (!parse_u32(value(), &min_pts)) return usage("--min-pts needs an unsigned integer");
+            have_min_pts = true;
         } else if (a == "--levels" && cmd == "components") {
             levels = true;
         } else if (a == "--no-gpu") {
@@ -187,6 +197,11 @@ int main(int argc, char **argv) {
         if (!database) return usage("components needs --database");
         if (!have_max_div) return usage("components needs --max-divergence");
         rc = levels ? smafa_component_levels(database, max_div, 1, (int)device) : smafa_components(database, max_div, 1, (int)device);
+    } else if (cmd == "density") {
+        if (!database) return usage("density needs --database");
+        if (!have_max_div) return usage("density needs --max-divergence");
+        if (!have_min_pts) return usage("density needs --min-pts");
+        rc = smafa_density(database, max_div, min_pts, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);
