@@ -24,6 +24,26 @@ int exception_code(const char *where) noexcept;
 int scan_to_host(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div, uint32_t max_num_hits,
                  std::vector<smafa_hit> &out);
 
+// Queries per workgroup pass of a scan launch over n_wg_tiles four-wave shares of the store: `override` (smafa_set_query_block)
+// as it is, else nq split into as many blocks as give the grid about 16 workgroups per slot, each of at least 256 queries.  The
+// slot count, n_cu x 6, is the first scan kernel's (6 four-wave workgroups per CU); today's zone kernel runs 14 two-wave workgroups
+// per CU.  The constants are kept because the block count they give still sits on the flat part of the sweep (aa 10M x 10 000:
+// 2-4 blocks 0.415-0.426 ms, 6 — the automatic one — 0.424-0.432, 8 0.44, 12 0.46; nt 10M x 100 000: 8 blocks, the automatic
+// count, 1.97 ms, 4 2.03, 2 2.16: profiles/r12_query_block.txt), not because they describe the kernel that runs now.
+// chunk > 1: the kernel walks a block in chunks of that many queries, and the automatic size is rounded up to whole chunks — a
+// block of 1667 ends in a chunk of 3 live queries that costs a whole one.
+inline uint32_t query_block_size(uint32_t override, uint32_t n_cu, uint32_t n_wg_tiles, uint32_t nq, uint32_t chunk) {
+    if (override) return override < (nq ? nq : 1u) ? override : (nq ? nq : 1u);
+    const uint32_t want_items = n_cu * 6u * 16u;
+    uint32_t nqb = (want_items + n_wg_tiles - 1) / n_wg_tiles;
+    const uint32_t max_nqb = nq / 256u > 1u ? nq / 256u : 1u;
+    nqb = nqb < max_nqb ? nqb : max_nqb;
+    if (nqb < 1u) nqb = 1u;
+    uint32_t qb = (nq + nqb - 1) / nqb;
+    if (chunk > 1u) qb = (qb + chunk - 1) / chunk * chunk;
+    return qb ? qb : 1u;
+}
+
 // Bring the HIP runtime and the device context up (a few hundred ms the first time in a process).  The drivers call it
 // on a helper thread while they read and decode their input; failures are ignored here — the first real call reports.
 void warm_device(int device);

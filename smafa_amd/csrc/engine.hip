@@ -765,17 +765,10 @@ static void launch_scan(const smafa_db *db, const uint32_t *d_qrec, const ScanAr
                        reinterpret_cast<const uint4 *>(db->d_planes), d_qrec, a, db->P, db->PQ, db->W, db->QS);
 }
 
-// queries per workgroup pass: big enough that the tile load is amortised (the scan is then bound by
-// VALU issue, not HBM), small enough that the grid has many more workgroups than the chip has slots.
-static uint32_t choose_query_block(const smafa_db *db, uint32_t n_wg_tiles, uint32_t nq) {
-    if (db->qb_override) return std::min<uint32_t>(std::max<uint32_t>(db->qb_override, 1u), std::max(nq, 1u));
-    const uint32_t slots = (uint32_t)db->n_cu * 6u;  // 6 workgroups of 4 waves per CU at the kernel's register budget
-    const uint32_t want_items = slots * 16u;
-    uint32_t nqb = (want_items + n_wg_tiles - 1) / n_wg_tiles;
-    const uint32_t max_nqb = std::max(1u, nq / 256u);
-    nqb = std::max(1u, std::min(nqb, max_nqb));
-    uint32_t qb = (nq + nqb - 1) / nqb;
-    return std::max(qb, 1u);
+// queries per workgroup pass (query_block_size, engine.h); whole_chunks: the launch walks its block in chunks of kChunk queries
+// (the zone kernel with more than 64 queries)
+static uint32_t choose_query_block(const smafa_db *db, uint32_t n_wg_tiles, uint32_t nq, bool whole_chunks) {
+    return query_block_size(db->qb_override, (uint32_t)db->n_cu, n_wg_tiles, nq, whole_chunks ? (uint32_t)kChunk : 1u);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1010,7 +1003,8 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
     a.q_end = q_end;
     // (the block size is chosen per 4-wave share of the store whatever the workgroup size, so that it does not change
     // with kZoneWgWaves: profiles/r02_zone_variants.txt)
-    a.qb_size = choose_query_block(db, (tile_end - tile_begin + kWgWaves * T - 1) / (kWgWaves * T), q_end - q_begin);
+    a.qb_size = choose_query_block(db, (tile_end - tile_begin + kWgWaves * T - 1) / (kWgWaves * T), q_end - q_begin,
+                                   zone && q_end - q_begin > 64u);
     // fixed common bound: no per-query array, no fill launch; per_query_bounds: fixed bounds read from thr
     a.thr = (k_tight || per_query_bounds) ? qs->thr.as<uint32_t>() : nullptr;
     a.thr0 = thr0;
