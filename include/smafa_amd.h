@@ -353,7 +353,8 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
  * Where the kept list held every pair, phase 2 is ONE launch over it and the store is joined once; otherwise the store is
  * joined a second time and phase 2 reads the raw lists.  Both give the same bytes.  SMAFA_DENSITY_KEEP_MAX (environment, read
  * when the handle is made, like SMAFA_JOIN_BLOCK) is the kept list's capacity in rows of 12 B, grown on demand; its default is
- * the value of the join's scratch ceiling (SMAFA_JOIN_SCRATCH_MAX, 2^27 rows); 0 forces the two-join path.  Degrees are exact at
+ * the value of the join's scratch ceiling (SMAFA_JOIN_SCRATCH_MAX, 2^27 rows); 0 forces the two-join path.  (The list and
+ * its capacity are shared with smafa_db_self_peaks below: one list per handle, whichever call fills it.)  Degrees are exact at
  * any capacity.  With no core row at all phase 2 is skipped; with min_pts <= 1 and degrees == NULL nothing needs counting and
  * the one join links directly, as the components call does.  Handle-owned scratch: 4 B x 3 per subject plus the kept list.
  * Edges: an empty store writes nothing and counts 0 / 0 / 0.  max_div >= seq_len: no scan, every degree is n_subjects - 1, and
@@ -373,6 +374,56 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
  */
 int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_labels, void *d_degrees /* may be NULL */, void *d_counts /* 3 x uint64 */);
 int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t *labels, uint32_t *degrees /* may be NULL */, uint64_t cap, uint64_t counts[3]);
+
+/* ------------------------------------------------- abundance-peak clusters of the store (amplicon denoising over the self-join) */
+/*
+ * "Which more abundant row does each row most plausibly derive from": density clusters cure chaining only where the bridge
+ * is sparse, and need a threshold.  Where abundance falls off continuously between two abundant rows, every min_pts either
+ * fuses them or drops the thin part as noise.  Here every row climbs to the heaviest row within the bound, and a cluster is
+ * everything that climbs to the same local maximum (the UNOISE / swarm partition), with no threshold at all.
+ * max_div = D is the neighbourhood, radius = r <= D the ball the weight is counted in; radius = SMAFA_NONE means r = D.
+ *   weight[i]  = 1 + the number of OTHER subjects within distance r of i.  r = 0 is abundance: the number of exact copies,
+ *                itself included.  r = D is the ball count: smafa_db_self_density's degree[i] + 1.
+ *   key(i)     = the pair (weight[i], -i) in lexicographic order: the heavier row wins, ties go to the smaller subject number.
+ *                It is a total order with no equal keys.
+ *   parent[i]  = the subject with the greatest key among {i} and {j : distance(i, j) <= D}.  parent[i] == i makes i a PEAK:
+ *                no row within the bound outranks it.
+ *   labels[i]  = the peak reached from i by following parent[].  The key strictly increases along every step, so parent[]
+ *                is a forest and the walk ends.
+ *   n_peaks    = the number of peaks = the number of clusters.
+ * The answer is a function of the store, D and r alone: the same bytes under smafa_set_prefilter / smafa_set_zone_level /
+ * smafa_set_index, every SMAFA_JOIN_* setting and SMAFA_DENSITY_KEEP_MAX.  Exact copies of one sequence have the same
+ * neighbourhood, so all of them get the same parent: the smallest-numbered copy, or the same heavier neighbour.  labels[i]
+ * need not be <= i.  labels[labels[i]] == labels[i], and labels[i] lies in i's single-linkage component at D.
+ * Not in the reference.  The pairs never leave the device.  Two phases with a kernel boundary between them, as for the
+ * density call (a key is known only once every pair is weighed): phase 1 applies the self-join's exactly-once rule to each
+ * piece's list, raises both weights of every kept pair within r and moves EVERY kept pair to the handle's kept pair list —
+ * the one list the density call uses, so SMAFA_DENSITY_KEEP_MAX is the capacity of that one shared list for both calls, 0
+ * forcing the two-join path; phase 2 offers the lower-keyed row of every pair the higher key (an atomic maximum on an 8-byte
+ * slot per subject), in ONE launch over the kept list where that held every pair, otherwise in a second join that reads the
+ * raw lists.  Both give the same bytes.  With no pair at all phase 2 is skipped.  The labels are then flattened by pointer
+ * doubling in place, one launch per round until a round changes nothing (at most 33 rounds; no thread ever walks a chain).
+ * Handle-owned scratch: 12 B per subject plus the kept list.
+ * Edges: an empty store writes nothing and n_peaks = 0.  One row: labels {0}, parents {0}, weights {1}, 1 peak, no scan.
+ * max_div >= seq_len: every row is every row's neighbour, so there is one peak, the row of greatest key, and every parent
+ * and label is that row; the weights come from a count-only join at r (nothing is kept, nothing is climbed), and if r >=
+ * seq_len too there is no scan at all and every weight is n_subjects.  SMAFA_ERR_INVALID, with the argument named in
+ * smafa_last_error() and nothing written: a NULL handle, labels or n_peaks; max_div = SMAFA_NONE; radius > max_div (other
+ * than SMAFA_NONE); cap < n_subjects.  The self-join's one failure is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone
+ * overfill the scratch list; the handle stays usable).
+ *
+ * smafa_db_self_peaks_launch: device-resident form.  d_labels = device buffer of n_subjects uint32, d_parents and d_weights =
+ * device buffers of n_subjects uint32 or NULL, d_n_peaks = device uint64.  Synchronisation as for
+ * smafa_db_self_components_launch.  smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of record
+ * building, scans (of both joins, where two ran), weigh/keep passes, the climb, the settle pass and the jump rounds;
+ * smafa_last_call_kernels lists the scan-family instantiations first, then smafa_join::store_records_kernel, then
+ * smafa_join::inverse_order_kernel if it ran, then the smafa_pk:: kernels that ran: init_peaks_kernel, weigh_keep_kernel,
+ * climb_kernel, crown_kernel, settle_kernel, jump_kernel.
+ *
+ * smafa_db_self_peaks: host form.  cap = capacity of `labels` (and of `parents` and `weights`, unless NULL) in entries.
+ */
+int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, void *d_labels, void *d_parents /* may be NULL */, void *d_weights /* may be NULL */, void *d_n_peaks /* uint64 */);
+int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *labels, uint32_t *parents /* may be NULL */, uint32_t *weights /* may be NULL */, uint64_t cap, uint64_t *n_peaks);
 
 /* ------------------------------------------------- the same store on several GPUs */
 /*
@@ -521,6 +572,10 @@ int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out
  * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
  * is printed as -1.  An empty DB prints nothing. */
 int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int out_fd, int device);
+/* `smafa peaks` (not in the reference): the same DB, and per subject its abundance-peak label, its parent and its weight
+ * (smafa_db_self_peaks at max_divergence and radius), "{i}\t{label}\t{parent}\t{weight}\n" in subject order.  An empty DB
+ * prints nothing. */
+int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

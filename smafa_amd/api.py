@@ -272,6 +272,32 @@ class SubjectStore:
                                                  C.c_void_p(d_degrees) if d_degrees else None,
                                                  C.c_void_p(d_counts) if d_counts else None))
 
+    # ---- abundance-peak clusters -----------------------------------------------------------
+    def self_peaks(self, max_divergence: int, radius: Optional[int] = 0, parents: bool = True, weights: bool = True):
+        """(labels, parents, weights, n_peaks) — smafa_db_self_peaks: weights[i] = 1 + the number of other subjects within
+        `radius` of subject i (0: its exact copies; None: max_divergence), parents[i] = the subject of greatest (weight,
+        smaller number) among i and the subjects within max_divergence of it — i itself makes i a peak — labels[i] = the peak
+        reached from i along the parents.  uint32, one per subject; parents / weights are None where not wanted.  The pairs
+        stay on the device."""
+        n = self.info().n_subjects
+        labels = np.zeros(max(n, 1), dtype=np.uint32)
+        par = np.zeros(max(n, 1), dtype=np.uint32) if parents else None
+        wts = np.zeros(max(n, 1), dtype=np.uint32) if weights else None
+        count = C.c_uint64(0)
+        check(lib().smafa_db_self_peaks(self._h, _opt(max_divergence), _opt(radius), labels.ctypes.data,
+                                        par.ctypes.data if parents else None, wts.ctypes.data if weights else None, n,
+                                        C.byref(count)))
+        return labels[:n], (par[:n] if parents else None), (wts[:n] if weights else None), int(count.value)
+
+    def self_peaks_launch(self, max_divergence: int, radius: Optional[int], d_labels: int, d_parents: int, d_weights: int,
+                          d_n_peaks: int) -> None:
+        """device-resident form (smafa_db_self_peaks_launch): n_subjects uint32 labels in d_labels, as many parents in
+        d_parents and weights in d_weights (0: not wanted), the number of peaks in *d_n_peaks (device uint64)"""
+        check(lib().smafa_db_self_peaks_launch(self._h, _opt(max_divergence), _opt(radius), C.c_void_p(d_labels) if d_labels else None,
+                                               C.c_void_p(d_parents) if d_parents else None,
+                                               C.c_void_p(d_weights) if d_weights else None,
+                                               C.c_void_p(d_n_peaks) if d_n_peaks else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -550,6 +576,12 @@ def density(db_path: str, max_divergence: int, min_pts: int, out_fd: int = 1, de
     """`smafa density`: "i\\tlabel\\tdegree" per subject of the DB file — its density-cluster label at max_divergence and
     min_pts (-1 for noise) and the number of other subjects within the bound of it — to out_fd."""
     check(lib().smafa_density(os.fsencode(db_path), _opt(max_divergence), int(min_pts), out_fd, device))
+
+
+def peaks(db_path: str, max_divergence: int, radius: Optional[int] = 0, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa peaks`: "i\\tlabel\\tparent\\tweight" per subject of the DB file — its abundance-peak label and parent at
+    max_divergence and its weight at `radius` (smafa_db_self_peaks) — to out_fd."""
+    check(lib().smafa_peaks(os.fsencode(db_path), _opt(max_divergence), _opt(radius), out_fd, device))
 
 
 def component_levels(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:

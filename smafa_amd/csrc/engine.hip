@@ -22,6 +22,7 @@
 #include "components.hip.h"
 #include "levels.hip.h"
 #include "density.hip.h"
+#include "peaks.hip.h"
 
 namespace smafa {
 
@@ -207,15 +208,19 @@ struct smafa_db {
         uint32_t blocks = 0, rescans = 0;
         // density (density.hip.h): parent holds parent[], degree[] and attach[], 4 B x 3 per subject, live for one call
         DevBuf kept;   // the kept pair list: the rows count_keep_kernel kept, for the one link launch of a one-join call
-        DevBuf ctl;    // two uint64: the kept total, and "some row is core"
+        DevBuf ctl;    // two uint64: the kept total, and "some row is core"; peaks: four — the kept total, unused, the crown, and
+                       // (its low word) the jump rounds' "changed"
         double count_ms = 0;  // density: init + count/keep passes
         uint32_t joins = 0;   // density: how often the store was joined by the last call (0: no scan, 1 or 2)
         bool kept_stuck = false;  // density: growing the kept list failed in this call; it is not tried again
+        // peaks (peaks.hip.h): parent holds best[] (8 B per subject) and weight[] (4 B) behind it, live for one call; kept, ctl,
+        // count_ms (init + weigh/keep passes), link_ms (the climb), flatten_ms (settle + jump rounds) and joins as for density
+        uint32_t jump_rounds = 0;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
     uint64_t join_scratch_max = 1ull << 27;  // rows the block's scratch list may grow to (1.5 GB) before the block is halved (SMAFA_JOIN_SCRATCH_MAX)
-    uint64_t density_keep_max = 1ull << 27;  // rows the density call's kept pair list may grow to; 0: never kept, the store is joined
+    uint64_t density_keep_max = 1ull << 27;  // rows the kept pair list (density and peaks calls) may grow to; 0: never kept, the store is joined
                                              // twice (SMAFA_DENSITY_KEEP_MAX; default: the value of join_scratch_max)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
@@ -1452,6 +1457,13 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 // pair to J.kept while that has room; the kept total then decides: every pair is in J.kept — link_cores_kernel runs ONCE
 // over it (one join); else the store is joined a second time with link_cores_kernel reading each piece's raw list.  No
 // core row at all: no link.  min_pts <= 1 without degrees: nothing to count, the one join links directly, as components.
+// A fifth consumer, pk != nullptr (smafa_db_self_peaks_launch; peaks.hip.h): d_labels is n labels, d_count one counter,
+// J.parent holds best[] and weight[].  The join runs at max_div with weigh_keep_kernel per piece (the exactly-once rule),
+// which raises both weights of every kept pair within the radius and moves every kept pair to J.kept while that has room;
+// the kept total then decides as for density: climb_kernel ONCE over J.kept, or the store joined a second time with
+// climb_kernel reading each piece's raw list; no pair at all: no climb.  settle_kernel writes parents, weights and the
+// peak count, and jump_kernel rounds flatten the labels.  max_div >= seq_len: the join, if any, runs at the radius and only
+// counts (nothing is kept or climbed), and crown_kernel finds the one peak.
 static bool join_inverse_current(const smafa_db *db) {
     const auto &j = db->join;
     return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
@@ -1460,6 +1472,12 @@ static bool join_inverse_current(const smafa_db *db) {
 struct DensityCall {
     uint32_t min_pts;     // >= 1
     uint32_t *d_degrees;  // device buffer of n degrees, or nullptr
+};
+
+struct PeaksCall {
+    uint32_t radius;      // <= max_div
+    uint32_t *d_parents;  // device buffers of n entries, or nullptr
+    uint32_t *d_weights;
 };
 
 // room in J.kept for `rows` rows, at most density_keep_max of them; the first `live` rows are carried over
@@ -1491,21 +1509,26 @@ static int grow_kept(smafa_db *db, uint64_t rows, uint64_t live) {
 }
 
 static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count,
-                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0, const DensityCall *dn = nullptr) {
+                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0, const DensityCall *dn = nullptr,
+                     const PeaksCall *pk = nullptr) {
     auto &J = db->join;
-    const bool linking = d_labels != nullptr, levelled = n_levels != 0, density = dn != nullptr;
+    const bool linking = d_labels != nullptr, levelled = n_levels != 0, density = dn != nullptr, peaks = pk != nullptr;
     // levels: the union-finds that are scanned for, and the one bound the join runs at
     const uint32_t E = levelled ? (uint32_t)std::min<uint64_t>(n_levels, std::max<uint32_t>(db->L, 1u)) : 0u;
-    const uint32_t scan_div = levelled ? E - 1u : max_div;
+    // peaks: at a bound no two rows can exceed the pairs are needed for the weights alone — the join runs at the radius
+    const bool crowned = peaks && max_div >= db->L;
+    const uint32_t scan_div = levelled ? E - 1u : crowned ? pk->radius : max_div;
     // density: which consumer a piece's list goes to — 1: count_keep_kernel, 2: link_cores_kernel (0: not a density call)
     int dn_stage = !density ? 0 : (dn->min_pts > 1u || dn->d_degrees) ? 1 : 2;
+    // peaks: 1: weigh_keep_kernel, 2: climb_kernel (0: not a peaks call)
+    int pk_stage = peaks ? 1 : 0;
     db->call_kernels.clear();
     db->call_ms = 0.f;
     db->call_launches = db->call_scans = 0;
     db->last_launches = 0;
     db->timed = false;
     J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = 0.0;
-    J.blocks = J.rescans = J.joins = 0;
+    J.blocks = J.rescans = J.joins = J.jump_rounds = 0;
     J.kept_stuck = false;
     int rc = use_device(db);
     if (rc) return rc;
@@ -1514,7 +1537,7 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     if (db->n < (linking ? 1u : 2u)) return SMAFA_OK;
     // components of one row, or at a bound no two rows can exceed: nothing to scan (the second would list all n^2 pairs to
     // learn "one component")
-    const bool no_scans = linking && (db->n < 2 || (!levelled && max_div >= db->L));
+    const bool no_scans = linking && (db->n < 2 || (!levelled && (peaks ? scan_div : max_div) >= db->L));
     if (!no_scans) {
         rc = maybe_resort(db);  // once, in front: positions are final for the whole join
         if (rc) return rc;
@@ -1527,11 +1550,19 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     const uint32_t n = (uint32_t)db->n;
     bool inverted = false;
     if (linking) {  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
-        rc = J.parent.ensure((size_t)n * (levelled ? E : density ? 3u : 1u) * sizeof(uint32_t));
+        rc = J.parent.ensure((size_t)n * (levelled ? E : density || peaks ? 3u : 1u) * sizeof(uint32_t));
         if (!rc && density) rc = J.ctl.ensure(2 * sizeof(unsigned long long));
+        if (!rc && peaks) rc = J.ctl.ensure(4 * sizeof(unsigned long long));
         if (rc) return rc;
         HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (density) {  // parent[] | degree[] | attach[]; every row within the bound of every other: degrees n - 1, one set
+        if (peaks) {  // best[] | weight[]; every row within the radius of every other: weights n
+            HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 4 * sizeof(unsigned long long), db->stream));
+            hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
+                               J.parent.as<unsigned long long>(), J.parent.as<uint32_t>() + 2 * (size_t)n, n,
+                               scan_div >= db->L ? n : 1u, 0u);
+            HIP_TRY(hipGetLastError());
+            db->call_launches++;
+        } else if (density) {  // parent[] | degree[] | attach[]; every row within the bound of every other: degrees n - 1, one set
             const bool all_near = max_div >= db->L;
             HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
             hipLaunchKernelGGL(smafa_dn::init_density_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
@@ -1552,7 +1583,7 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
         }
         HIP_TRY(hipEventRecord(J.ev[3], db->stream));
     }
-    if ((!linking || (dn_stage == 1 && !no_scans)) && !join_inverse_current(db)) {
+    if ((!linking || ((dn_stage == 1 || peaks) && !no_scans)) && !join_inverse_current(db)) {
         J.valid = false;
         rc = J.pos_of.ensure((size_t)n * sizeof(uint32_t));
         if (rc) return rc;
@@ -1572,8 +1603,10 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     auto take_filter_time = [&]() {  // the filter / link pass of the piece before: finished by the time a later wait returns
         float ms = 0.f;
         if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) {
-            (!linking ? J.filter_ms : dn_stage == 1 ? J.count_ms : J.link_ms) += ms;
-            if (linking)
+            (!linking ? J.filter_ms : dn_stage == 1 || pk_stage == 1 ? J.count_ms : J.link_ms) += ms;
+            if (peaks)
+                log_line(3, "peaks: %s, %.3f ms", linked ? "a piece's rows climbed" : counted ? "a piece's rows weighed" : "weight[] initialised", ms);
+            else if (linking)
                 log_line(3, "%s: parent[] %s, %.3f ms", density ? "density" : levelled ? "levels" : "components",
                          linked ? "linked with a piece's rows" : counted ? "untouched, a piece's rows counted" : "initialised", ms);
         }
@@ -1582,7 +1615,10 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
     // density: the three arrays of J.parent
     uint32_t *const parent = density ? J.parent.as<uint32_t>() : nullptr, *const degree = density ? parent + n : nullptr;
     uint32_t *const attach = density ? parent + 2 * (size_t)n : nullptr;
-    unsigned long long kept_seen = 0;  // density: the kept total as of the pieces before the one just scanned
+    // peaks: the two arrays of J.parent, the 8-byte one first
+    unsigned long long *const best = peaks ? J.parent.as<unsigned long long>() : nullptr;
+    uint32_t *const weight = peaks ? J.parent.as<uint32_t>() + 2 * (size_t)n : nullptr;
+    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned
     const uint64_t span_rows = db->join_block * db->join_stride;
     auto join_pass = [&]() -> int {  // the whole join, every piece's list to the consumer of this call (and stage)
         uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
@@ -1617,7 +1653,7 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
                     if (rc) return rc;
                     unsigned long long count = 0;
                     HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-                    if (dn_stage == 1)  // (every count/keep pass in front of this scan has ended with it)
+                    if (dn_stage == 1 || (pk_stage == 1 && !crowned))  // (every count/keep pass in front of this scan has ended with it)
                         HIP_TRY(hipMemcpyAsync(&kept_seen, J.ctl.p, sizeof kept_seen, hipMemcpyDeviceToHost, db->stream));
                     HIP_TRY(hipStreamSynchronize(db->stream));
                     take_filter_time();
@@ -1647,7 +1683,32 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
                                          "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
                     }
                     const dim3 list_grid((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256));
-                    if (count && dn_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
+                    if (count && pk_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
+                        // the kept list as the density call grows it; at a crowned bound nothing is kept
+                        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
+                        if (!crowned && !J.kept_stuck) {
+                            rc = grow_kept(db, kept_seen + count, std::min<uint64_t>(kept_seen, have));
+                            if (rc) return rc;
+                        }
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_pk::weigh_keep_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), weight, pk->radius, J.kept.as<smafa_hit>(),
+                                           crowned ? 0ull
+                                                   : (unsigned long long)std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max),
+                                           J.ctl.as<unsigned long long>());
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = counted = true;
+                        db->call_launches++;
+                    } else if (count && pk_stage == 2) {
+                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+                        hipLaunchKernelGGL(smafa_pk::climb_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
+                                           (uint32_t)p0, S, R, db->d_order, weight, best);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+                        filter_pending = linked = true;
+                        db->call_launches++;
+                    } else if (count && dn_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
                         // room for whatever this piece keeps on top of the rows kept so far, while the knob allows it
                         const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
                         if (!J.kept_stuck) {
@@ -1733,6 +1794,85 @@ static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t
             rc = join_pass();
             if (rc) return rc;
         }
+    }
+    if (peaks) {  // every weight is final: the rows' own keys, then the climb (kept list, second join, or none), settle, jump
+        unsigned long long kept_total = 0;
+        HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        take_filter_time();
+        pk_stage = 2;
+        bool crown_ran = false, jumped = false;
+        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
+        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+        if (crowned) {
+            hipLaunchKernelGGL(smafa_pk::crown_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, weight, n,
+                               J.ctl.as<unsigned long long>() + 2);
+            crown_ran = true;
+        } else {
+            hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, best, weight, n, 0u, 1u);
+        }
+        HIP_TRY(hipGetLastError());
+        db->call_launches++;
+        bool second_join = false;
+        if (!crowned && kept_total && kept_total <= have) {
+            hipLaunchKernelGGL(smafa_pk::climb_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (kept_total + 255) / 256)), dim3(256), 0,
+                               db->stream, J.kept.as<smafa_hit>(), kept_total, 0u, 1u, 1u, (const uint32_t *)nullptr, weight, best);
+            HIP_TRY(hipGetLastError());
+            linked = true;
+            db->call_launches++;
+        } else if (!crowned && kept_total) {
+            second_join = true;
+        }
+        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+        filter_pending = true;
+        if (second_join) {
+            log_line(3, "peaks: %llu pairs, the kept list holds %llu: joining once more to climb", kept_total, (unsigned long long)have);
+            rc = join_pass();
+            if (rc) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        take_filter_time();
+        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+        hipLaunchKernelGGL(smafa_pk::settle_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, best, weight, n,
+                           crowned ? J.ctl.as<unsigned long long>() + 2 : (const unsigned long long *)nullptr, d_labels, pk->d_parents,
+                           pk->d_weights, d_count);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+        db->call_launches++;
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms = ms;
+        // pointer doubling until a round changes nothing; without a climb every label is its own row or the crown: flat already
+        for (uint32_t changed = linked ? 1u : 0u; changed;) {
+            if (J.jump_rounds == 33u) return set_error(SMAFA_ERR_DEVICE, "peaks: parent[] is no forest (33 jump rounds did not flatten it)");
+            uint32_t *const d_changed = reinterpret_cast<uint32_t *>(J.ctl.as<unsigned long long>() + 3);
+            HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), db->stream));
+            HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+            hipLaunchKernelGGL(smafa_pk::jump_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, d_labels, n, d_changed);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+            HIP_TRY(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, db->stream));
+            HIP_TRY(hipStreamSynchronize(db->stream));
+            if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms += ms;
+            J.jump_rounds++;
+            db->call_launches++;
+            jumped = true;
+        }
+        db->call_ms += (float)(J.rec_ms + J.count_ms + J.link_ms + J.flatten_ms);
+        db->call_timed = true;  // (scan_range cleared it)
+        if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+        if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
+        note_call_kernel(db, "smafa_pk::init_peaks_kernel");
+        if (counted) note_call_kernel(db, "smafa_pk::weigh_keep_kernel");
+        if (linked) note_call_kernel(db, "smafa_pk::climb_kernel");
+        if (crown_ran) note_call_kernel(db, "smafa_pk::crown_kernel");
+        note_call_kernel(db, "smafa_pk::settle_kernel");
+        if (jumped) note_call_kernel(db, "smafa_pk::jump_kernel");
+        log_line(2, "peaks of %u rows at bound %u, radius %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
+                 "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s", n, max_div, pk->radius, J.blocks + J.rescans,
+                 J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
+                 J.jump_rounds == 1 ? "" : "s");
+        return SMAFA_OK;
     }
     if (linking) {  // the kernel boundary makes every hook visible: labels[i] = root(i), representatives counted
         HIP_TRY(hipStreamSynchronize(db->stream));
@@ -2980,6 +3120,58 @@ int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_density");
+}
+
+int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, void *d_labels, void *d_parents, void *d_weights,
+                               void *d_n_peaks) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL handle");
+    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL labels");
+    if (!d_n_peaks) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL n_peaks");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: peaks need a bound (max_div)");
+    if (radius != SMAFA_NONE && radius > max_div)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: radius %u is larger than max_div %u", radius, max_div);
+    const PeaksCall pk = {radius == SMAFA_NONE ? max_div : radius, (uint32_t *)d_parents, (uint32_t *)d_weights};
+    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_peaks, (uint32_t *)d_labels, 0, nullptr, &pk);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_peaks_launch");
+}
+
+int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *labels, uint32_t *parents, uint32_t *weights,
+                        uint64_t cap, uint64_t *n_peaks) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL handle");
+    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL labels");
+    if (!n_peaks) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL n_peaks");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: peaks need a bound (max_div)");
+    if (radius != SMAFA_NONE && radius > max_div)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: radius %u is larger than max_div %u", radius, max_div);
+    if (cap < db->n)  // (nothing is written, the count included)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: labels holds %llu entries, the store has %llu subjects",
+                         (unsigned long long)cap, (unsigned long long)db->n);
+    *n_peaks = 0;
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // the labels, and the parents and weights behind them, on their way to the caller: 4 B x 3 per subject
+    rc = J.out.ensure(std::max<uint64_t>(n, 1) * 3u * sizeof(uint32_t));
+    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
+    if (rc) return rc;
+    const PeaksCall pk = {radius == SMAFA_NONE ? max_div : radius, parents ? J.out.as<uint32_t>() + n : nullptr,
+                          weights ? J.out.as<uint32_t>() + 2 * n : nullptr};
+    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), 0, nullptr, &pk);
+    if (rc) return rc;
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    if (n && parents) HIP_TRY(hipMemcpyAsync(parents, J.out.as<uint32_t>() + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    if (n && weights) HIP_TRY(hipMemcpyAsync(weights, J.out.as<uint32_t>() + 2 * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    *n_peaks = count;
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    if (J.kept.cap > (512ull << 20)) J.kept.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_peaks");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -777,6 +777,52 @@ int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts
     return smafa::exception_code("smafa_density");
 }
 
+// ------------------------------------------------------------------------------------ peaks
+// The abundance-peak label, the parent and the weight of every subject of a DB file (smafa_db_self_peaks), printed
+// "{i}\t{label}\t{parent}\t{weight}\n" in subject order.
+int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_peaks: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_peaks: a bound (max_divergence) is needed");
+    if (radius != SMAFA_NONE && radius > max_divergence)
+        return set_error(SMAFA_ERR_INVALID, "smafa_peaks: radius %u is larger than max_divergence %u", radius, max_divergence);
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    const size_t n = (size_t)info.n_subjects;
+    std::vector<uint32_t> labels(n), parents(n), weights(n);
+    uint64_t n_peaks = 0;
+    rc = smafa_db_self_peaks(store.db, max_divergence, radius, labels.data(), parents.data(), weights.data(), n, &n_peaks);
+    if (rc) return rc;
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // rows per write
+    for (size_t b0 = 0; b0 < n; b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(n, b0 + block); i < e; i++) {
+            append_u32(text, (uint32_t)i);
+            text.push_back('\t');
+            append_u32(text, labels[i]);
+            text.push_back('\t');
+            append_u32(text, parents[i]);
+            text.push_back('\t');
+            append_u32(text, weights[i]);
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu peaks among %llu sequences within %u, weighed within %u, took %llu seconds", (unsigned long long)n_peaks,
+             (unsigned long long)n, max_divergence, radius == SMAFA_NONE ? max_divergence : radius,
+             (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_peaks");
+}
+
 // ------------------------------------------------------------------------------------ cluster
 //
 // The reference handles one record at a time: skip exact duplicates, scan the record against the

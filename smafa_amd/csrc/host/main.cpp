@@ -10,6 +10,8 @@
 //           every subject; --levels: at every bound 0 .. INT)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
+//   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
+//           and the weight of every subject)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -53,7 +55,12 @@ static int usage(const char *msg, FILE *to = stderr) {
             "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
-            "        core sequence number of its cluster, for a non-core sequence that of its smallest core neighbour, -1 for noise)\n");
+            "        core sequence number of its cluster, for a non-core sequence that of its smallest core neighbour, -1 for noise)\n"
+            "peaks   -d, --database <FILE>  --max-divergence <INT>  [--radius <INT>]  [--device <N>]  (not in the reference: abundance-peak\n"
+            "        clusters of the database's own sequences, one \"i<TAB>label<TAB>parent<TAB>weight\" line per sequence; weight = 1 +\n"
+            "        the number of other sequences within the radius (default 0: the number of exact copies); parent = the heaviest\n"
+            "        sequence within the bound, ties to the smaller number, the sequence itself if none outranks it (a peak);\n"
+            "        label = the peak reached by following the parents)\n");
     return 2;
 }
 
@@ -93,7 +100,7 @@ int main(int argc, char **argv) {
     const bool is_cluster = cmd == "cluster";
     const char *input = nullptr, *database = nullptr, *query = nullptr;
     std::vector<const char *> count_paths;
-    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0;
+    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0;
     bool have_min_pts = false;
     bool have_max_div = false, packed = false, no_gpu = false, levels = false;
     std::vector<int> devices;  // query: more than one handle
@@ -131,6 +138,8 @@ int main(int argc, char **argv) {
         } else if (a == "--min-pts" && cmd == "density") {
             if (!parse_u32(value(), &min_pts)) return usage("--min-pts needs an unsigned integer");
             have_min_pts = true;
+        } else if (a == "--radius" && cmd == "peaks") {
+            if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
         } else if (a == "--levels" && cmd == "components") {
             levels = true;
         } else if (a == "--no-gpu") {
@@ -202,6 +211,10 @@ int main(int argc, char **argv) {
         if (!have_max_div) return usage("density needs --max-divergence");
         if (!have_min_pts) return usage("density needs --min-pts");
         rc = smafa_density(database, max_div, min_pts, 1, (int)device);
+    } else if (cmd == "peaks") {
+        if (!database) return usage("peaks needs --database");
+        if (!have_max_div) return usage("peaks needs --max-divergence");
+        rc = smafa_peaks(database, max_div, radius, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);
