@@ -44,6 +44,27 @@ inline uint32_t query_block_size(uint32_t override, uint32_t n_cu, uint32_t n_wg
     return qb ? qb : 1u;
 }
 
+// The self-join's piece-size rule (self_join.hip.h: join_pass): what follows a scan of `rows` store rows that found `count` rows
+// for a scratch list of `capacity` rows which may grow to `ceiling` rows (SMAFA_JOIN_SCRATCH_MAX).  A count the list held is
+// taken, and a piece size reduced earlier doubles back towards `block` (SMAFA_JOIN_BLOCK) once a count falls under a quarter of
+// the ceiling.  A count the list did not hold is exact all the same: under the ceiling the list grows to it and the same rows are
+// scanned again; above it the piece is cut in half, to whole 64-record chunks; 64 rows or fewer cannot be cut and the call fails.
+enum PieceVerdict { kPieceTake, kPieceGrow, kPieceHalve, kPieceFail };
+struct PieceRule {
+    PieceVerdict verdict;
+    uint64_t piece;  // rows per scan from here on
+};
+inline PieceRule join_piece_rule(uint64_t count, uint64_t capacity, uint64_t ceiling, uint64_t rows, uint64_t piece, uint64_t block) {
+    if (count <= capacity) {
+        const uint64_t twice = piece * 2 < block ? piece * 2 : block;
+        return {kPieceTake, piece < block && count * 4 < ceiling ? twice : piece};
+    }
+    if (count <= ceiling) return {kPieceGrow, piece};
+    if (rows <= 64) return {kPieceFail, piece};
+    const uint64_t half = (rows / 2 + 63) / 64 * 64;
+    return {kPieceHalve, half > 64 ? half : 64};
+}
+
 // Bring the HIP runtime and the device context up (a few hundred ms the first time in a process).  The drivers call it
 // on a helper thread while they read and decode their input; failures are ignored here — the first real call reports.
 void warm_device(int device);

@@ -1429,509 +1429,7 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 }
 
 // ---------------------------------------------------------------------------------------------
-// The self-join (smafa_db_self_launch; kernels: join.hip.h): every unordered pair of the store's subjects within max_div.
-// The store is walked in SPANS of join_stride x join_block consecutive positions.  A span's rows become query records on
-// the device (store_records_kernel), dealt round-robin into join_stride BLOCKS: block b holds the span's positions b,
-// b + S, b + 2S, ...  Per block the fixed-bound scan runs its records against the wave tiles from the span's first one to the
-// end of the store — tiles in front of the span could only repeat pairs an earlier span has found — into the handle's
-// scratch list, and join_filter_kernel moves the rows with position(query) < position(subject) to the caller's list.
-// Why interleaved: the store is sorted by filter bits, so a block of CONSECUTIVE positions is 65 536 rows that all pass the
-// zone level on the same few tiles and fail it on the rest — the surviving work of a launch sits in a few workgroups
-// (measured: profiles/r07_self_join.txt, stride 1 against 16).  Rows a whole span apart differ in all but its few leading bits.
-// The host waits for each block's scan to learn its row count: a piece that overflowed the scratch list is scanned again with
-// the list grown to that count (exact at any capacity), or cut in half once the list would pass join_scratch_max rows; the
-// reduced piece size is kept until a piece's count falls under a quarter of that ceiling.
-// The driver has two consumers of a finished piece's list.  d_labels == nullptr: the join as above.  d_labels != nullptr
-// (smafa_db_self_components_launch): link_rows_kernel unites the two subjects of every row in J.parent (components.hip.h)
-// — no pos_of[], no filter, no rows for the caller — and after the last piece flatten_labels_kernel writes labels[i] = the
-// smallest subject number of i's component and counts the representatives into *d_count.  Spans, records, scans, the
-// wait for each count, the re-scan of an overflowing piece (a truncated list is never linked), the halving and the
-// SMAFA_ERR_NOMEM case are the same code for both.
-// A third consumer, n_levels != 0 (smafa_db_self_levels_launch; levels.hip.h): d_labels is n_levels x n, d_count n_levels
-// counters, J.parent one union-find per SCANNED level (E = min(max_div, L - 1) + 1 of them; the levels above are all zeros
-// and need no scan), the join runs once at bound E - 1 and hook_levels_kernel unites the subjects of a row at every level
-// from its distance upwards; flatten_levels_kernel writes every level in one launch.  Everything between is the shared path.
-// A fourth consumer, dn != nullptr (smafa_db_self_density_launch; density.hip.h): d_labels is n labels, d_count three
-// counters, J.parent holds parent[], degree[] and attach[].  The join runs at max_div with count_keep_kernel per piece
-// (the exactly-once rule, so pos_of[] as for the plain join), which raises both degrees of every kept pair and moves the
-// pair to J.kept while that has room; the kept total then decides: every pair is in J.kept — link_cores_kernel runs ONCE
-// over it (one join); else the store is joined a second time with link_cores_kernel reading each piece's raw list.  No
-// core row at all: no link.  min_pts <= 1 without degrees: nothing to count, the one join links directly, as components.
-// A fifth consumer, pk != nullptr (smafa_db_self_peaks_launch; peaks.hip.h): d_labels is n labels, d_count one counter,
-// J.parent holds best[] and weight[].  The join runs at max_div with weigh_keep_kernel per piece (the exactly-once rule),
-// which raises both weights of every kept pair within the radius and moves every kept pair to J.kept while that has room;
-// the kept total then decides as for density: climb_kernel ONCE over J.kept, or the store joined a second time with
-// climb_kernel reading each piece's raw list; no pair at all: no climb.  settle_kernel writes parents, weights and the
-// peak count, and jump_kernel rounds flatten the labels.  max_div >= seq_len: the join, if any, runs at the radius and only
-// counts (nothing is kept or climbed), and crown_kernel finds the one peak.
-static bool join_inverse_current(const smafa_db *db) {
-    const auto &j = db->join;
-    return j.valid && j.generation == db->generation && j.n == db->n && j.resorts == db->resorts;
-}
-
-struct DensityCall {
-    uint32_t min_pts;     // >= 1
-    uint32_t *d_degrees;  // device buffer of n degrees, or nullptr
-};
-
-struct PeaksCall {
-    uint32_t radius;      // <= max_div
-    uint32_t *d_parents;  // device buffers of n entries, or nullptr
-    uint32_t *d_weights;
-};
-
-// room in J.kept for `rows` rows, at most density_keep_max of them; the first `live` rows are carried over
-static int grow_kept(smafa_db *db, uint64_t rows, uint64_t live) {
-    DevBuf &K = db->join.kept;
-    rows = std::min<uint64_t>(rows, db->density_keep_max);
-    if (rows * sizeof(smafa_hit) <= K.cap) return SMAFA_OK;
-    const uint64_t want = std::min<uint64_t>(db->density_keep_max, std::max<uint64_t>(rows, K.cap / sizeof(smafa_hit) * 2));
-    DevBuf bigger;  // (a bare hipMalloc: a failure here is no failure of the call and leaves no text in smafa_last_error())
-    if (hipMalloc(&bigger.p, want * sizeof(smafa_hit)) == hipSuccess) bigger.cap = want * sizeof(smafa_hit);
-    if (!bigger.p) {
-        // no room for a larger list: the one there is stays as it is and overflows — counted, not stored — and the call
-        // falls back to the second join, which needs no list and gives the same bytes
-        (void)hipGetLastError();
-        db->join.kept_stuck = true;
-        log_line(2, "density: no memory for a kept pair list of %llu rows; the store will be joined twice", (unsigned long long)want);
-        return SMAFA_OK;
-    }
-    hipError_t e = hipSuccess;
-    if (live) e = hipMemcpyAsync(bigger.p, K.p, live * sizeof(smafa_hit), hipMemcpyDeviceToDevice, db->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
-    if (e != hipSuccess) {
-        bigger.release();
-        return set_error(SMAFA_ERR_DEVICE, "density: moving the kept pair list failed: %s", hipGetErrorString(e));
-    }
-    K.release();
-    K = bigger;
-    return SMAFA_OK;
-}
-
-static int self_join(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count,
-                     uint32_t *d_labels = nullptr, uint32_t n_levels = 0, const DensityCall *dn = nullptr,
-                     const PeaksCall *pk = nullptr) {
-    auto &J = db->join;
-    const bool linking = d_labels != nullptr, levelled = n_levels != 0, density = dn != nullptr, peaks = pk != nullptr;
-    // levels: the union-finds that are scanned for, and the one bound the join runs at
-    const uint32_t E = levelled ? (uint32_t)std::min<uint64_t>(n_levels, std::max<uint32_t>(db->L, 1u)) : 0u;
-    // peaks: at a bound no two rows can exceed the pairs are needed for the weights alone — the join runs at the radius
-    const bool crowned = peaks && max_div >= db->L;
-    const uint32_t scan_div = levelled ? E - 1u : crowned ? pk->radius : max_div;
-    // density: which consumer a piece's list goes to — 1: count_keep_kernel, 2: link_cores_kernel (0: not a density call)
-    int dn_stage = !density ? 0 : (dn->min_pts > 1u || dn->d_degrees) ? 1 : 2;
-    // peaks: 1: weigh_keep_kernel, 2: climb_kernel (0: not a peaks call)
-    int pk_stage = peaks ? 1 : 0;
-    db->call_kernels.clear();
-    db->call_ms = 0.f;
-    db->call_launches = db->call_scans = 0;
-    db->last_launches = 0;
-    db->timed = false;
-    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = 0.0;
-    J.blocks = J.rescans = J.joins = J.jump_rounds = 0;
-    J.kept_stuck = false;
-    int rc = use_device(db);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_count, 0, (levelled ? (size_t)n_levels : density ? 3u : 1u) * sizeof(unsigned long long), db->stream));
-    db->call_timed = true;
-    if (db->n < (linking ? 1u : 2u)) return SMAFA_OK;
-    // components of one row, or at a bound no two rows can exceed: nothing to scan (the second would list all n^2 pairs to
-    // learn "one component")
-    const bool no_scans = linking && (db->n < 2 || (!levelled && (peaks ? scan_div : max_div) >= db->L));
-    if (!no_scans) {
-        rc = maybe_resort(db);  // once, in front: positions are final for the whole join
-        if (rc) return rc;
-    }
-    for (hipEvent_t &e : J.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    rc = db->count.ensure(sizeof(unsigned long long));
-    if (!rc && !no_scans && db->hits_cap() < (1ull << 22)) rc = db->hits.ensure((1ull << 22) * sizeof(smafa_hit));
-    if (rc) return rc;
-    const uint32_t n = (uint32_t)db->n;
-    bool inverted = false;
-    if (linking) {  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
-        rc = J.parent.ensure((size_t)n * (levelled ? E : density || peaks ? 3u : 1u) * sizeof(uint32_t));
-        if (!rc && density) rc = J.ctl.ensure(2 * sizeof(unsigned long long));
-        if (!rc && peaks) rc = J.ctl.ensure(4 * sizeof(unsigned long long));
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (peaks) {  // best[] | weight[]; every row within the radius of every other: weights n
-            HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 4 * sizeof(unsigned long long), db->stream));
-            hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
-                               J.parent.as<unsigned long long>(), J.parent.as<uint32_t>() + 2 * (size_t)n, n,
-                               scan_div >= db->L ? n : 1u, 0u);
-            HIP_TRY(hipGetLastError());
-            db->call_launches++;
-        } else if (density) {  // parent[] | degree[] | attach[]; every row within the bound of every other: degrees n - 1, one set
-            const bool all_near = max_div >= db->L;
-            HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
-            hipLaunchKernelGGL(smafa_dn::init_density_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
-                               J.parent.as<uint32_t>() + n, J.parent.as<uint32_t>(), J.parent.as<uint32_t>() + 2 * (size_t)n, n,
-                               all_near ? n - 1u : 0u, all_near ? 1u : 0u);
-            HIP_TRY(hipGetLastError());
-            db->call_launches++;
-        } else if (levelled) {
-            hipLaunchKernelGGL(smafa_lv::init_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, E);
-            HIP_TRY(hipGetLastError());
-            db->call_launches++;
-        } else if (max_div >= db->L) {
-            HIP_TRY(hipMemsetAsync(J.parent.p, 0, (size_t)n * sizeof(uint32_t), db->stream));
-        } else {
-            hipLaunchKernelGGL(smafa_cc::init_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n);
-            HIP_TRY(hipGetLastError());
-            db->call_launches++;
-        }
-        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-    }
-    if ((!linking || ((dn_stage == 1 || peaks) && !no_scans)) && !join_inverse_current(db)) {
-        J.valid = false;
-        rc = J.pos_of.ensure((size_t)n * sizeof(uint32_t));
-        if (rc) return rc;
-        hipLaunchKernelGGL(smafa_join::inverse_order_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, db->d_order, n,
-                           J.pos_of.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        J.generation = db->generation;
-        J.n = db->n;
-        J.resorts = db->resorts;
-        J.valid = true;
-        inverted = true;
-        db->call_launches++;
-    }
-    smafa_qset *qs = &db->join_q;
-    qs->db = db;
-    bool filtered = false, linked = false, counted = false, filter_pending = linking;  // (linking: the initialisation of parent[] is pending)
-    auto take_filter_time = [&]() {  // the filter / link pass of the piece before: finished by the time a later wait returns
-        float ms = 0.f;
-        if (filter_pending && hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) {
-            (!linking ? J.filter_ms : dn_stage == 1 || pk_stage == 1 ? J.count_ms : J.link_ms) += ms;
-            if (peaks)
-                log_line(3, "peaks: %s, %.3f ms", linked ? "a piece's rows climbed" : counted ? "a piece's rows weighed" : "weight[] initialised", ms);
-            else if (linking)
-                log_line(3, "%s: parent[] %s, %.3f ms", density ? "density" : levelled ? "levels" : "components",
-                         linked ? "linked with a piece's rows" : counted ? "untouched, a piece's rows counted" : "initialised", ms);
-        }
-        filter_pending = false;
-    };
-    // density: the three arrays of J.parent
-    uint32_t *const parent = density ? J.parent.as<uint32_t>() : nullptr, *const degree = density ? parent + n : nullptr;
-    uint32_t *const attach = density ? parent + 2 * (size_t)n : nullptr;
-    // peaks: the two arrays of J.parent, the 8-byte one first
-    unsigned long long *const best = peaks ? J.parent.as<unsigned long long>() : nullptr;
-    uint32_t *const weight = peaks ? J.parent.as<uint32_t>() + 2 * (size_t)n : nullptr;
-    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned
-    const uint64_t span_rows = db->join_block * db->join_stride;
-    auto join_pass = [&]() -> int {  // the whole join, every piece's list to the consumer of this call (and stage)
-        uint64_t piece = db->join_block;  // rows per scan; halved where a piece's rows would pass the scratch ceiling
-        J.joins++;
-        for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
-            const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
-            const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
-            const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
-            // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
-            const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
-            qs->nq = (uint64_t)S * R;
-            qs->serial = g_qset_serial.fetch_add(1);
-            int rc = qs->qrec.ensure(padded * db->QS * sizeof(uint32_t));
-            if (!rc) rc = qs->thr.ensure(padded * sizeof(uint32_t));
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(J.ev[0], db->stream));
-            HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
-            const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
-            hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0, db->stream,
-                               reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0, (uint32_t)p1, S, R,
-                               qs->qrec.as<uint32_t>());
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(J.ev[1], db->stream));
-            db->call_launches++;
-            bool rec_timed = false;
-            for (uint32_t b = 0; b < S; b++) {
-                const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
-                for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
-                    const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
-                    rc = scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
-                                    db->count.as<unsigned long long>(), t0);
-                    if (rc) return rc;
-                    unsigned long long count = 0;
-                    HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-                    if (dn_stage == 1 || (pk_stage == 1 && !crowned))  // (every count/keep pass in front of this scan has ended with it)
-                        HIP_TRY(hipMemcpyAsync(&kept_seen, J.ctl.p, sizeof kept_seen, hipMemcpyDeviceToHost, db->stream));
-                    HIP_TRY(hipStreamSynchronize(db->stream));
-                    take_filter_time();
-                    const float before = db->call_ms;
-                    note_call_scan(db);
-                    const double scan_ms = db->call_ms - before;
-                    J.scan_ms += scan_ms;
-                    float ms = 0.f;
-                    if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
-                    rec_timed = true;
-                    log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
-                             (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
-                    if (count > db->hits_cap()) {
-                        J.rescans++;
-                        if (count <= db->join_scratch_max) {  // the count is exact: room for it, and the same piece once more
-                            rc = db->hits.ensure(count * sizeof(smafa_hit));
-                            if (rc) return rc;
-                            continue;
-                        }
-                        if (q1 - q0 > 64) {
-                            piece = std::max<uint64_t>(64, ((q1 - q0) / 2 + 63) / 64 * 64);
-                            continue;
-                        }
-                        // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
-                        return set_error(SMAFA_ERR_NOMEM,
-                                         "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
-                                         "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
-                    }
-                    const dim3 list_grid((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256));
-                    if (count && pk_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
-                        // the kept list as the density call grows it; at a crowned bound nothing is kept
-                        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
-                        if (!crowned && !J.kept_stuck) {
-                            rc = grow_kept(db, kept_seen + count, std::min<uint64_t>(kept_seen, have));
-                            if (rc) return rc;
-                        }
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_pk::weigh_keep_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), weight, pk->radius, J.kept.as<smafa_hit>(),
-                                           crowned ? 0ull
-                                                   : (unsigned long long)std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max),
-                                           J.ctl.as<unsigned long long>());
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = counted = true;
-                        db->call_launches++;
-                    } else if (count && pk_stage == 2) {
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_pk::climb_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, weight, best);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = linked = true;
-                        db->call_launches++;
-                    } else if (count && dn_stage == 1) {  // (count <= capacity here: a truncated list was scanned again above)
-                        // room for whatever this piece keeps on top of the rows kept so far, while the knob allows it
-                        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
-                        if (!J.kept_stuck) {
-                            rc = grow_kept(db, kept_seen + count, std::min<uint64_t>(kept_seen, have));
-                            if (rc) return rc;
-                        }
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_dn::count_keep_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), degree, dn->min_pts, J.kept.as<smafa_hit>(),
-                                           (unsigned long long)std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max),
-                                           J.ctl.as<unsigned long long>());
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = counted = true;
-                        db->call_launches++;
-                    } else if (count && dn_stage == 2) {
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_dn::link_cores_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, degree, dn->min_pts, parent, attach);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = linked = true;
-                        db->call_launches++;
-                    } else if (count && levelled) {
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_lv::hook_levels_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, J.parent.as<uint32_t>(), n, E);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = linked = true;
-                        db->call_launches++;
-                    } else if (count && linking) {
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_cc::link_rows_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, J.parent.as<uint32_t>());
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = linked = true;
-                        db->call_launches++;
-                    } else if (count) {
-                        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-                        hipLaunchKernelGGL(smafa_join::join_filter_kernel, list_grid, dim3(256), 0, db->stream, db->hits.as<smafa_hit>(), count,
-                                           (uint32_t)p0, S, R, db->d_order, J.pos_of.as<uint32_t>(), d_hits, (unsigned long long)cap, d_count);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-                        filter_pending = filtered = true;
-                        db->call_launches++;
-                    }
-                    J.blocks++;
-                    q0 = q1;
-                    if (piece < db->join_block && count * 4 < db->join_scratch_max) piece = std::min<uint64_t>(db->join_block, piece * 2);
-                }
-            }
-            HIP_TRY(hipStreamSynchronize(db->stream));  // the span's records are overwritten next
-            take_filter_time();
-        }
-        return SMAFA_OK;
-    };
-    if (!no_scans) {
-        rc = join_pass();
-        if (rc) return rc;
-    }
-    if (dn_stage == 1 && !no_scans) {  // every degree is final: link from the kept list, or join once more, or not at all
-        unsigned long long ctl[2] = {0, 0};  // the kept total; "some row is core"
-        HIP_TRY(hipMemcpyAsync(ctl, J.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        take_filter_time();
-        dn_stage = 2;
-        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
-        if (ctl[0] == 0 || (dn->min_pts > 1u && !ctl[1])) {
-            // no pair, or no core row: nothing to link, every row keeps the set and the attach[] it was given
-        } else if (ctl[0] <= have) {
-            HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-            hipLaunchKernelGGL(smafa_dn::link_cores_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (ctl[0] + 255) / 256)), dim3(256), 0,
-                               db->stream, J.kept.as<smafa_hit>(), ctl[0], 0u, 1u, 1u, (const uint32_t *)nullptr, degree, dn->min_pts, parent,
-                               attach);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-            filter_pending = linked = true;
-            db->call_launches++;
-        } else {
-            log_line(3, "density: %llu pairs, the kept list holds %llu: joining once more to link", ctl[0], (unsigned long long)have);
-            rc = join_pass();
-            if (rc) return rc;
-        }
-    }
-    if (peaks) {  // every weight is final: the rows' own keys, then the climb (kept list, second join, or none), settle, jump
-        unsigned long long kept_total = 0;
-        HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        take_filter_time();
-        pk_stage = 2;
-        bool crown_ran = false, jumped = false;
-        const uint64_t have = std::min<uint64_t>(J.kept.cap / sizeof(smafa_hit), db->density_keep_max);
-        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (crowned) {
-            hipLaunchKernelGGL(smafa_pk::crown_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, weight, n,
-                               J.ctl.as<unsigned long long>() + 2);
-            crown_ran = true;
-        } else {
-            hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, best, weight, n, 0u, 1u);
-        }
-        HIP_TRY(hipGetLastError());
-        db->call_launches++;
-        bool second_join = false;
-        if (!crowned && kept_total && kept_total <= have) {
-            hipLaunchKernelGGL(smafa_pk::climb_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (kept_total + 255) / 256)), dim3(256), 0,
-                               db->stream, J.kept.as<smafa_hit>(), kept_total, 0u, 1u, 1u, (const uint32_t *)nullptr, weight, best);
-            HIP_TRY(hipGetLastError());
-            linked = true;
-            db->call_launches++;
-        } else if (!crowned && kept_total) {
-            second_join = true;
-        }
-        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-        filter_pending = true;
-        if (second_join) {
-            log_line(3, "peaks: %llu pairs, the kept list holds %llu: joining once more to climb", kept_total, (unsigned long long)have);
-            rc = join_pass();
-            if (rc) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        take_filter_time();
-        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        hipLaunchKernelGGL(smafa_pk::settle_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, best, weight, n,
-                           crowned ? J.ctl.as<unsigned long long>() + 2 : (const unsigned long long *)nullptr, d_labels, pk->d_parents,
-                           pk->d_weights, d_count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-        db->call_launches++;
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms = ms;
-        // pointer doubling until a round changes nothing; without a climb every label is its own row or the crown: flat already
-        for (uint32_t changed = linked ? 1u : 0u; changed;) {
-            if (J.jump_rounds == 33u) return set_error(SMAFA_ERR_DEVICE, "peaks: parent[] is no forest (33 jump rounds did not flatten it)");
-            uint32_t *const d_changed = reinterpret_cast<uint32_t *>(J.ctl.as<unsigned long long>() + 3);
-            HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), db->stream));
-            HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-            hipLaunchKernelGGL(smafa_pk::jump_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, d_labels, n, d_changed);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-            HIP_TRY(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, db->stream));
-            HIP_TRY(hipStreamSynchronize(db->stream));
-            if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms += ms;
-            J.jump_rounds++;
-            db->call_launches++;
-            jumped = true;
-        }
-        db->call_ms += (float)(J.rec_ms + J.count_ms + J.link_ms + J.flatten_ms);
-        db->call_timed = true;  // (scan_range cleared it)
-        if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
-        if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
-        note_call_kernel(db, "smafa_pk::init_peaks_kernel");
-        if (counted) note_call_kernel(db, "smafa_pk::weigh_keep_kernel");
-        if (linked) note_call_kernel(db, "smafa_pk::climb_kernel");
-        if (crown_ran) note_call_kernel(db, "smafa_pk::crown_kernel");
-        note_call_kernel(db, "smafa_pk::settle_kernel");
-        if (jumped) note_call_kernel(db, "smafa_pk::jump_kernel");
-        log_line(2, "peaks of %u rows at bound %u, radius %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
-                 "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s", n, max_div, pk->radius, J.blocks + J.rescans,
-                 J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
-                 J.jump_rounds == 1 ? "" : "s");
-        return SMAFA_OK;
-    }
-    if (linking) {  // the kernel boundary makes every hook visible: labels[i] = root(i), representatives counted
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        take_filter_time();
-        HIP_TRY(hipEventRecord(J.ev[2], db->stream));
-        if (density)
-            hipLaunchKernelGGL(smafa_dn::flatten_density_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream, parent, degree, attach,
-                               n, dn->min_pts, d_labels, dn->d_degrees, d_count);
-        else if (levelled)
-            hipLaunchKernelGGL(smafa_lv::flatten_levels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
-                               J.parent.as<uint32_t>(), n, E, n_levels, d_labels, d_count);
-        else
-            hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, dim3((n + 255u) / 256u), dim3(256), 0, db->stream,
-                               J.parent.as<uint32_t>(), n, d_labels, d_count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(J.ev[3], db->stream));
-        db->call_launches++;
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, J.ev[2], J.ev[3]) == hipSuccess) J.flatten_ms = ms;
-        db->call_ms += (float)(J.rec_ms + J.count_ms + J.link_ms + J.flatten_ms);
-        db->call_timed = true;  // (scan_range cleared it)
-        if (!no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
-        if (density) {
-            if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
-            note_call_kernel(db, "smafa_dn::init_density_kernel");
-            if (counted) note_call_kernel(db, "smafa_dn::count_keep_kernel");
-            if (linked) note_call_kernel(db, "smafa_dn::link_cores_kernel");
-            note_call_kernel(db, "smafa_dn::flatten_density_kernel");
-            log_line(2, "density of %u rows at bound %u, min_pts %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
-                     "count/keep %.3f ms, link %.3f ms, flatten %.3f ms", n, max_div, dn->min_pts, J.blocks + J.rescans, J.rescans, J.joins,
-                     J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms);
-            return SMAFA_OK;
-        }
-        if (levelled) {
-            note_call_kernel(db, "smafa_lv::init_levels_kernel");
-            if (linked) note_call_kernel(db, "smafa_lv::hook_levels_kernel");
-            note_call_kernel(db, "smafa_lv::flatten_levels_kernel");
-            log_line(2, "levels 0..%u of %u rows, joined at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, "
-                     "link %.3f ms, flatten %.3f ms", n_levels - 1u, n, scan_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms,
-                     J.link_ms, J.flatten_ms);
-            return SMAFA_OK;
-        }
-        if (max_div < db->L) note_call_kernel(db, "smafa_cc::init_labels_kernel");
-        if (linked) note_call_kernel(db, "smafa_cc::link_rows_kernel");
-        note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
-        log_line(2, "components of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, link %.3f ms, "
-                 "flatten %.3f ms", n, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms, J.flatten_ms);
-        return SMAFA_OK;
-    }
-    db->call_ms += (float)(J.rec_ms + J.filter_ms);
-    db->call_timed = true;  // (scan_range cleared it)
-    note_call_kernel(db, "smafa_join::store_records_kernel");
-    if (inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
-    if (filtered) note_call_kernel(db, "smafa_join::join_filter_kernel");
-    log_line(2, "self-join of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, filter %.3f ms", n,
-             max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.filter_ms);
-    return SMAFA_OK;
-}
+#include "self_join.hip.h"  // the self-join: its driver and the five calls that consume its pieces
 
 void db_life_stats(const smafa_db *db, double *kernel_ms, uint64_t *launches) {
     *kernel_ms = db ? db->life_ms : 0.0;
@@ -2948,7 +2446,7 @@ int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t 
     if (!d_count) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL count");
     if (!d_hits && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL row buffer with a capacity");
     if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: a self-join needs a bound (max_div)");
-    return self_join(db, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
+    return join_pairs(db, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
 } catch (...) {
     return smafa::exception_code("smafa_db_self_launch");
 }
@@ -2967,7 +2465,7 @@ int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t 
     rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));
     if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
     if (rc) return rc;
-    rc = self_join(db, max_div, J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
+    rc = join_pairs(db, max_div, J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
     if (rc) return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
@@ -3003,7 +2501,7 @@ int smafa_db_self_components_launch(smafa_db *db, uint32_t max_div, void *d_labe
     if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL count");
     if (max_div == SMAFA_NONE)
         return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: components need a bound (max_div)");
-    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_components, (uint32_t *)d_labels);
+    return join_components(db, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
 } catch (...) {
     return smafa::exception_code("smafa_db_self_components_launch");
 }
@@ -3023,7 +2521,7 @@ int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, u
     rc = J.out.ensure(std::max<uint64_t>(db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller: 4 B per subject
     if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
     if (rc) return rc;
-    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>());
+    rc = join_components(db, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
     if (rc) return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
@@ -3041,7 +2539,7 @@ int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, 
     if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL labels");
     if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL count");
     if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: levels need a bound (max_div)");
-    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_components, (uint32_t *)d_labels, max_div + 1u);
+    return join_levels(db, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
 } catch (...) {
     return smafa::exception_code("smafa_db_self_levels_launch");
 }
@@ -3063,7 +2561,7 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
     rc = J.out.ensure(std::max<uint64_t>(T * db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller
     if (!rc) rc = J.cnt.ensure(T * sizeof(unsigned long long));
     if (rc) return rc;
-    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), (uint32_t)T);
+    rc = join_levels(db, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
     if (rc) return rc;
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
     HIP_TRY(hipMemcpyAsync(n_components, J.cnt.p, T * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
@@ -3083,8 +2581,7 @@ int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pt
     if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL labels");
     if (!d_counts) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL counts");
     if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: density needs a bound (max_div)");
-    const DensityCall dn = {std::max<uint32_t>(min_pts, 1u), (uint32_t *)d_degrees};
-    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_counts, (uint32_t *)d_labels, 0, &dn);
+    return join_density(db, max_div, std::max<uint32_t>(min_pts, 1u), (uint32_t *)d_degrees, (uint32_t *)d_labels, (unsigned long long *)d_counts);
 } catch (...) {
     return smafa::exception_code("smafa_db_self_density_launch");
 }
@@ -3107,8 +2604,8 @@ int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint
     rc = J.out.ensure(std::max<uint64_t>(n, 1) * (degrees ? 2u : 1u) * sizeof(uint32_t));
     if (!rc) rc = J.cnt.ensure(3 * sizeof(unsigned long long));
     if (rc) return rc;
-    const DensityCall dn = {std::max<uint32_t>(min_pts, 1u), degrees ? J.out.as<uint32_t>() + n : nullptr};
-    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), 0, &dn);
+    rc = join_density(db, max_div, std::max<uint32_t>(min_pts, 1u), degrees ? J.out.as<uint32_t>() + n : nullptr, J.out.as<uint32_t>(),
+                      J.cnt.as<unsigned long long>());
     if (rc) return rc;
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
     HIP_TRY(hipMemcpyAsync(counts, J.cnt.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
@@ -3130,8 +2627,8 @@ int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, 
     if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: peaks need a bound (max_div)");
     if (radius != SMAFA_NONE && radius > max_div)
         return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: radius %u is larger than max_div %u", radius, max_div);
-    const PeaksCall pk = {radius == SMAFA_NONE ? max_div : radius, (uint32_t *)d_parents, (uint32_t *)d_weights};
-    return self_join(db, max_div, nullptr, 0, (unsigned long long *)d_n_peaks, (uint32_t *)d_labels, 0, nullptr, &pk);
+    return join_peaks(db, max_div, radius == SMAFA_NONE ? max_div : radius, (uint32_t *)d_labels, (uint32_t *)d_parents, (uint32_t *)d_weights,
+                      (unsigned long long *)d_n_peaks);
 } catch (...) {
     return smafa::exception_code("smafa_db_self_peaks_launch");
 }
@@ -3156,9 +2653,8 @@ int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_
     rc = J.out.ensure(std::max<uint64_t>(n, 1) * 3u * sizeof(uint32_t));
     if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
     if (rc) return rc;
-    const PeaksCall pk = {radius == SMAFA_NONE ? max_div : radius, parents ? J.out.as<uint32_t>() + n : nullptr,
-                          weights ? J.out.as<uint32_t>() + 2 * n : nullptr};
-    rc = self_join(db, max_div, nullptr, 0, J.cnt.as<unsigned long long>(), J.out.as<uint32_t>(), 0, nullptr, &pk);
+    rc = join_peaks(db, max_div, radius == SMAFA_NONE ? max_div : radius, J.out.as<uint32_t>(), parents ? J.out.as<uint32_t>() + n : nullptr,
+                    weights ? J.out.as<uint32_t>() + 2 * n : nullptr, J.cnt.as<unsigned long long>());
     if (rc) return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));

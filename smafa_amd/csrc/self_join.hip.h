@@ -1,0 +1,532 @@
+// self_join.hip.h — host code of the self-join of a resident store: one driver that walks the store and knows no consumer
+// (join_pass), and the five calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks).
+// Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
+#pragma once
+
+// one call's state on the host
+struct JoinCall {
+    smafa_db *db;
+    bool no_scans = false;  // one row, or a bound no two rows can exceed: nothing to scan (a scan would list all n^2 pairs to learn "one set")
+    bool nothing = false;   // join_begin: too few rows for any work, the zeroed counters are the result
+    bool inverted = false;  // this call launched inverse_order_kernel
+    double *slot = nullptr;      // the timed pass whose events are not read yet: the J.*_ms it is booked to ...
+    const char *what = nullptr;  // ... and its level-3 trace text (nullptr: none)
+    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned
+};
+
+// a piece's finished list: rows (record of the piece, subject, distance) of block records p0 + b + S * k, k < R
+struct JoinPiece {
+    const smafa_hit *list;
+    unsigned long long count;  // > 0, and all of them in the list
+    uint32_t p0, S, R;
+    const uint32_t *order;  // position -> subject of the list's queries (nullptr: the list names subjects already)
+};
+
+// What a call does with the pieces of one join.  A new consumer supplies `take` (timed_consumer: from its launch) — and whatever
+// it wants in front of and behind the join — and never touches join_pass.
+struct JoinConsumer {
+    std::function<int(const JoinPiece &)> take;  // enqueues the kernel that reads the piece's list
+    std::function<int()> before_wait;            // optional: enqueued in front of the one host wait of every piece
+    bool used = false;                           // some piece was taken: the kernel belongs on the call's list
+};
+
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+static dim3 row_grid(uint32_t n) { return dim3((n + 255u) / 256u); }
+static dim3 list_grid(unsigned long long count) { return dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)); }
+
+// A timed pass on the join's stream: timed_begin, the launches, timed_end — or timed_pass around a single launch.  The slot of J
+// the time belongs to is given with the launch; the events are read later, after a wait that the call needs anyway
+// (timed_sync) — never by a wait of their own.
+static int timed_begin(JoinCall &c, double *slot, const char *what) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    c.slot = slot, c.what = what;
+    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+    return SMAFA_OK;
+}
+static int timed_end(JoinCall &c, uint32_t launches = 1) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+    db->call_launches += launches;
+    return SMAFA_OK;
+}
+template <class Launch>
+static int timed_pass(JoinCall &c, double *slot, const char *what, Launch launch) {
+    RC_TRY(timed_begin(c, slot, what));
+    launch();
+    return timed_end(c);
+}
+
+// the consumer whose pieces go to one launch each, timed into `slot`
+template <class Launch>
+static JoinConsumer timed_consumer(JoinCall &c, double *slot, const char *what, Launch launch) {
+    return {[&c, slot, what, launch](const JoinPiece &p) { return timed_pass(c, slot, what, [&] { launch(p); }); }, nullptr};
+}
+static int consume(JoinConsumer &k, const JoinPiece &p) {
+    k.used = true;
+    return k.take(p);
+}
+
+// a wait of the call's, and the time of the pass before, which has finished by the time the wait returns
+static int timed_sync(JoinCall &c) {
+    smafa_db *db = c.db;
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    float ms = 0.f;
+    if (c.slot && hipEventElapsedTime(&ms, db->join.ev[2], db->join.ev[3]) == hipSuccess) {
+        *c.slot += ms;
+        if (c.what) log_line(3, "%s, %.3f ms", c.what, ms);
+    }
+    c.slot = nullptr;
+    return SMAFA_OK;
+}
+
+// What every call starts with: the statistics of the call before forgotten, `counters` zeros behind d_count, and — unless
+// the store has fewer than min_rows rows (c.nothing) — the re-sort (once, in front: positions are final for the whole join),
+// the events and the scratch list.
+static int join_begin(JoinCall &c, unsigned long long *d_count, size_t counters, uint32_t min_rows) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    db->call_kernels.clear();
+    db->call_ms = 0.f;
+    db->call_launches = db->call_scans = db->last_launches = 0;
+    db->timed = false;
+    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = 0.0;
+    J.blocks = J.rescans = J.joins = J.jump_rounds = 0;
+    J.kept_stuck = false;
+    RC_TRY(use_device(db));
+    HIP_TRY(hipMemsetAsync(d_count, 0, counters * sizeof(unsigned long long), db->stream));
+    db->call_timed = true;
+    c.nothing = db->n < min_rows;
+    if (c.nothing) return SMAFA_OK;
+    if (!c.no_scans) RC_TRY(maybe_resort(db));
+    for (hipEvent_t &e : J.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    RC_TRY(db->count.ensure(sizeof(unsigned long long)));
+    return !c.no_scans && db->hits_cap() < (1ull << 22) ? db->hits.ensure((1ull << 22) * sizeof(smafa_hit)) : SMAFA_OK;
+}
+
+// pos_of[] for the consumers with the exactly-once rule (position(query) < position(subject)): kept while the store stays as it is
+static int join_positions(JoinCall &c) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    if (J.valid && J.generation == db->generation && J.n == db->n && J.resorts == db->resorts) return SMAFA_OK;
+    J.valid = false;
+    RC_TRY(J.pos_of.ensure((size_t)db->n * sizeof(uint32_t)));
+    hipLaunchKernelGGL(smafa_join::inverse_order_kernel, row_grid((uint32_t)db->n), dim3(256), 0, db->stream, db->d_order, (uint32_t)db->n,
+                       J.pos_of.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    J.generation = db->generation, J.n = db->n, J.resorts = db->resorts;
+    J.valid = c.inverted = true;
+    db->call_launches++;
+    return SMAFA_OK;
+}
+
+// The driver: every pair of the store's rows within scan_div of each other, once or twice, as the lists of PIECES to `consumer`.
+// The store is walked in SPANS of join_stride x join_block consecutive positions.  A span's rows become query records on
+// the device (store_records_kernel), dealt round-robin into join_stride BLOCKS: block b holds the span's positions b,
+// b + S, b + 2S, ...  Per block the fixed-bound scan runs its records against the wave tiles from the span's first one to the
+// end of the store — tiles in front of the span could only repeat pairs an earlier span has found — into the handle's
+// scratch list, and the consumer's kernel reads that list behind the scan, on the same stream.
+// Why interleaved: the store is sorted by filter bits, so a block of CONSECUTIVE positions is 65 536 rows whose surviving work
+// sits in a few workgroups (profiles/r07_self_join.txt, stride 1 against 16).
+// The host waits for each piece's scan to learn its row count, and join_piece_rule (engine.h) says what follows: a piece that
+// overflowed the scratch list is scanned again with the list grown to that count (exact at any capacity; a truncated list
+// never reaches a consumer), or cut in half once the list would pass join_scratch_max rows; the reduced piece size is kept
+// until a piece's count falls under a quarter of that ceiling.
+static int join_pass(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    smafa_qset *qs = &db->join_q;
+    qs->db = db;
+    const uint64_t span_rows = db->join_block * db->join_stride;
+    uint64_t piece = db->join_block;  // rows per scan
+    J.joins++;
+    for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
+        const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
+        const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
+        const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
+        // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
+        const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
+        qs->nq = (uint64_t)S * R;
+        qs->serial = g_qset_serial.fetch_add(1);
+        RC_TRY(qs->qrec.ensure(padded * db->QS * sizeof(uint32_t)));
+        RC_TRY(qs->thr.ensure(padded * sizeof(uint32_t)));
+        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
+        const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
+        hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0,
+                           db->stream, reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0,
+                           (uint32_t)p1, S, R, qs->qrec.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+        db->call_launches++;
+        bool rec_timed = false;
+        for (uint32_t b = 0; b < S; b++) {
+            const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
+            for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
+                const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
+                RC_TRY(scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
+                                db->count.as<unsigned long long>(), t0));
+                unsigned long long count = 0;
+                HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+                if (consumer.before_wait) RC_TRY(consumer.before_wait());
+                RC_TRY(timed_sync(c));  // (with it ends the consumer's pass over the piece before)
+                const float before = db->call_ms;
+                note_call_scan(db);
+                const double scan_ms = db->call_ms - before;
+                J.scan_ms += scan_ms;
+                float ms = 0.f;
+                if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
+                rec_timed = true;
+                log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
+                         (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
+                const PieceRule rule = join_piece_rule(count, db->hits_cap(), db->join_scratch_max, q1 - q0, piece, db->join_block);
+                piece = rule.piece;
+                if (rule.verdict != kPieceTake) J.rescans++;
+                if (rule.verdict == kPieceFail)
+                    // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
+                    return set_error(SMAFA_ERR_NOMEM,
+                                     "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
+                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
+                if (rule.verdict == kPieceGrow) RC_TRY(db->hits.ensure(count * sizeof(smafa_hit)));
+                if (rule.verdict != kPieceTake) continue;  // the same rows, or their first half, once more
+                if (count) RC_TRY(consume(consumer, {db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order}));
+                J.blocks++;
+                q0 = q1;
+            }
+        }
+        RC_TRY(timed_sync(c));  // the span's records are overwritten next
+    }
+    return SMAFA_OK;
+}
+
+// What every call ends with: its stage times in smafa_last_scan_ms, and the kernels of the shared path in front of its own
+static void join_finish(JoinCall &c) {
+    smafa_db *db = c.db;
+    const auto &J = db->join;
+    db->call_ms += (float)(J.rec_ms + J.filter_ms + J.count_ms + J.link_ms + J.flatten_ms);
+    db->call_timed = true;  // (scan_range cleared it)
+    if (!c.no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+    if (c.inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
+}
+
+// ---- the kept pair list of the density and peaks calls: what the counting join kept, so that the linking pass need not join again
+static uint64_t kept_room(const smafa_db *db) { return std::min<uint64_t>(db->join.kept.cap / sizeof(smafa_hit), db->density_keep_max); }
+
+// room in J.kept for `rows` rows, at most density_keep_max of them; the first `live` rows are carried over
+static int grow_kept(smafa_db *db, uint64_t rows, uint64_t live) {
+    DevBuf &K = db->join.kept;
+    rows = std::min<uint64_t>(rows, db->density_keep_max);
+    if (rows * sizeof(smafa_hit) <= K.cap) return SMAFA_OK;
+    const uint64_t want = std::min<uint64_t>(db->density_keep_max, std::max<uint64_t>(rows, K.cap / sizeof(smafa_hit) * 2));
+    DevBuf bigger;  // (a bare hipMalloc: a failure here is no failure of the call and leaves no text in smafa_last_error())
+    if (hipMalloc(&bigger.p, want * sizeof(smafa_hit)) == hipSuccess) bigger.cap = want * sizeof(smafa_hit);
+    if (!bigger.p) {
+        // no room for a larger list: the one there is stays as it is and overflows — counted, not stored — and the call
+        // falls back to the second join, which needs no list and gives the same bytes
+        (void)hipGetLastError();
+        db->join.kept_stuck = true;
+        log_line(2, "density: no memory for a kept pair list of %llu rows; the store will be joined twice", (unsigned long long)want);
+        return SMAFA_OK;
+    }
+    hipError_t e = hipSuccess;
+    if (live) e = hipMemcpyAsync(bigger.p, K.p, live * sizeof(smafa_hit), hipMemcpyDeviceToDevice, db->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
+    if (e != hipSuccess) {
+        bigger.release();
+        return set_error(SMAFA_ERR_DEVICE, "density: moving the kept pair list failed: %s", hipGetErrorString(e));
+    }
+    K.release();
+    K = bigger;
+    return SMAFA_OK;
+}
+
+// A consumer whose kernel also moves pairs to J.kept.  In front of every piece's wait the kept total so far is read back (every
+// count/keep pass in front of the piece's scan has ended with it), and in front of its pass (count <= the scratch capacity: a
+// truncated list was scanned again) the list gets room for whatever the piece keeps on top of that, while the knob allows it.
+template <class Launch>
+static JoinConsumer keeping_consumer(JoinCall &c, double *slot, const char *what, Launch launch) {
+    JoinConsumer k = timed_consumer(c, slot, what, launch);
+    k.before_wait = [&c] {
+        smafa_db *db = c.db;
+        auto &J = db->join;
+        unsigned long long &kept_seen = c.kept_seen;
+        HIP_TRY(hipMemcpyAsync(&kept_seen, J.ctl.p, sizeof kept_seen, hipMemcpyDeviceToHost, db->stream));
+        return SMAFA_OK;
+    };
+    k.take = [&c, timed = k.take](const JoinPiece &p) {
+        if (!c.db->join.kept_stuck) RC_TRY(grow_kept(c.db, c.kept_seen + p.count, std::min<uint64_t>(c.kept_seen, kept_room(c.db))));
+        return timed(p);
+    };
+    return k;
+}
+
+// Every count is final and `total` pairs were kept or counted over.  None: there is nothing to link.  All of them in J.kept: ONE
+// launch of the linking kernel over that list (kept_piece) replaces a join.  Else the store is joined a second time with the
+// linking kernel reading each piece's raw list — no list needed, the same bytes.
+enum KeptPlan { kKeptNothing, kKeptOnce, kKeptJoinAgain };
+static KeptPlan kept_plan(const smafa_db *db, unsigned long long total, const char *who, const char *verb) {
+    if (total == 0) return kKeptNothing;
+    if (total <= kept_room(db)) return kKeptOnce;
+    log_line(3, "%s: %llu pairs, the kept list holds %llu: joining once more to %s", who, total, (unsigned long long)kept_room(db), verb);
+    return kKeptJoinAgain;
+}
+static JoinPiece kept_piece(const smafa_db *db, unsigned long long total) { return {db->join.kept.as<smafa_hit>(), total, 0u, 1u, 1u, nullptr}; }
+
+// smafa_db_self_launch: every unordered pair within max_div, once.  join_filter_kernel moves the rows of a piece's list with
+// position(query) < position(subject) to the caller's list.
+static int join_pairs(smafa_db *db, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count) {
+    auto &J = db->join;
+    JoinCall c{db};
+    RC_TRY(join_begin(c, d_count, 1, 2));
+    if (c.nothing) return SMAFA_OK;
+    RC_TRY(join_positions(c));
+    JoinConsumer filter = timed_consumer(c, &J.filter_ms, nullptr, [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_join::join_filter_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, J.pos_of.as<uint32_t>(), d_hits, (unsigned long long)cap, d_count);
+    });
+    RC_TRY(join_pass(c, max_div, filter));
+    join_finish(c);
+    if (filter.used) note_call_kernel(db, "smafa_join::join_filter_kernel");
+    log_line(2, "self-join of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, filter %.3f ms",
+             (uint32_t)db->n, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.filter_ms);
+    return SMAFA_OK;
+}
+
+// the one launch behind the last pass of a linking call (the kernel boundary makes every hook visible), waited for
+template <class Launch>
+static int join_flatten(JoinCall &c, Launch launch) {
+    RC_TRY(timed_sync(c));
+    RC_TRY(timed_pass(c, &c.db->join.flatten_ms, nullptr, launch));
+    return timed_sync(c);
+}
+
+// smafa_db_self_components_launch (components.hip.h): link_rows_kernel unites the two subjects of every row in J.parent — no
+// pos_of[], no filter, no rows for the caller — and after the last piece flatten_labels_kernel writes labels[i] = the smallest
+// subject number of i's component and counts the representatives into *d_count.
+static int join_components(smafa_db *db, uint32_t max_div, uint32_t *d_labels, unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool all_near = max_div >= db->L;
+    JoinCall c{db, db->n < 2 || all_near};
+    RC_TRY(join_begin(c, d_count, 1, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * sizeof(uint32_t)));
+    RC_TRY(timed_begin(c, &J.link_ms, "components: parent[] initialised"));
+    if (all_near)  // parent[i] = i — or 0 everywhere where every row is within the bound of row 0
+        HIP_TRY(hipMemsetAsync(J.parent.p, 0, (size_t)n * sizeof(uint32_t), db->stream));
+    else
+        hipLaunchKernelGGL(smafa_cc::init_labels_kernel, row_grid(n), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n);
+    RC_TRY(timed_end(c, all_near ? 0u : 1u));
+    JoinConsumer link = timed_consumer(c, &J.link_ms, "components: parent[] linked with a piece's rows", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_cc::link_rows_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           J.parent.as<uint32_t>());
+    });
+    if (!c.no_scans) RC_TRY(join_pass(c, max_div, link));
+    RC_TRY(join_flatten(c, [&] {
+        hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, row_grid(n), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, d_labels, d_count);
+    }));
+    join_finish(c);
+    if (!all_near) note_call_kernel(db, "smafa_cc::init_labels_kernel");
+    if (link.used) note_call_kernel(db, "smafa_cc::link_rows_kernel");
+    note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
+    log_line(2, "components of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, link %.3f ms, "
+             "flatten %.3f ms", n, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms, J.flatten_ms);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_levels_launch (levels.hip.h): d_labels is (max_div + 1) x n, d_count as many counters, J.parent one union-find per
+// SCANNED level (E = min(max_div, L - 1) + 1 of them; the levels above are all zeros and need no scan).  The join runs once at
+// bound E - 1 and hook_levels_kernel unites the subjects of a row at every level from its distance upwards;
+// flatten_levels_kernel writes every level in one launch.
+static int join_levels(smafa_db *db, uint32_t max_div, uint32_t *d_labels, unsigned long long *d_count) {
+    auto &J = db->join;
+    const uint32_t n_levels = max_div + 1u, E = std::min(n_levels, std::max<uint32_t>(db->L, 1u)), scan_div = E - 1u;
+    JoinCall c{db, db->n < 2};
+    RC_TRY(join_begin(c, d_count, n_levels, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * E * sizeof(uint32_t)));
+    RC_TRY(timed_pass(c, &J.link_ms, "levels: parent[] initialised", [&] {
+        hipLaunchKernelGGL(smafa_lv::init_levels_kernel, row_grid(n), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, E);
+    }));
+    JoinConsumer hook = timed_consumer(c, &J.link_ms, "levels: parent[] linked with a piece's rows", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_lv::hook_levels_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           J.parent.as<uint32_t>(), n, E);
+    });
+    if (!c.no_scans) RC_TRY(join_pass(c, scan_div, hook));
+    RC_TRY(join_flatten(c, [&] {
+        hipLaunchKernelGGL(smafa_lv::flatten_levels_kernel, row_grid(n), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, E, n_levels,
+                           d_labels, d_count);
+    }));
+    join_finish(c);
+    note_call_kernel(db, "smafa_lv::init_levels_kernel");
+    if (hook.used) note_call_kernel(db, "smafa_lv::hook_levels_kernel");
+    note_call_kernel(db, "smafa_lv::flatten_levels_kernel");
+    log_line(2, "levels 0..%u of %u rows, joined at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, "
+             "link %.3f ms, flatten %.3f ms", max_div, n, scan_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms, J.flatten_ms);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_density_launch (density.hip.h): d_labels is n labels, d_count three counters, J.parent holds parent[], degree[]
+// and attach[].  The join runs at max_div with count_keep_kernel per piece (the exactly-once rule, so pos_of[] as for the plain
+// join), which raises both degrees of every kept pair and moves the pair to J.kept while that has room; the kept total then
+// decides (kept_plan) how link_cores_kernel gets the pairs.  No core row at all: no link.  min_pts <= 1 without degrees:
+// nothing to count, the one join links directly, as components.
+// min_pts >= 1; d_degrees: n entries, or nullptr
+static int join_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t *d_degrees, uint32_t *d_labels, unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool counting = min_pts > 1u || d_degrees, all_near = max_div >= db->L;
+    JoinCall c{db, db->n < 2 || all_near};
+    RC_TRY(join_begin(c, d_count, 3, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * 3u * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(2 * sizeof(unsigned long long)));
+    uint32_t *const parent = J.parent.as<uint32_t>(), *const degree = parent + n, *const attach = parent + 2 * (size_t)n;
+    RC_TRY(timed_begin(c, counting ? &J.count_ms : &J.link_ms, "density: parent[] initialised"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
+    // every row within the bound of every other: degrees n - 1, one set
+    hipLaunchKernelGGL(smafa_dn::init_density_kernel, row_grid(n), dim3(256), 0, db->stream, degree, parent, attach, n,
+                       all_near ? n - 1u : 0u, all_near ? 1u : 0u);
+    RC_TRY(timed_end(c));
+    JoinConsumer count = keeping_consumer(c, &J.count_ms, "density: parent[] untouched, a piece's rows counted", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_dn::count_keep_kernel, list_grid(p.count), dim3(256), 0,
+                           db->stream, p.list, p.count, p.p0, p.S, p.R, p.order, J.pos_of.as<uint32_t>(), degree, min_pts,
+                           J.kept.as<smafa_hit>(), (unsigned long long)kept_room(db), J.ctl.as<unsigned long long>());
+    });
+    JoinConsumer link = timed_consumer(c, &J.link_ms, "density: parent[] linked with a piece's rows", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_dn::link_cores_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           degree, min_pts, parent, attach);
+    });
+    if (!c.no_scans && counting) {
+        RC_TRY(join_positions(c));
+        RC_TRY(join_pass(c, max_div, count));
+        unsigned long long ctl[2] = {0, 0};  // every degree is final: the kept total; "some row is core"
+        HIP_TRY(hipMemcpyAsync(ctl, J.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, db->stream));
+        RC_TRY(timed_sync(c));
+        // (no core row: nothing to link, every row keeps the set and the attach[] it was given)
+        const KeptPlan plan = min_pts > 1u && !ctl[1] ? kKeptNothing : kept_plan(db, ctl[0], "density", "link");
+        if (plan == kKeptOnce) RC_TRY(consume(link, kept_piece(db, ctl[0])));
+        if (plan == kKeptJoinAgain) RC_TRY(join_pass(c, max_div, link));
+    } else if (!c.no_scans) {
+        RC_TRY(join_pass(c, max_div, link));
+    }
+    RC_TRY(join_flatten(c, [&] {
+        hipLaunchKernelGGL(smafa_dn::flatten_density_kernel, row_grid(n), dim3(256), 0, db->stream, parent, degree, attach, n, min_pts,
+                           d_labels, d_degrees, d_count);
+    }));
+    join_finish(c);
+    note_call_kernel(db, "smafa_dn::init_density_kernel");
+    if (count.used) note_call_kernel(db, "smafa_dn::count_keep_kernel");
+    if (link.used) note_call_kernel(db, "smafa_dn::link_cores_kernel");
+    note_call_kernel(db, "smafa_dn::flatten_density_kernel");
+    log_line(2, "density of %u rows at bound %u, min_pts %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
+             "count/keep %.3f ms, link %.3f ms, flatten %.3f ms", n, max_div, min_pts, J.blocks + J.rescans, J.rescans, J.joins,
+             J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms);
+    return SMAFA_OK;
+}
+
+// settle_kernel behind the climb, then pointer doubling until a round changes nothing; without a climb every label is its own
+// row or the crown: flat already
+static int peaks_settle(JoinCall &c, bool crowned, bool climbed, uint32_t *d_labels, uint32_t *d_parents, uint32_t *d_weights,
+                        unsigned long long *d_count) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(join_flatten(c, [&] {
+        hipLaunchKernelGGL(smafa_pk::settle_kernel, row_grid(n), dim3(256), 0,
+                           db->stream, J.parent.as<unsigned long long>(), J.parent.as<uint32_t>() + 2 * (size_t)n, n,
+                           crowned ? J.ctl.as<unsigned long long>() + 2 : (const unsigned long long *)nullptr, d_labels, d_parents,
+                           d_weights, d_count);
+    }));
+    for (uint32_t changed = climbed ? 1u : 0u; changed; J.jump_rounds++) {
+        if (J.jump_rounds == 33u) return set_error(SMAFA_ERR_DEVICE, "peaks: parent[] is no forest (33 jump rounds did not flatten it)");
+        uint32_t *const d_changed = reinterpret_cast<uint32_t *>(J.ctl.as<unsigned long long>() + 3);
+        HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), db->stream));
+        RC_TRY(timed_pass(c, &J.flatten_ms, nullptr, [&] {
+            hipLaunchKernelGGL(smafa_pk::jump_kernel, row_grid(n), dim3(256), 0, db->stream, d_labels, n, d_changed);
+        }));
+        HIP_TRY(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, db->stream));
+        RC_TRY(timed_sync(c));
+    }
+    return SMAFA_OK;
+}
+
+// smafa_db_self_peaks_launch (peaks.hip.h): d_labels is n labels, d_count one counter, J.parent holds best[] (the 8-byte one
+// first) and weight[].  The join runs at max_div with weigh_keep_kernel per piece (the exactly-once rule), which raises both
+// weights of every kept pair within the radius and moves every kept pair to J.kept while that has room; the kept total then
+// decides (kept_plan) how climb_kernel gets the pairs.  settle_kernel writes parents, weights and the peak count, and jump_kernel
+// rounds flatten the labels.  max_div >= seq_len (crowned: no two rows can exceed the bound, the pairs are needed for the
+// weights alone): the join, if any, runs at the radius and only counts — nothing is kept or climbed — and crown_kernel finds
+// the one peak.
+// radius <= max_div; d_parents, d_weights: n entries each, or nullptr
+static int join_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *d_labels, uint32_t *d_parents, uint32_t *d_weights,
+                      unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool crowned = max_div >= db->L;
+    const uint32_t scan_div = crowned ? radius : max_div;
+    JoinCall c{db, db->n < 2 || scan_div >= db->L};
+    RC_TRY(join_begin(c, d_count, 1, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * 3u * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(4 * sizeof(unsigned long long)));
+    unsigned long long *const best = J.parent.as<unsigned long long>();
+    uint32_t *const weight = J.parent.as<uint32_t>() + 2 * (size_t)n;
+    RC_TRY(timed_begin(c, &J.count_ms, "peaks: weight[] initialised"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 4 * sizeof(unsigned long long), db->stream));
+    // every row within the radius of every other: weights n
+    hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, best, weight, n, scan_div >= db->L ? n : 1u, 0u);
+    RC_TRY(timed_end(c));
+    const auto launch_weigh = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_pk::weigh_keep_kernel, list_grid(p.count), dim3(256), 0,
+                           db->stream, p.list, p.count, p.p0, p.S, p.R, p.order, J.pos_of.as<uint32_t>(), weight, radius,
+                           J.kept.as<smafa_hit>(), crowned ? 0ull : (unsigned long long)kept_room(db), J.ctl.as<unsigned long long>());
+    };
+    const auto launch_climb = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_pk::climb_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           weight, best);
+    };
+    const char *const weighed = "peaks: a piece's rows weighed", *const climbed = "peaks: a piece's rows climbed";
+    // at a crowned bound nothing is kept
+    JoinConsumer weigh = crowned ? timed_consumer(c, &J.count_ms, weighed, launch_weigh) : keeping_consumer(c, &J.count_ms, weighed, launch_weigh);
+    JoinConsumer climb = timed_consumer(c, &J.link_ms, climbed, launch_climb);
+    if (!c.no_scans) {
+        RC_TRY(join_positions(c));
+        RC_TRY(join_pass(c, scan_div, weigh));
+    }
+    unsigned long long kept_total = 0;
+    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    // every weight is final: the rows' own keys — or the crown — and the climb over the kept list, if that has every pair, in ONE
+    // timed pass (its trace text: the last kind of pass that ran)
+    const KeptPlan plan = crowned ? kKeptNothing : kept_plan(db, kept_total, "peaks", "climb");
+    RC_TRY(timed_begin(c, &J.link_ms, plan == kKeptOnce ? climbed : weigh.used ? weighed : "peaks: weight[] initialised"));
+    if (crowned)
+        hipLaunchKernelGGL(smafa_pk::crown_kernel, row_grid(n), dim3(256), 0, db->stream, weight, n, J.ctl.as<unsigned long long>() + 2);
+    else
+        hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, best, weight, n, 0u, 1u);
+    HIP_TRY(hipGetLastError());
+    climb.used = plan == kKeptOnce;
+    if (climb.used) launch_climb(kept_piece(db, kept_total));
+    RC_TRY(timed_end(c, climb.used ? 2u : 1u));
+    if (plan == kKeptJoinAgain) RC_TRY(join_pass(c, scan_div, climb));
+    RC_TRY(peaks_settle(c, crowned, climb.used, d_labels, d_parents, d_weights, d_count));
+    join_finish(c);
+    note_call_kernel(db, "smafa_pk::init_peaks_kernel");
+    if (weigh.used) note_call_kernel(db, "smafa_pk::weigh_keep_kernel");
+    if (climb.used) note_call_kernel(db, "smafa_pk::climb_kernel");
+    if (crowned) note_call_kernel(db, "smafa_pk::crown_kernel");
+    note_call_kernel(db, "smafa_pk::settle_kernel");
+    if (J.jump_rounds) note_call_kernel(db, "smafa_pk::jump_kernel");
+    log_line(2, "peaks of %u rows at bound %u, radius %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
+             "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s", n, max_div, radius, J.blocks + J.rescans,
+             J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
+             J.jump_rounds == 1 ? "" : "s");
+    return SMAFA_OK;
+}
+#undef RC_TRY

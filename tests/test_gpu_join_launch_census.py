@@ -1,0 +1,38 @@
+"""The self-join's five calls launch what the commit before the driver/consumer split launched (self_join.hip.h).
+
+tests/join_launch_census.json holds, per call and case, `launches` and `scans` of smafa_last_call_stats and the whole list of
+smafa_last_call_kernels, recorded by tools/join_census.py from a build of that parent commit (three repeats).  The cases are
+the stores of the other GPU suites: the dense 4 000-row store at its bounds (the rescan at the default ceiling, the halving at
+1 000 000 rows), nt60 x 3 020 rows with the kept list unset, 0 and half the pairs, aa60 x 20 020 rows in blocks of 128 at
+stride 2 (many spans, a short last block), no row, one row, bounds at and above the sequence length, and a peaks radius
+below the bound under and at a crowned bound.  Where the parent's own repeats differed in `launches` — the jump rounds of a
+peaks call that climbed — the table holds null and only scans and kernels are pinned."""
+import json
+import os
+import sys
+
+import pytest
+
+from smafa_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import join_census  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "join_launch_census.json")) as f:
+    TABLE = json.load(f)
+
+
+@pytest.mark.parametrize("call", join_census.CALLS)
+def test_launches_scans_and_kernels_are_the_parents(call):
+    want = TABLE["calls"][call]
+    got = join_census.census(join_census.load(_lib.LIB_PATH), call)
+    assert sorted(got) == sorted(want)
+    for cid, rec in want.items():
+        print(call, cid, got[cid]["launches"], got[cid]["scans"], got[cid]["kernels"])
+        assert got[cid]["scans"] == rec["scans"], (call, cid)
+        assert got[cid]["kernels"] == rec["kernels"], (call, cid)
+        if rec["launches"] is not None:
+            assert got[cid]["launches"] == rec["launches"], (call, cid)
