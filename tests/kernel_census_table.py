@@ -9,6 +9,10 @@ amino acids on five), the row length L, the bound D (None: none) and k (0: every
 prefilter, the zone level (0 off, 2 forced), whether a block index is built, `marker` (the note the call's kernel list adds after
 the template-id for one form of the kernel: "zone level on", "sample counts"), E — the bound its edge pairs are planted at
 (tests/kernel_edges.py) — and `spread` (fillers at distances 0..spread, so every step of the near-hit ladder finishes some).
+
+Every fixed-bound case here launches over the whole store (first tile 0).  The fixed-bound forms at a non-zero first tile — the
+self-join's triangular cut, for every word count and the wide, generic, zone and few-query kernels — are covered by the self-join
+shape tests (tests/test_gpu_self_join_shapes.py).
 """
 from __future__ import annotations
 
