@@ -425,6 +425,54 @@ int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint
 int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, void *d_labels, void *d_parents /* may be NULL */, void *d_weights /* may be NULL */, void *d_n_peaks /* uint64 */);
 int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *labels, uint32_t *parents /* may be NULL */, uint32_t *weights /* may be NULL */, uint64_t cap, uint64_t *n_peaks);
 
+/* ------------------------------------------------- neighbour lists of the store (the self-join's graph in CSR form, k nearest) */
+/*
+ * "Who is near row i, nearest first": the one general output of the self-join, in the form graph tools take (a CSR matrix,
+ * community detection, UMAP, HDBSCAN core distances, k-distance plots).  smafa_db_self_hits returns each edge once, under
+ * its smaller endpoint; here every row has its own list.  max_div = D is the bound, max_num_hits = k the cut (SMAFA_NONE: no
+ * cut).  Subjects are numbered in append order.
+ *   N(i)          = { j != i : distance(i, j) <= D }, ordered by (distance, j) ascending.  Exact copies (distance 0) are
+ *                   neighbours like any other.
+ *   list(i)       = the first min(|N(i)|, k) entries of N(i): ties at the cut go to the smaller subject number.
+ *   offsets[i]    = the start of list(i); offsets[n_subjects] = total, the number of entries.  Without a cut
+ *                   offsets[i + 1] - offsets[i] is smafa_db_self_density's degree[i] and total is twice the pair count of
+ *                   smafa_db_self_launch.
+ *   neighbours[], dists[] hold list(i) at offsets[i] .. offsets[i + 1); dists may be NULL.
+ * The answer is a function of the store, D and k alone: the same bytes under smafa_set_prefilter / smafa_set_zone_level /
+ * smafa_set_index, every SMAFA_JOIN_* setting and SMAFA_NEIGHBOUR_SORT.
+ * Capacity as for smafa_db_self_hits: cap = the capacity of `neighbours` (and of `dists`) in entries.  The offsets and the
+ * total are exact at any capacity and always written.  total > cap: SMAFA_ERR_CAPACITY, *n_out (*d_total) = the entries
+ * needed, neighbours and dists untouched.  cap = 0 with NULL lists asks for the degrees alone.  Nothing is kept for the retry:
+ * it joins again.
+ * Not in the reference.  The pairs never leave the device: the self-join's exactly-once rule is applied to each piece's list
+ * and every kept pair {a, b, d} is appended as two 8-byte entries, (a; d; b) and (b; d; a), to a handle-owned entry list
+ * that grows in front of a piece's pass (doubling, live entries carried over).  Behind the join the entries are ordered by
+ * (row, dist, neighbour) with the device radix sort — one sort of the entries as keys where row and distance fit 32 bits
+ * (the distance field is as wide as min(D, seq_len) needs, the row field as n_subjects - 1 needs), otherwise two stable sorts;
+ * SMAFA_NEIGHBOUR_SORT=2, read when the handle is made, forces the latter — a binary search per row finds where each row
+ * begins, with a cut the degrees are cut and summed, and one pass over the sorted entries writes the lists.  The host learns
+ * the total (with a cut: one wait more) and decides on SMAFA_ERR_CAPACITY.  Handle-owned scratch: 8 (12) B per entry for the
+ * list, 8 (24) B per entry for the sort, 16 B per subject with a cut.
+ * Edges: an empty store gives offsets {0} and total 0; one row {0, 0}.  max_div >= seq_len is no shortcut — the distances
+ * still differ: the join runs at min(max_div, seq_len) and every row lists every other.  SMAFA_ERR_INVALID, with the argument
+ * named in smafa_last_error() and nothing written: a NULL handle, offsets or total (n_out); NULL neighbours with a capacity;
+ * max_div = SMAFA_NONE; max_num_hits = 0.  More than 2^31 - 1 entries before the cut: SMAFA_ERR_NOMEM with the count in the
+ * text (the device sort's item limit); an entry list that cannot grow: SMAFA_ERR_NOMEM; the handle stays usable.  The
+ * self-join's own failure is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list).
+ *
+ * smafa_db_self_neighbours_launch: device-resident form.  d_offsets = device buffer of n_subjects + 1 uint64, d_neighbours and
+ * d_dists = device buffers of cap uint32 (d_neighbours may be NULL if cap == 0, d_dists may be NULL), d_total = device uint64.
+ * Synchronisation as for smafa_db_self_peaks_launch.  smafa_last_scan_ms / smafa_last_call_stats hold the device time and
+ * launches of record building, scans, pack passes, the sort, the bounds / cut pass and the emit pass;
+ * smafa_last_call_kernels lists the scan-family instantiations first, then smafa_join::store_records_kernel, then
+ * smafa_join::inverse_order_kernel if it ran, then the smafa_nb:: kernels that ran: mirror_pack_kernel, row_bounds_kernel,
+ * cut_degrees_kernel, emit_kernel (with no entry at all: mirror_pack_kernel alone).
+ *
+ * smafa_db_self_neighbours: host form.  offsets holds n_subjects + 1 entries.
+ */
+int smafa_db_self_neighbours_launch(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, void *d_offsets /* n_subjects + 1 uint64 */, void *d_neighbours /* cap uint32, may be NULL if cap == 0 */, void *d_dists /* cap uint32 or NULL */, uint64_t cap, void *d_total /* uint64 */);
+int smafa_db_self_neighbours(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, uint64_t *offsets, uint32_t *neighbours, uint32_t *dists /* may be NULL */, uint64_t cap, uint64_t *n_out);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -576,6 +624,10 @@ int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts
  * (smafa_db_self_peaks at max_divergence and radius), "{i}\t{label}\t{parent}\t{weight}\n" in subject order.  An empty DB
  * prints nothing. */
 int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, int out_fd, int device);
+/* `smafa neighbours` (not in the reference): the same DB, and per subject its neighbours within max_divergence, nearest first,
+ * at most max_num_hits of them (SMAFA_NONE: all) — smafa_db_self_neighbours, a degrees-only call and then the sized one —
+ * "{i}\t{j}\t{dist}\n" per entry, both directions of every pair, ordered by (i, dist, j).  An empty DB prints nothing. */
+int smafa_neighbours(const char *db_path, uint32_t max_divergence, uint32_t max_num_hits, int out_fd, int device);
 /* count(paths) — src/lib.rs:378-398 (JSON to out_fd).  Host only. */
 int smafa_count(const char *const *paths, uint64_t n_paths, int out_fd);
 

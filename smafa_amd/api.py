@@ -298,6 +298,42 @@ class SubjectStore:
                                                C.c_void_p(d_weights) if d_weights else None,
                                                C.c_void_p(d_n_peaks) if d_n_peaks else None))
 
+    # ---- neighbour lists ------------------------------------------------------------------
+    def self_neighbours(self, max_divergence: int, k: Optional[int] = None, dists: bool = True, first_cap: int = 1 << 16):
+        """(offsets uint64[n + 1], neighbours uint32, dists uint32 or None) — smafa_db_self_neighbours: the store's graph at
+        max_divergence as per-row lists.  Row i's neighbours, every other subject within the bound, are
+        neighbours[offsets[i]:offsets[i + 1]], ordered by (distance, number), with their distances beside them in `dists`;
+        k cuts every list to its k nearest (ties to the smaller number).  `first_cap` entries are offered first, and the
+        buffers grow to what the call asks for (it joins again).
+
+        The three arrays are a CSR matrix as they are: scipy.sparse.csr_matrix((dists, neighbours, offsets), shape=(n, n))
+        (distance 0, an exact copy, is a stored zero).  The k-distance of a row with at least k neighbours — the value a
+        k-distance plot sorts to choose DBSCAN's eps — is dists[offsets[i] + k - 1]."""
+        n = self.info().n_subjects
+        cap = max(int(first_cap), 0)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        while True:
+            nb = np.zeros(max(cap, 1), dtype=np.uint32)
+            ds = np.zeros(max(cap, 1), dtype=np.uint32) if dists else None
+            n_out = C.c_uint64(0)
+            rc = lib().smafa_db_self_neighbours(self._h, _opt(max_divergence), _opt(k), offsets.ctypes.data, nb.ctypes.data,
+                                                ds.ctypes.data if dists else None, cap, C.byref(n_out))
+            if rc == _lib.ERR_CAPACITY:
+                cap = int(n_out.value)
+                continue
+            check(rc)
+            return offsets, nb[: n_out.value], (ds[: n_out.value] if dists else None)
+
+    def self_neighbours_launch(self, max_divergence: int, k: Optional[int], d_offsets: int, d_neighbours: int, d_dists: int, cap: int,
+                               d_total: int) -> None:
+        """device-resident form (smafa_db_self_neighbours_launch): n_subjects + 1 uint64 offsets in d_offsets, up to `cap`
+        uint32 neighbours in d_neighbours and distances in d_dists (0: not wanted), the number of entries in *d_total (device
+        uint64); SmafaError with code ERR_CAPACITY where they do not fit (offsets and total are written all the same)"""
+        check(lib().smafa_db_self_neighbours_launch(self._h, _opt(max_divergence), _opt(k), C.c_void_p(d_offsets) if d_offsets else None,
+                                                    C.c_void_p(d_neighbours) if d_neighbours else None,
+                                                    C.c_void_p(d_dists) if d_dists else None, cap,
+                                                    C.c_void_p(d_total) if d_total else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -576,6 +612,12 @@ def density(db_path: str, max_divergence: int, min_pts: int, out_fd: int = 1, de
     """`smafa density`: "i\\tlabel\\tdegree" per subject of the DB file — its density-cluster label at max_divergence and
     min_pts (-1 for noise) and the number of other subjects within the bound of it — to out_fd."""
     check(lib().smafa_density(os.fsencode(db_path), _opt(max_divergence), int(min_pts), out_fd, device))
+
+
+def neighbours(db_path: str, max_divergence: int, max_num_hits: Optional[int] = None, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa neighbours`: "i\\tj\\tdist" per subject i of the DB file and neighbour j within max_divergence, nearest first, at
+    most max_num_hits per i (smafa_db_self_neighbours), to out_fd."""
+    check(lib().smafa_neighbours(os.fsencode(db_path), _opt(max_divergence), _opt(max_num_hits), out_fd, device))
 
 
 def peaks(db_path: str, max_divergence: int, radius: Optional[int] = 0, out_fd: int = 1, device: int = 0) -> None:

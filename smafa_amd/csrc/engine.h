@@ -65,6 +65,22 @@ inline PieceRule join_piece_rule(uint64_t count, uint64_t capacity, uint64_t cei
     return {kPieceHalve, half > 64 ? half : 64};
 }
 
+// How the neighbours call (self_join.hip.h: join_neighbours) orders its entries (row, dist, neighbour): a pure function of the
+// store's rows, the bound and the sequence length.  dist_bits holds the largest distance the join can report,
+// min(max_div, seq_len); row_bits holds n - 1.  Where both fit 32 bits an entry is ONE 64-bit key, row << (32 + dist_bits) |
+// dist << 32 | neighbour, and one radix sort over its 32 + dist_bits + row_bits bits orders the list (sorts = 1); otherwise two
+// stable sorts do, by dist << 32 | neighbour and then by the row (sorts = 2).
+struct NeighbourKey {
+    uint32_t dist_bits, row_bits, sorts;
+};
+inline NeighbourKey neighbour_key_rule(uint64_t n, uint32_t max_div, uint32_t seq_len) {
+    const uint64_t bound = max_div < seq_len ? max_div : seq_len, last = n ? n - 1 : 0;
+    uint32_t dist_bits = 1, row_bits = 1;
+    while (dist_bits < 32 && (1ull << dist_bits) <= bound) dist_bits++;
+    while (row_bits < 32 && (1ull << row_bits) <= last) row_bits++;
+    return {dist_bits, row_bits, row_bits + dist_bits <= 32 ? 1u : 2u};
+}
+
 // Bring the HIP runtime and the device context up (a few hundred ms the first time in a process).  The drivers call it
 // on a helper thread while they read and decode their input; failures are ignored here — the first real call reports.
 void warm_device(int device);

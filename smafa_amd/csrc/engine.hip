@@ -23,6 +23,7 @@
 #include "levels.hip.h"
 #include "density.hip.h"
 #include "peaks.hip.h"
+#include "neighbours.hip.h"
 
 namespace smafa {
 
@@ -216,12 +217,20 @@ struct smafa_db {
         // peaks (peaks.hip.h): parent holds best[] (8 B per subject) and weight[] (4 B) behind it, live for one call; kept, ctl,
         // count_ms (init + weigh/keep passes), link_ms (the climb), flatten_ms (settle + jump rounds) and joins as for density
         uint32_t jump_rounds = 0;
+        // neighbours (neighbours.hip.h): the entry list, 8 B per entry and 4 B more behind them where the sort needs the row apart;
+        // its capacity is kept across calls, its contents are not.  ctl[0] is the entry total; parent holds lower[] and the cut
+        // degrees, 8 B x 2 per subject, live for one call; filter_ms (pack), count_ms (sort), link_ms (bounds, cut and sum) and
+        // flatten_ms (emit)
+        DevBuf entries;
+        uint64_t entries_cap = 0;  // entries the list has room for
+        uint32_t growths = 0;      // how often the last call grew it
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
     uint64_t join_scratch_max = 1ull << 27;  // rows the block's scratch list may grow to (1.5 GB) before the block is halved (SMAFA_JOIN_SCRATCH_MAX)
     uint64_t density_keep_max = 1ull << 27;  // rows the kept pair list (density and peaks calls) may grow to; 0: never kept, the store is joined
                                              // twice (SMAFA_DENSITY_KEEP_MAX; default: the value of join_scratch_max)
+    bool neighbour_two_sorts = false;  // neighbours: the two-sort order also where one key would hold an entry (SMAFA_NEIGHBOUR_SORT=2, tests)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
     uint64_t hits_cap() const { return hits.cap / sizeof(smafa_hit); }
@@ -1429,7 +1438,7 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 }
 
 // ---------------------------------------------------------------------------------------------
-#include "self_join.hip.h"  // the self-join: its driver and the five calls that consume its pieces
+#include "self_join.hip.h"  // the self-join: its driver and the six calls that consume its pieces
 
 void db_life_stats(const smafa_db *db, double *kernel_ms, uint64_t *launches) {
     *kernel_ms = db ? db->life_ms : 0.0;
@@ -1892,6 +1901,7 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *jv = getenv("SMAFA_JOIN_BLOCK")) db->join_block = std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64);
     if (const char *jv = getenv("SMAFA_JOIN_STRIDE")) db->join_stride = std::min<uint64_t>(4096, std::max<uint64_t>(1, strtoull(jv, nullptr, 10)));
     if (const char *jv = getenv("SMAFA_JOIN_SCRATCH_MAX")) db->join_scratch_max = std::max<uint64_t>(4096, strtoull(jv, nullptr, 10));
+    if (const char *jv = getenv("SMAFA_NEIGHBOUR_SORT")) db->neighbour_two_sorts = atoi(jv) == 2;
     db->density_keep_max = db->join_scratch_max;
     if (const char *jv = getenv("SMAFA_DENSITY_KEEP_MAX")) {  // any number of rows, 0 included (two joins); not a number: ignored, aloud
         char *end = nullptr;
@@ -2030,7 +2040,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
-                      &db->join.kept, &db->join.ctl, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
+                      &db->join.kept, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
         if (e) (void)hipEventDestroy(e);
@@ -2668,6 +2678,68 @@ int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_peaks");
+}
+
+// the argument checks the two neighbours calls share (nothing is written before they pass)
+static int neighbours_args(const char *who, const smafa_db *db, uint32_t max_div, uint32_t max_num_hits, const void *offsets,
+                           const void *neighbours, uint64_t cap, const void *total, const char *total_name) {
+    if (!offsets) return set_error(SMAFA_ERR_INVALID, "%s: NULL offsets", who);
+    if (!total) return set_error(SMAFA_ERR_INVALID, "%s: NULL %s", who, total_name);
+    if (!neighbours && cap) return set_error(SMAFA_ERR_INVALID, "%s: NULL neighbours with a capacity", who);
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: neighbour lists need a bound (max_div)", who);
+    if (max_num_hits == 0) return set_error(SMAFA_ERR_INVALID, "%s: max_num_hits is 0 (SMAFA_NONE: no cut)", who);
+    if (!db) return set_error(SMAFA_ERR_INVALID, "%s: NULL handle", who);  // (last: the checks above need no handle, and no device)
+    return SMAFA_OK;
+}
+
+int smafa_db_self_neighbours_launch(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, void *d_offsets, void *d_neighbours,
+                                    void *d_dists, uint64_t cap, void *d_total) try {
+    int rc = neighbours_args("smafa_db_self_neighbours_launch", db, max_div, max_num_hits, d_offsets, d_neighbours, cap, d_total, "total");
+    if (rc) return rc;
+    return join_neighbours(db, max_div, max_num_hits, (unsigned long long *)d_offsets, (uint32_t *)d_neighbours, (uint32_t *)d_dists, cap,
+                           (unsigned long long *)d_total);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_neighbours_launch");
+}
+
+int smafa_db_self_neighbours(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, uint64_t *offsets, uint32_t *neighbours,
+                             uint32_t *dists, uint64_t cap, uint64_t *n_out) try {
+    int rc = neighbours_args("smafa_db_self_neighbours", db, max_div, max_num_hits, offsets, neighbours, cap, n_out, "n_out");
+    if (rc) return rc;
+    *n_out = 0;
+    rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // no row lists more than the others, or than the cut: beyond that a larger capacity buys nothing
+    const uint64_t room = std::min<uint64_t>(cap, n < 2 ? 0 : n * std::min<uint64_t>(n - 1, max_num_hits));
+    // the offsets, the neighbours and the distances behind them, on their way to the caller
+    rc = J.out.ensure((n + 1) * sizeof(uint64_t) + room * (dists ? 2u : 1u) * sizeof(uint32_t));
+    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
+    if (rc) return rc;
+    unsigned long long *const d_offsets = J.out.as<unsigned long long>();
+    uint32_t *const d_neighbours = reinterpret_cast<uint32_t *>(d_offsets + n + 1), *const d_dists = dists ? d_neighbours + room : nullptr;
+    rc = join_neighbours(db, max_div, max_num_hits, d_offsets, d_neighbours, d_dists, room, J.cnt.as<unsigned long long>());
+    if (rc && rc != SMAFA_ERR_CAPACITY) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the offsets are copied as they lie");
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, J.cnt.p, sizeof total, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipMemcpyAsync(offsets, d_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
+    if (!rc && total) {
+        HIP_TRY(hipMemcpyAsync(neighbours, d_neighbours, total * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+        if (dists) HIP_TRY(hipMemcpyAsync(dists, d_dists, total * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    *n_out = total;
+    if (rc)  // (join_neighbours saw `room`; the text names the capacity the caller gave)
+        set_error(SMAFA_ERR_CAPACITY, "neighbour lists too small: %llu entries needed, capacity %llu", total, (unsigned long long)cap);
+    for (DevBuf *b : {&J.out, &db->hits, &J.entries})
+        if (b->cap > (512ull << 20)) b->release();
+    if (db->keys_a.cap > (512ull << 20))
+        for (DevBuf *b : {&db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b, &db->sort_tmp}) b->release();
+    return rc;  // (SMAFA_ERR_CAPACITY: its text stands, the offsets and *n_out are written, the lists are not)
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_neighbours");
 }
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -823,6 +823,57 @@ int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, i
     return smafa::exception_code("smafa_peaks");
 }
 
+// ------------------------------------------------------------------------------------ neighbours
+// The neighbours of every subject of a DB file within the bound, nearest first, at most max_num_hits of them
+// (smafa_db_self_neighbours), printed "{i}\t{j}\t{dist}\n" ordered by (i, dist, j): both directions of every pair.
+int smafa_neighbours(const char *db_path, uint32_t max_divergence, uint32_t max_num_hits, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: a bound (max_divergence) is needed");
+    if (max_num_hits == 0) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: max_num_hits is 0");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    const size_t n = (size_t)info.n_subjects;
+    std::vector<uint64_t> offsets(n + 1);
+    std::vector<uint32_t> neighbours, dists;
+    uint64_t total = 0;
+    // the capacity protocol: the degrees alone first, then the call sized by them
+    rc = smafa_db_self_neighbours(store.db, max_divergence, max_num_hits, offsets.data(), nullptr, nullptr, 0, &total);
+    if (rc == SMAFA_ERR_CAPACITY) {
+        neighbours.resize((size_t)total);
+        dists.resize((size_t)total);
+        rc = smafa_db_self_neighbours(store.db, max_divergence, max_num_hits, offsets.data(), neighbours.data(), dists.data(), total, &total);
+    }
+    if (rc) return rc;
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // entries per write, about
+    for (size_t i = 0; i < n; i++) {
+        for (uint64_t e = offsets[i]; e < offsets[i + 1]; e++) {
+            append_u32(text, (uint32_t)i);
+            text.push_back('\t');
+            append_u32(text, neighbours[e]);
+            text.push_back('\t');
+            append_u32(text, dists[e]);
+            text.push_back('\n');
+        }
+        if (i + 1 == n || offsets[i + 1] / block != offsets[i] / block) {
+            rc = write_all(out_fd, text.data(), text.size());
+            if (rc) return rc;
+            text.clear();
+        }
+    }
+    log_line(1, "%llu neighbours of %llu sequences within %u, took %llu seconds", (unsigned long long)total, (unsigned long long)n,
+             max_divergence, (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_neighbours");
+}
+
 // ------------------------------------------------------------------------------------ cluster
 //
 // The reference handles one record at a time: skip exact duplicates, scan the record against the

@@ -12,6 +12,8 @@
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
 //           and the weight of every subject)
+//   neighbours -d/--database FILE  --max-divergence INT  [--max-num-hits INT]   (this build only: per subject its neighbours
+//           within the bound, nearest first)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -60,7 +62,11 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        clusters of the database's own sequences, one \"i<TAB>label<TAB>parent<TAB>weight\" line per sequence; weight = 1 +\n"
             "        the number of other sequences within the radius (default 0: the number of exact copies); parent = the heaviest\n"
             "        sequence within the bound, ties to the smaller number, the sequence itself if none outranks it (a peak);\n"
-            "        label = the peak reached by following the parents)\n");
+            "        label = the peak reached by following the parents)\n"
+            "neighbours -d, --database <FILE>  --max-divergence <INT>  [--max-num-hits <INT>]  [--device <N>]  (not in the reference: the\n"
+            "        neighbour lists of the database's own sequences, one \"i<TAB>j<TAB>divergence\" line per sequence i and neighbour j\n"
+            "        within the bound, both directions of every pair, ordered by i, then divergence, then j; --max-num-hits: at most\n"
+            "        that many lines per i, the nearest, ties to the smaller j)\n");
     return 2;
 }
 
@@ -215,6 +221,11 @@ int main(int argc, char **argv) {
         if (!database) return usage("peaks needs --database");
         if (!have_max_div) return usage("peaks needs --max-divergence");
         rc = smafa_peaks(database, max_div, radius, 1, (int)device);
+    } else if (cmd == "neighbours") {
+        if (!database) return usage("neighbours needs --database");
+        if (!have_max_div) return usage("neighbours needs --max-divergence");
+        if (max_hits == 0) return usage("--max-num-hits needs a positive integer");
+        rc = smafa_neighbours(database, max_div, max_hits, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);

@@ -1,5 +1,6 @@
 // self_join.hip.h — host code of the self-join of a resident store: one driver that walks the store and knows no consumer
-// (join_pass), and the five calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks).
+// (join_pass), and the six calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks,
+// join_neighbours).
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
 #pragma once
 
@@ -11,7 +12,8 @@ struct JoinCall {
     bool inverted = false;  // this call launched inverse_order_kernel
     double *slot = nullptr;      // the timed pass whose events are not read yet: the J.*_ms it is booked to ...
     const char *what = nullptr;  // ... and its level-3 trace text (nullptr: none)
-    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned
+    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned; neighbours: the
+                                       // entry total likewise
 };
 
 // a piece's finished list: rows (record of the piece, subject, distance) of block records p0 + b + S * k, k < R
@@ -527,6 +529,175 @@ static int join_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t 
              "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s", n, max_div, radius, J.blocks + J.rescans,
              J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
              J.jump_rounds == 1 ? "" : "s");
+    return SMAFA_OK;
+}
+// ---- the entry list of the neighbours call (neighbours.hip.h): two entries per kept pair, 8 B each — and 4 B more, the rows,
+// in a second list behind them where the order takes two sorts (apart)
+static uint32_t *entry_rows(const smafa_db *db) { return reinterpret_cast<uint32_t *>(db->join.entries.as<unsigned long long>() + db->join.entries_cap); }
+
+// Room in J.entries for `want` entries; the first `live` are carried over.  Grown as grow_kept grows J.kept — doubling, a bare
+// hipMalloc — but a list that cannot grow has no second join to fall back on: the call fails, and the handle stays usable.
+static int grow_entries(smafa_db *db, uint64_t want, uint64_t live, bool apart) {
+    auto &J = db->join;
+    if (want <= J.entries_cap) return SMAFA_OK;
+    const size_t each = apart ? 12u : 8u;
+    const uint64_t room = std::max<uint64_t>(want, J.entries_cap * 2);
+    DevBuf bigger;
+    if (hipMalloc(&bigger.p, room * each) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(SMAFA_ERR_NOMEM, "neighbours: no memory for a list of %llu entries (%llu bytes)", (unsigned long long)room,
+                         (unsigned long long)(room * each));
+    }
+    bigger.cap = room * each;
+    hipError_t e = hipSuccess;
+    if (live) e = hipMemcpyAsync(bigger.p, J.entries.p, live * 8u, hipMemcpyDeviceToDevice, db->stream);
+    if (live && apart && e == hipSuccess)
+        e = hipMemcpyAsync(bigger.as<unsigned long long>() + room, entry_rows(db), live * 4u, hipMemcpyDeviceToDevice, db->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
+    if (e != hipSuccess) {
+        bigger.release();
+        return set_error(SMAFA_ERR_DEVICE, "neighbours: moving the entry list failed: %s", hipGetErrorString(e));
+    }
+    J.entries.release();
+    J.entries = bigger;
+    J.entries_cap = room;
+    J.growths++;
+    return SMAFA_OK;
+}
+
+constexpr unsigned long long kSortItemsMax = 0x7fffffffull;  // the device radix sort counts its items in an int
+
+// smafa_db_self_neighbours_launch (neighbours.hip.h): d_offsets is n + 1 offsets, d_neighbours and d_dists (or nullptr) cap
+// entries each, d_total one counter.  The join runs at min(max_div, seq_len) — also where no two rows can exceed the bound: the
+// distances still differ — with mirror_pack_kernel per piece (the exactly-once rule, so pos_of[]), which appends both directions
+// of every kept pair to J.entries; in front of every piece's pass the list gets room for two entries per row of the piece's
+// list on top of the total read back in front of the piece's wait.  Behind the join: the sort (neighbour_key_rule: one sort of
+// the entries as keys, or two stable sorts with the rows apart), row_bounds_kernel, with a cut cut_degrees_kernel and an
+// exclusive sum, the total — with a cut read back, the one wait the cut costs — and, where it fits cap, emit_kernel.  No entry
+// at all: the offsets are zeroed and nothing else runs.
+// k: SMAFA_NONE = no cut
+static int join_neighbours(smafa_db *db, uint32_t max_div, uint32_t k, unsigned long long *d_offsets, uint32_t *d_neighbours,
+                           uint32_t *d_dists, uint64_t cap, unsigned long long *d_total) {
+    auto &J = db->join;
+    JoinCall c{db};
+    RC_TRY(join_begin(c, d_total, 1, 2));
+    const size_t offsets_bytes = (size_t)(db->n + 1) * sizeof(unsigned long long);
+    if (c.nothing) {  // no row, or one: {0}, or {0, 0}
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, db->stream));
+        return SMAFA_OK;
+    }
+    const uint32_t n = (uint32_t)db->n, scan_div = std::min(max_div, db->L);
+    const bool cut = k != SMAFA_NONE;
+    NeighbourKey key = neighbour_key_rule(n, max_div, db->L);
+    if (db->neighbour_two_sorts) key.sorts = 2u;
+    const bool apart = key.sorts == 2u;
+    const uint32_t shift = apart ? 0u : 32u + key.dist_bits;
+    const dim3 bounds_grid((uint32_t)(((uint64_t)n + 256u) / 256u));  // n + 1 threads
+    // The buffer is kept across calls, its division is not: a call with the rows apart places them behind entries_cap 8-byte
+    // entries, so a buffer that an earlier call filled at 8 B per entry serves this one at cap / 12 entries, and the other way round.
+    J.entries_cap = J.entries.cap / (apart ? 12u : 8u);
+    J.growths = 0;
+    RC_TRY(J.ctl.ensure(2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
+    RC_TRY(join_positions(c));
+    JoinConsumer pack = timed_consumer(c, &J.filter_ms, "neighbours: a piece's rows mirrored and packed", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_nb::mirror_pack_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, J.pos_of.as<uint32_t>(), shift, J.entries.as<unsigned long long>(), apart ? entry_rows(db) : (uint32_t *)nullptr,
+                           (unsigned long long)J.entries_cap, J.ctl.as<unsigned long long>());
+    });
+    pack.before_wait = [&c] {
+        smafa_db *db = c.db;
+        unsigned long long &seen = c.kept_seen;
+        HIP_TRY(hipMemcpyAsync(&seen, db->join.ctl.p, sizeof seen, hipMemcpyDeviceToHost, db->stream));
+        return SMAFA_OK;
+    };
+    const auto too_many = [](unsigned long long entries) {
+        return set_error(SMAFA_ERR_NOMEM, "neighbours: %llu entries before the cut, the device sort orders at most %llu", entries, kSortItemsMax);
+    };
+    pack.take = [&, timed = pack.take](const JoinPiece &p) {
+        if (c.kept_seen > kSortItemsMax) return too_many(c.kept_seen);  // (exact so far, and it only grows)
+        RC_TRY(grow_entries(db, c.kept_seen + 2 * p.count, c.kept_seen, apart));
+        return timed(p);
+    };
+    RC_TRY(join_pass(c, scan_div, pack));
+    unsigned long long entries = 0, total = 0;
+    HIP_TRY(hipMemcpyAsync(&entries, J.ctl.p, sizeof entries, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    if (entries > kSortItemsMax) return too_many(entries);
+    const unsigned long long *sorted = nullptr, *lower = d_offsets;
+    const uint32_t *rows = nullptr;
+    if (entries) {
+        // ---- the order
+        const int count = (int)entries, low_bits = (int)(32u + key.dist_bits), row_bits = (int)key.row_bits;
+        unsigned long long *const list = J.entries.as<unsigned long long>();
+        RC_TRY(db->keys_a.ensure(entries * sizeof(unsigned long long)));
+        unsigned long long *const ka = db->keys_a.as<unsigned long long>();
+        size_t tmp_bytes = 0, tmp_second = 0;
+        if (!apart) {
+            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, list, ka, count, 0, low_bits + row_bits, db->stream));
+            RC_TRY(db->sort_tmp.ensure(tmp_bytes));
+            RC_TRY(timed_begin(c, &J.count_ms, "neighbours: entries sorted as keys"));
+            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(db->sort_tmp.p, tmp_bytes, list, ka, count, 0, low_bits + row_bits, db->stream));
+            sorted = ka;
+        } else {
+            RC_TRY(db->keys_b.ensure(entries * sizeof(unsigned long long)));
+            RC_TRY(db->idx_a.ensure(entries * sizeof(uint32_t)));
+            RC_TRY(db->idx_b.ensure(entries * sizeof(uint32_t)));
+            unsigned long long *const kb = db->keys_b.as<unsigned long long>();
+            uint32_t *const ra = db->idx_a.as<uint32_t>(), *const rb = db->idx_b.as<uint32_t>();
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, list, ka, entry_rows(db), ra, count, 0, low_bits, db->stream));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_second, ra, rb, ka, kb, count, 0, row_bits, db->stream));
+            tmp_bytes = std::max(tmp_bytes, tmp_second);
+            RC_TRY(db->sort_tmp.ensure(tmp_bytes));
+            RC_TRY(timed_begin(c, &J.count_ms, "neighbours: entries sorted by (dist, neighbour), then by row"));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(db->sort_tmp.p, tmp_bytes, list, ka, entry_rows(db), ra, count, 0, low_bits, db->stream));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(db->sort_tmp.p, tmp_bytes, ra, rb, ka, kb, count, 0, row_bits, db->stream));
+            sorted = kb, rows = rb;
+        }
+        RC_TRY(timed_end(c, key.sorts));
+        RC_TRY(timed_sync(c));
+        // ---- where the rows begin, the cut, the total
+        if (cut) {
+            RC_TRY(J.parent.ensure(((size_t)n + 1u) * 2u * sizeof(unsigned long long)));
+            unsigned long long *const lo = J.parent.as<unsigned long long>(), *const deg = lo + ((size_t)n + 1u);
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, deg, d_offsets, (uint64_t)n + 1u, db->stream));
+            RC_TRY(db->sort_tmp.ensure(tmp_bytes));
+            RC_TRY(timed_begin(c, &J.link_ms, "neighbours: rows bounded, degrees cut and summed"));
+            hipLaunchKernelGGL(smafa_nb::row_bounds_kernel, bounds_grid, dim3(256), 0, db->stream, sorted, rows, shift, entries, n, lo);
+            hipLaunchKernelGGL(smafa_nb::cut_degrees_kernel, bounds_grid, dim3(256), 0, db->stream, lo, n, k, deg);
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(db->sort_tmp.p, tmp_bytes, deg, d_offsets, (uint64_t)n + 1u, db->stream));
+            lower = lo;
+        } else {
+            RC_TRY(timed_begin(c, &J.link_ms, "neighbours: rows bounded"));
+            hipLaunchKernelGGL(smafa_nb::row_bounds_kernel, bounds_grid, dim3(256), 0, db->stream, sorted, rows, shift, entries, n, d_offsets);
+        }
+        HIP_TRY(hipMemcpyAsync(d_total, d_offsets + n, sizeof total, hipMemcpyDeviceToDevice, db->stream));
+        RC_TRY(timed_end(c, cut ? 3u : 1u));
+        total = entries;
+        if (cut) HIP_TRY(hipMemcpyAsync(&total, d_offsets + n, sizeof total, hipMemcpyDeviceToHost, db->stream));
+        RC_TRY(timed_sync(c));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, db->stream));
+    }
+    const bool fits = total <= cap;
+    if (entries && fits) {
+        RC_TRY(timed_pass(c, &J.flatten_ms, "neighbours: entries emitted", [&] {
+            hipLaunchKernelGGL(smafa_nb::emit_kernel, list_grid(entries), dim3(256), 0, db->stream, sorted, rows, shift, entries, lower,
+                               d_offsets, k, (unsigned long long)cap, d_neighbours, d_dists);
+        }));
+        RC_TRY(timed_sync(c));
+    }
+    join_finish(c);
+    if (pack.used) note_call_kernel(db, "smafa_nb::mirror_pack_kernel");
+    if (entries) note_call_kernel(db, "smafa_nb::row_bounds_kernel");
+    if (entries && cut) note_call_kernel(db, "smafa_nb::cut_degrees_kernel");
+    if (entries && fits) note_call_kernel(db, "smafa_nb::emit_kernel");
+    log_line(2, "neighbours of %u rows at bound %u, cut %s: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, pack %.3f ms, "
+             "sort %.3f ms (%u sort%s), bounds %.3f ms, emit %.3f ms, %llu entries, %llu listed, %u growths", n, max_div, cut ? std::to_string(k).c_str() : "none",
+             J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.filter_ms, J.count_ms, entries ? key.sorts : 0u,
+             entries && key.sorts == 1u ? "" : "s", J.link_ms, J.flatten_ms, entries, total, J.growths);
+    if (!fits)
+        return set_error(SMAFA_ERR_CAPACITY, "neighbour lists too small: %llu entries needed, capacity %llu", total, (unsigned long long)cap);
     return SMAFA_OK;
 }
 #undef RC_TRY
