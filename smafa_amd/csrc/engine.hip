@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "scan_plan.h"
 #include "host/packed.h"
 #include "kernels.hip.h"
 #include "index.hip.h"
@@ -105,11 +106,7 @@ struct smafa_db {
     struct EachKey { const void *qs, *qrec, *hits, *counts; uint64_t qs_serial, cap, nq, generation; uint32_t max_div, qb; int zone; bool filter; } each_key{};
     std::vector<std::string> each_kernels;  // ... and the instantiations its capture launched (a replay names them again)
     uint32_t qb_override = 0;
-    bool use_filter = true;  // exact lower-bound prefilter in the scan kernel (SMAFA_FILTER=0 disables)
-    uint32_t tiles_override = 0;  // SMAFA_TILES
-    bool lazy = true;             // filter-plane-resident kernel where it applies (SMAFA_LAZY=0 disables)
-    bool wide_one = true;         // one-word stores (L <= 32) through scan_wide_kernel's two-plane level 2 (SMAFA_WIDE_ONE=0: lazy kernel)
-    uint32_t wide_from = 5;       // words per plane from which scan_wide_kernel replaces the per-length kernels (SMAFA_WIDE_FROM)
+    ScanKnobs knobs;  // the switches the kernel choice of a scan launch reads (scan_plan.h)
     // what the last launch used (smafa_last_scan_plan)
     uint32_t plan_lazy = 0, plan_tiles = 1, plan_qblocks = 1;
     char plan_kernel[96] = "";  // the instantiation of the last launch, as rocprofv3 names it (smafa_last_scan_kernel)
@@ -135,30 +132,23 @@ struct smafa_db {
     std::vector<Run> runs;        // the appends the store consists of (each sorted within itself or not); kept in the packed file
     // What the zone level can prune with, MEASURED: shared filter bits per wave tile (both words), read back after every
     // append; hist[b] = tiles sharing b bits.  Sorting gives ~log2(rows / 256) on unrelated sequences, related ones share
-    // more, many small appends share few — use_zone() works from this, not from assumptions about the data.
+    // more, many small appends share few — zone_pays() works from this, not from assumptions about the data.
     std::vector<uint8_t> tile_bits;
     uint64_t zone_hist[65] = {0};
     uint64_t rows_since_sort = 0;  // rows appended since the whole store was last in one sorted run
     uint32_t resorts = 0;          // full re-sorts so far (resort_store)
     bool resort = true;            // SMAFA_RESORT=0: never
-    double prune_p = 2e-3;         // prefilter_prunes: largest level-1 pass probability per subject (SMAFA_PRUNE_P)
     uint64_t resort_min = 32768;   // stores below this many rows are left alone (SMAFA_RESORT_MIN)
-    double zone_loose = 0.3;      // pass share below which the zone kernel also takes bounds level 1 cannot prune at (SMAFA_ZONE_LOOSE)
-    int zone = 1;                 // zone level of the filter-plane-resident kernel: 1 = where it prunes (use_zone), 0 = never
-                                  // (SMAFA_ZONE=0), 2 = whenever that kernel runs (SMAFA_ZONE=2, tests)
     bool sort_rows = true;        // sort big appends by their filter words (SMAFA_SORT=0: keep the append order)
     smafa_qset scratch_q;     // query set of smafa_scan_hits / smafa_distances
     smafa_qset scratch_q2;    // the compacted batch of queries the near-hit probe did not finish
     smafa_qset scratch_q3;    // the sample of open queries the later steps of the ladder are planned from
     smafa_qset join_q;        // the self-join's block of store rows as query records (store_records_kernel)
     bool two_phase = true;    // near-hit probe before the tightening path (SMAFA_TWO_PHASE=0 disables)
-    bool fold3 = true;        // scan_kernel's all-planes-but-the-last bound for launches whose bound starts above 32 (SMAFA_FOLD3=0)
     bool stream_nt = true;    // one-query-block launches of scan_lazy_kernel load their filter words non-temporally (SMAFA_STREAM_NT=0)
     uint32_t count_first_k = 3;  // smallest k whose loose-bound scans count first and append second (SMAFA_COUNT_FIRST_K)
     bool ladder_probe = true;    // the ladder's first step is asked of a 256-query sample before the whole batch pays for it (SMAFA_LADDER_PROBE=0)
-    bool zone_direct = true;     // fixed-bound zone launches without LDS staging and barriers (SMAFA_ZONE_DIRECT=0: the staged form)
     int zone_key_gate = -1;      // ScanArgs::key_gate (SMAFA_ZONE_KEY_GATE; 65: no key test); -1: by alphabet (kernels.hip.h)
-    bool lazy_fold = true;       // the filter-plane-resident kernel also at the bounds only its level 2 rejects at (SMAFA_LAZY_FOLD=0)
     bool kth_hist_seed = true;   // k >= 2: the seed bound from an LDS histogram over the first tiles (SMAFA_KTH_HIST_SEED=0: a counting launch)
     uint32_t kth_sample_min_tiles = 4096;  // stores below this many wave tiles (1M subjects) count everything first (SMAFA_KTH_SAMPLE_MIN_TILES)
     uint32_t kth_sample_div = 32;  // ... counting only the first 1/32 of the tiles, the rest counted and appended in one pass (SMAFA_KTH_SAMPLE=0: count everything first)
@@ -233,6 +223,7 @@ struct smafa_db {
     bool neighbour_two_sorts = false;  // neighbours: the two-sort order also where one key would hold an entry (SMAFA_NEIGHBOUR_SORT=2, tests)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
+    ScanShape shape() const { return {P, PQ, W, L}; }
     uint64_t hits_cap() const { return hits.cap / sizeof(smafa_hit); }
 };
 
@@ -526,263 +517,89 @@ static void note_kernel(const smafa_db *db, const char *fmt, ...) {
     note_call_kernel(db, db->plan_kernel);
 }
 
-template <int PS, int PQ, int W, int T>
-static void launch_lazy_t(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid) {
-    const bool seed = a.hits == nullptr && a.k_tight == 1;
-    // two words per plane, bound 13..17: level 2 sums the filter plane's per-word popcounts (the OR-fold rejects nothing there)
-    const bool sumfold = W == 2 && !seed && a.thr0 > 12u && a.thr0 <= 17u;  // (fold_rejects sends bounds up to 14 here)
-    note_kernel(db, "smafa::scan_lazy_kernel<%d, %d, %d, %d, %s, %s>", PS, PQ, W, T, seed ? "true" : "false", sumfold ? "true" : "false");
+template <int N>
+using ic = std::integral_constant<int, N>;
+
+// The twelve (PS, PQ, W) shapes the per-shape kernels are instantiated for: fn(ic<PS>, ic<PQ>, ic<W>) for the store's shape, and
+// what it returns; false without a call where the store has no such shape (more than four words per plane).
+template <class F>
+static bool for_shape(const ScanShape &s, F &&fn) {
+    auto by_words = [&](auto ps, auto pq) {
+        return s.W == 1 ? fn(ps, pq, ic<1>{}) : s.W == 2 ? fn(ps, pq, ic<2>{}) : s.W == 3 ? fn(ps, pq, ic<3>{}) : s.W == 4 && fn(ps, pq, ic<4>{});
+    };
+    if (s.P == 2 && s.PQ == 3) return by_words(ic<2>{}, ic<3>{});
+    if (s.P == 3 && s.PQ == 3) return by_words(ic<3>{}, ic<3>{});
+    return s.P == 5 && s.PQ == 5 && by_words(ic<5>{}, ic<5>{});
+}
+
+// Launch the plan's instantiation.  Every choice was made by plan_scan (scan_plan.h); the branches below only spell the
+// instantiations the binary holds — tests/test_kernel_census.py counts them, so a guard that is too wide fails there.
+// false: the plan names an instantiation that does not exist.
+static bool launch_scan(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid, const ScanPlan &plan) {
     const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
-    if (seed)
-        hipLaunchKernelGGL((scan_lazy_kernel<PS, PQ, W, T, true>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else if (W == 2 && sumfold)
-        hipLaunchKernelGGL((scan_lazy_kernel<PS, PQ, W, T, false, W == 2>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else
-        hipLaunchKernelGGL((scan_lazy_kernel<PS, PQ, W, T, false>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-}
-
-// sorted store: the zone level in front (scan_zone_kernel; up to 64 queries per launch: scan_zone_few_kernel)
-template <int PS, int PQ, int W>
-static void launch_zone_t(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid) {
-    const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
-    if (a.q_end - a.q_begin <= 64u) {
-        note_kernel(db, "smafa::scan_zone_few_kernel<%d, %d, %d>", PS, PQ, W);
-        hipLaunchKernelGGL((scan_zone_few_kernel<PS, PQ, W>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-        return;
+    auto go = [&](auto kernel, int block, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, db->stream, planes, d_qrec, a, more...);
+        return true;
+    };
+    const bool seed = plan.seed;
+    if (plan.family == ScanFamily::generic) return go(scan_generic_kernel, 256, db->P, db->PQ, db->W, db->QS);
+    if (plan.family == ScanFamily::wide) {  // above 128 columns, or up to 32 (SMAFA_WIDE_FROM=3: from 65); one instantiation per plane pair
+        auto wide = [&](auto ps, auto pq, auto fw, auto wc) {
+            constexpr int PS = decltype(ps)::value, PQ = decltype(pq)::value, FW = decltype(fw)::value, WC = decltype(wc)::value;
+            return plan.fw == (uint32_t)FW && plan.wc == (uint32_t)WC &&
+                   (seed ? go(scan_wide_kernel<PS, PQ, true, FW, WC>, 256, db->W) : go(scan_wide_kernel<PS, PQ, false, FW, WC>, 256, db->W));
+        };
+        auto planes_of = [&](auto ps, auto pq) {
+            return wide(ps, pq, ic<1>{}, ic<0>{}) || wide(ps, pq, ic<3>{}, ic<0>{}) || wide(ps, pq, ic<3>{}, ic<3>{}) || wide(ps, pq, ic<3>{}, ic<4>{});
+        };
+        return db->P == 2 ? planes_of(ic<2>{}, ic<3>{}) : db->P == 3 ? planes_of(ic<3>{}, ic<3>{}) : planes_of(ic<5>{}, ic<5>{});
     }
-    const bool fixed = a.thr == nullptr;  // one bound for every query: LDS-DMA staging, scalar bound
-    const bool direct = fixed && db->zone_direct && a.hits != nullptr;  // ... or no staging at all (SMAFA_ZONE_DIRECT)
-    note_kernel(db, "smafa::scan_zone_kernel<%d, %d, %d, %s, %s>", PS, PQ, W, fixed ? "true" : "false", direct ? "true" : "false");
-    if (direct)
-        hipLaunchKernelGGL((scan_zone_kernel<PS, PQ, W, true, true>), dim3(grid), dim3(kZoneWgWaves * 64), 0, db->stream, planes, d_qrec, a);
-    else if (fixed)
-        hipLaunchKernelGGL((scan_zone_kernel<PS, PQ, W, true>), dim3(grid), dim3(kZoneWgWaves * 64), 0, db->stream, planes, d_qrec, a);
-    else
-        hipLaunchKernelGGL((scan_zone_kernel<PS, PQ, W, false>), dim3(grid), dim3(kZoneWgWaves * 64), 0, db->stream, planes, d_qrec, a);
-}
-
-template <int PS, int PQ, int W, int T>
-static void launch_scan_t(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid) {
-    // the seed pass of the running-minimum mode (no append) has its own instantiation
-    const bool seed = a.hits == nullptr && a.k_tight == 1;
-    // Two words per plane: level 2 by the bound of the launch.  Up to 12 the OR-fold of the filter plane's words (one
-    // popcount per subject); 13..17 the filter plane's per-word popcounts summed (FOLD 1: the OR-fold rejects nothing
-    // there); 18..32, stores of 3 planes and more, the same over two planes (FOLD 2: flat 14.7 ms from 18 to 28 where the full
-    // comparison costs 31, 10 000 queries x 10M aa); beyond that nothing rejects.
-    int fold = 0;
-    if (SMAFA_SUM_FOLD && W == 2 && !seed && a.use_filter) {
-        if (a.thr0 > 12u && a.thr0 <= 17u) fold = 1;
-        else if (PS >= 3 && a.thr0 >= 18u && a.thr0 <= 32u) fold = 2;
-        else if (PS >= 4 && a.thr0 > 32u && db->fold3) fold = 3;  // all planes but the last (the k-th modes without a bound)
-        else if (PS == 3 && a.thr0 > 32u && db->fold3) fold = 2;  // three planes: "all but the last" IS the two-plane form
-    }
-    note_kernel(db, "smafa::scan_kernel<%d, %d, %d, %d, %s, %d>", PS, PQ, W, T, seed ? "true" : "false", fold);
-    const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
-    if (seed)
-        hipLaunchKernelGGL((scan_kernel<PS, PQ, W, T, true, 0>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else if (W == 2 && fold == 1)
-        hipLaunchKernelGGL((scan_kernel<PS, PQ, W, T, false, (W == 2 ? 1 : 0)>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else if (W == 2 && PS >= 3 && fold == 2)
-        hipLaunchKernelGGL((scan_kernel<PS, PQ, W, T, false, (W == 2 && PS >= 3 ? 2 : 0)>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else if (W == 2 && PS >= 4 && fold == 3)
-        hipLaunchKernelGGL((scan_kernel<PS, PQ, W, T, false, (W == 2 && PS >= 4 ? 3 : 0)>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-    else
-        hipLaunchKernelGGL((scan_kernel<PS, PQ, W, T, false, 0>), dim3(grid), dim3(256), 0, db->stream, planes, d_qrec, a);
-}
-
-// wave tiles per wave (4*T subjects per lane).  With the cheap first-level bound the per-query work that does
-// not depend on the subject count (LDS read, OR tree, compare, branches, loop bookkeeping) is what T amortises:
-// measured 2 beats 1 for every store with W <= 2 even where it costs occupancy (profiles/r01_variant_tiles*.txt).
-// SMAFA_TILES=1|2|4 overrides (4: 2-plane store only).
-// The filter-plane-resident kernel wins where the prefilter prunes (sparse hits: +18 % aa, 5x less HBM traffic)
-// and loses 10-100 % where it cannot (profiles/r01_lazy_vs_resident.txt, r01_length_probe.txt).  Chosen per launch
-// from the initial bound, so best-hit scans without --max-divergence (bound = L) and short sequences with a loose
-// bound keep the all-planes kernel.
-// Level 1 looks at cols = min(32, L) columns of one plane, where unrelated sequences differ in about half: a subject
-// passes it with probability P(Binomial(cols, 1/2) <= bound).  The filter-plane-resident kernels pay off while a
-// wave's 1024 subjects rarely produce a pass, i.e. while that tail stays below ~2e-3 — for cols = 32 this is
-// bound <= 7, the measured crossover (profiles/r01_lazy_vs_resident.txt); short sequences need a tighter bound
-// (cols = 20: bound <= 3; cols = 12: bound 0 — L = 12 with bound 2 ran 3x slower through these kernels).
-static bool prefilter_prunes(const smafa_db *db, uint32_t bound) {
-    const uint32_t cols = std::min<uint32_t>(32u, db->L);
-    if (bound >= cols) return false;
-    double term = 1.0, tail = 0.0;  // C(cols, k), summed for k = 0..bound
-    for (uint32_t k = 0; k <= bound; k++) {
-        tail += term;
-        term = term * (double)(cols - k) / (double)(k + 1);
-    }
-    for (uint32_t i = 0; i < cols; i++) tail *= 0.5;
-    return tail <= db->prune_p;
-}
-
-// Two words per plane: beyond the bounds level 1 prunes at, level 2 still rejects nearly every pair while the bound is well
-// below what unrelated sequences score on it — the OR of the two words' mismatch bits has ~3/4 of the second word's columns
-// set (+ half of the first word's columns that have no partner): bound <= half of that (L = 60: 12); then the per-word sums up
-// to 14 (SUMFOLD).  There the filter-plane-resident kernel — 16 subjects per lane, one plane streamed — beats the all-planes
-// one, which only ever uses its other planes for the pairs that pass: 10 000 queries x 10M aa, bound 8 / 9 / 10 / 12:
-// 8.7 / 9.5 / 8.9 / 9.6 -> 7.8 / 8.3 / 8.4 / 9.1 ms, bound 14: 12.2 -> 11.3 (tools/bound_probe.py, profiles/r04_bound_probe.txt).
-// SMAFA_LAZY_FOLD=0: off.
-static bool fold_rejects(const smafa_db *db, uint32_t bound) {
-    if (!db->lazy_fold || db->W != 2 || db->L < 56) return false;  // (measured at 60 columns; shorter second words: not claimed)
-    const uint32_t second = db->L - 32u;                                  // columns that have a partner in the other word
-    const uint32_t unrelated = (3u * second + 2u * (32u - second)) / 4u;  // expected popcount of the OR-fold (L = 60: 23)
-    // OR-fold up to 12, the per-word sums (SUMFOLD) at 13 and 14; from 15 on too many wave steps pass level 2 and fetch their
-    // tiles from L2 (bound 16: 18.1 ms against 13.8 for the all-planes kernel, whose tiles are resident)
-    return bound * 2u <= unrelated + 1u || bound <= 14u;
-}
-
-static bool use_lazy(const smafa_db *db, uint32_t thr0) {
-    const bool wide = db->W >= db->wide_from || (db->W == 1 && db->wide_one);
-    return db->lazy && db->use_filter && db->W <= 4 && !wide && (prefilter_prunes(db, thr0) || fold_rejects(db, thr0));
-}
-
-// More than four words per plane (L > 128): scan_wide_kernel under the same rule — its levels 1 and 2 are the lazy
-// kernel's, with 16 subjects per lane whatever the length.  One-word stores (L <= 32) take it too: its level 2
-// folds a second plane, which a single filter word needs (up to 1.8x on sparse hits, equal elsewhere).  At W = 3, 4
-// it is 8-25 % faster than the per-length kernels on sparse hits but 1.3-2x slower on dense or closely related
-// stores (tools/dense_check.py: their level 2 folds every filter word and their full comparison keeps the tile in
-// registers), so those lengths keep them; SMAFA_WIDE_FROM=3 switches them over (profiles/r01_wide_vs_lazy.txt).
-// Bound too loose, or prefilter off: scan_kernel (W <= 4) / scan_generic_kernel.
-static bool use_wide(const smafa_db *db, uint32_t thr0) {
-    const bool one = db->W == 1 && db->wide_one;
-    return db->lazy && db->use_filter && (db->W >= db->wide_from || one) && prefilter_prunes(db, thr0) &&
-           wide_fits((int)db->PQ, (int)db->W);
-}
-
-// P(Binomial(bits, 1/2) <= bound): how often `bits` shared filter bits of a tile fail to exclude a random query
-static double binom_tail(uint32_t bits, uint32_t bound) {
-    if (bound >= bits) return 1.0;
-    double term = 1.0, tail = 0.0;
-    for (uint32_t k = 0; k <= bound; k++) {
-        tail += term;
-        term = term * (double)(bits - k) / (double)(k + 1);
-    }
-    for (uint32_t i = 0; i < bits; i++) tail *= 0.5;
-    return tail;
-}
-
-// Does the zone level pay?  A tile that shares b filter bits lets a query unrelated to it through with probability
-// P(Binomial(b, 1/2) <= bound); the expected share of (query, tile) pairs that pass follows from the store's measured
-// shared-bit histogram (zone_hist).  Measured (tools/zone_threshold.sh, profiles/r02_zone_threshold.txt): the zone
-// kernel wins while that share stays below ~0.6 — 1M rows at bound 5 (~12 bits, 0.39): 0.51 vs 0.64 ms; 250k rows at
-// bound 5 (~10 bits, 0.62): 0.225 vs 0.208 ms; 10M rows at bound 7 (~15 bits, 0.50): 5.8 vs 6.5 ms.
-static double zone_pass_share(const smafa_db *db, uint32_t thr0) {
-    double tiles = 0.0, pass = 0.0;
-    for (uint32_t b = 0; b <= 64; b++) {
-        if (!db->zone_hist[b]) continue;
-        tiles += (double)db->zone_hist[b];
-        pass += (double)db->zone_hist[b] * binom_tail(b, thr0);
-    }
-    return tiles > 0.0 ? pass / tiles : 1.0;
-}
-
-// `prunes`: does level 1 (word 0 of the filter plane) prune at this bound (prefilter_prunes)?  Where it does not — short
-// sequences, loose bounds: every (query, tile) pair that passes the zone level goes on to the exact comparison — the
-// zone level has to exclude more on its own to beat the all-planes kernel: SMAFA_ZONE_LOOSE (default 0.3).
-static bool zone_pays(const smafa_db *db, uint32_t thr0, bool prunes) {
-    if (!db->lazy || !db->use_filter) return false;
-    if (db->zone != 1) return db->zone == 2;
-    // (five planes of four words: the survivors' levels 2-3 fetch 20 vectors per tile from L2 — the crossover comes
-    // earlier: aa 128 columns at bound 7, share 0.5: 11.7 ms vs 9.5 ms without the zone level; 80 columns: 6.6 vs 7.8)
-    const double pays = db->W <= 4 && db->P * db->W >= 20 ? 0.4 : 0.6;  // (scan_wide_kernel's own zone level: 0.6)
-    return zone_pass_share(db, thr0) < (prunes ? pays : db->zone_loose);
-}
-// up to 128 columns: scan_zone_kernel; longer: the zone level inside scan_wide_kernel (ScanArgs::zone_on)
-static bool use_zone(const smafa_db *db, uint32_t thr0, bool prunes) { return db->W <= 4 && zone_pays(db, thr0, prunes); }
-
-static uint32_t tiles_per_wave(const smafa_db *db, bool lazy, uint32_t thr0) {
-    if (lazy) return db->W >= 3 ? 2u : 4u;  // every filter word resident: 8 subjects per lane from 3 words on
-    if (db->W > 2) return 1;
-    if (db->tiles_override == 4) return db->P == 2 ? 4u : 2u;
-    if (db->tiles_override == 1 || db->tiles_override == 2) return db->tiles_override;
-    // Two tiles per wave share the per-query work of the bound levels between 8 subjects per lane — which pays while those
-    // levels reject most pairs.  Where (nearly) every pair gets the full comparison — prefilter off, or a bound above 16 with
-    // four and more planes (FOLD 2 / 3) — one tile per wave is faster: 80 registers less, more waves resident, and for a one-query
-    // pass shorter waves that keep the memory pipeline full.  10 000 x 10M aa: prefilter off 30.5 -> 25.4 ms, bound 24
-    // 15.0 -> 14.4 ms, best hit without a bound 23.1 -> 21.8 ms, bound 8 the other way (8.3 -> 9.6 ms: stays at two); one query
-    // streaming every plane of the 10M store: 70.3 -> 58.4 us = 0.72 -> 0.86 of HBM peak (profiles/r03_stream_nt.txt).
-    // (nucleotide stores the same way, less to gain: best hit without a bound, half the queries unrelated, 13.6 -> 12.8 ms)
-    if (!db->use_filter || thr0 > 16u) return 1u;
-    return 2u;
-}
-
-template <int PS, int PQ>
-static void launch_wide_t(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid) {
-    const bool seed = a.hits == nullptr && a.k_tight == 1;
-    const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
-    // resident filter words per subject: 1 = one-word store (plus word 0 of a second plane), else 3 (a fourth
-    // pushes the kernel past 128 VGPRs: measured spills, and one wave per SIMD less)
-    const uint32_t fw = db->W == 1 ? 1u : 3u;
-    const uint32_t wc = (db->W == 3 || db->W == 4) ? db->W : 0u;  // compile-time word count: register-resident dense walk
-#define SMAFA_WIDE(FW_, WC_)                                                                                     \
-    if (fw == FW_ && wc == WC_) {                                                                               \
-        note_kernel(db, "smafa::scan_wide_kernel<%d, %d, %s, %d, %d>", PS, PQ, seed ? "true" : "false", FW_, WC_);    \
-        if (a.zone_on) { /* (the call's list names the zone-level form as a marker of its own, after the template-id) */ \
-            const std::string id = db->plan_kernel;                                                             \
-            note_kernel(db, "%s (zone level on)", id.c_str());                                                  \
-        }                                                                                                       \
-        if (seed)                                                                                               \
-            hipLaunchKernelGGL((scan_wide_kernel<PS, PQ, true, FW_, WC_>), dim3(grid), dim3(256), 0, db->stream, \
-                               planes, d_qrec, a, db->W);                                                       \
-        else                                                                                                    \
-            hipLaunchKernelGGL((scan_wide_kernel<PS, PQ, false, FW_, WC_>), dim3(grid), dim3(256), 0, db->stream, \
-                               planes, d_qrec, a, db->W);                                                       \
-        return;                                                                                                 \
-    }
-    SMAFA_WIDE(1, 0) SMAFA_WIDE(3, 0) SMAFA_WIDE(3, 3) SMAFA_WIDE(3, 4)
-#undef SMAFA_WIDE
-}
-
-static void launch_scan(const smafa_db *db, const uint32_t *d_qrec, const ScanArgs &a, uint32_t grid, uint32_t T,
-                        bool lazy, bool zone) {
-    if (lazy && !zone && (db->W >= db->wide_from || (db->W == 1 && db->wide_one))) {  // above 64 columns, or up to 32
-        if (db->P == 2) return launch_wide_t<2, 3>(db, d_qrec, a, grid);
-        if (db->P == 3) return launch_wide_t<3, 3>(db, d_qrec, a, grid);
-        return launch_wide_t<5, 5>(db, d_qrec, a, grid);
-    }
-    if (lazy && zone) {  // sorted store, bound the zone level prunes at
-#define SMAFA_ZONE(PS_, PQ_, W_)                                 \
-    if (db->P == PS_ && db->PQ == PQ_ && db->W == W_) {          \
-        launch_zone_t<PS_, PQ_, W_>(db, d_qrec, a, grid);        \
-        return;                                                  \
-    }
-        SMAFA_ZONE(2, 3, 1) SMAFA_ZONE(3, 3, 1) SMAFA_ZONE(5, 5, 1) SMAFA_ZONE(2, 3, 2) SMAFA_ZONE(3, 3, 2) SMAFA_ZONE(5, 5, 2)
-        SMAFA_ZONE(2, 3, 3) SMAFA_ZONE(3, 3, 3) SMAFA_ZONE(5, 5, 3) SMAFA_ZONE(2, 3, 4) SMAFA_ZONE(3, 3, 4) SMAFA_ZONE(5, 5, 4)
-#undef SMAFA_ZONE
-    }
-    if (lazy) {  // filter-plane-resident kernel
-#define SMAFA_LAZY(PS_, PQ_, W_, T_)                                  \
-    if (db->P == PS_ && db->PQ == PQ_ && db->W == W_ && T == T_) {    \
-        launch_lazy_t<PS_, PQ_, W_, T_>(db, d_qrec, a, grid);         \
-        return;                                                       \
-    }
-        SMAFA_LAZY(2, 3, 2, 4) SMAFA_LAZY(3, 3, 2, 4) SMAFA_LAZY(5, 5, 2, 4)
-        SMAFA_LAZY(2, 3, 1, 4) SMAFA_LAZY(3, 3, 1, 4) SMAFA_LAZY(5, 5, 1, 4)
-        SMAFA_LAZY(2, 3, 3, 2) SMAFA_LAZY(3, 3, 3, 2) SMAFA_LAZY(5, 5, 3, 2)
-        SMAFA_LAZY(2, 3, 4, 2) SMAFA_LAZY(3, 3, 4, 2) SMAFA_LAZY(5, 5, 4, 2)
-#undef SMAFA_LAZY
-    }
-#define SMAFA_CASE(PS_, PQ_, W_, T_)                          \
-    if (db->P == PS_ && db->PQ == PQ_ && db->W == W_ && T == T_) { \
-        launch_scan_t<PS_, PQ_, W_, T_>(db, d_qrec, a, grid); \
-        return;                                               \
-    }
-    SMAFA_CASE(2, 3, 1, 1) SMAFA_CASE(2, 3, 2, 1) SMAFA_CASE(2, 3, 3, 1) SMAFA_CASE(2, 3, 4, 1)
-    SMAFA_CASE(3, 3, 1, 1) SMAFA_CASE(3, 3, 2, 1) SMAFA_CASE(3, 3, 3, 1) SMAFA_CASE(3, 3, 4, 1)
-    SMAFA_CASE(5, 5, 1, 1) SMAFA_CASE(5, 5, 2, 1) SMAFA_CASE(5, 5, 3, 1) SMAFA_CASE(5, 5, 4, 1)
-    SMAFA_CASE(2, 3, 1, 2) SMAFA_CASE(2, 3, 2, 2) SMAFA_CASE(3, 3, 1, 2) SMAFA_CASE(3, 3, 2, 2)
-    SMAFA_CASE(5, 5, 1, 2) SMAFA_CASE(5, 5, 2, 2)
-    SMAFA_CASE(2, 3, 1, 4) SMAFA_CASE(2, 3, 2, 4)
-#undef SMAFA_CASE
-    note_kernel(db, "smafa::scan_generic_kernel");
-    hipLaunchKernelGGL(scan_generic_kernel, dim3(grid), dim3(256), 0, db->stream,
-                       reinterpret_cast<const uint4 *>(db->d_planes), d_qrec, a, db->P, db->PQ, db->W, db->QS);
-}
-
-// queries per workgroup pass (query_block_size, engine.h); whole_chunks: the launch walks its block in chunks of kChunk queries
-// (the zone kernel with more than 64 queries)
-static uint32_t choose_query_block(const smafa_db *db, uint32_t n_wg_tiles, uint32_t nq, bool whole_chunks) {
-    return query_block_size(db->qb_override, (uint32_t)db->n_cu, n_wg_tiles, nq, whole_chunks ? (uint32_t)kChunk : 1u);
+    return for_shape(db->shape(), [&](auto ps, auto pq, auto w) {
+        constexpr int PS = decltype(ps)::value, PQ = decltype(pq)::value, W = decltype(w)::value;
+        switch (plan.family) {
+        case ScanFamily::zone_few:
+            return go(scan_zone_few_kernel<PS, PQ, W>, 256);
+        case ScanFamily::zone:
+            return plan.direct  ? go(scan_zone_kernel<PS, PQ, W, true, true>, kZoneWgWaves * 64)
+                   : plan.fixed ? go(scan_zone_kernel<PS, PQ, W, true, false>, kZoneWgWaves * 64)
+                                : go(scan_zone_kernel<PS, PQ, W, false, false>, kZoneWgWaves * 64);
+        case ScanFamily::lazy: {
+            constexpr int T = W <= 2 ? 4 : 2;  // the only tile count of this shape
+            if (plan.T != (uint32_t)T) return false;
+            if (seed) return go(scan_lazy_kernel<PS, PQ, W, T, true, false>, 256);
+            if constexpr (W == 2) {  // SUMFOLD exists for two words per plane
+                if (plan.sumfold) return go(scan_lazy_kernel<PS, PQ, W, T, false, true>, 256);
+            }
+            return go(scan_lazy_kernel<PS, PQ, W, T, false, false>, 256);
+        }
+        case ScanFamily::scan: {
+            auto tiles = [&](auto t) {  // FOLD 1 to 3 exist for two words per plane, 2 from three planes on, 3 from four
+                constexpr int T = decltype(t)::value;
+                if (seed) return go(scan_kernel<PS, PQ, W, T, true, 0>, 256);
+                if constexpr (W == 2) {
+                    if (plan.fold == 1) return go(scan_kernel<PS, PQ, W, T, false, 1>, 256);
+                    if constexpr (PS >= 3) {
+                        if (plan.fold == 2) return go(scan_kernel<PS, PQ, W, T, false, 2>, 256);
+                    }
+                    if constexpr (PS >= 4) {
+                        if (plan.fold == 3) return go(scan_kernel<PS, PQ, W, T, false, 3>, 256);
+                    }
+                }
+                return plan.fold == 0 && go(scan_kernel<PS, PQ, W, T, false, 0>, 256);
+            };
+            if (plan.T == 1) return tiles(ic<1>{});  // one tile per wave everywhere, two up to two words, four for two planes of those
+            if constexpr (W <= 2) {
+                if (plan.T == 2) return tiles(ic<2>{});
+                if constexpr (PS == 2) {
+                    if (plan.T == 4) return tiles(ic<4>{});
+                }
+            }
+            return false;
+        }
+        default:
+            return false;
+        }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -897,14 +714,17 @@ static int index_build(smafa_db *db, uint32_t blocks) {
 static double index_cand_limit(const smafa_db *db, uint32_t thr0) {
     double per_subject = db->index_cand_per_subject;
     if (per_subject < 0.0) {
-        const bool prunes = prefilter_prunes(db, thr0);
+        const ScanShape shape = db->shape();
+        const bool prunes = prefilter_prunes(shape, db->knobs, thr0);
         // (two-word amino-acid stores: the zone kernel's key test cuts its time per pass-share to ~0.3 of that, 2.4e-14 —
         // 10M x 10k bound 5: 1.69 -> 0.56 ms, profiles/r05_zone_keys.txt, -> 0.50 ms with the key work hoisted per chunk,
         // profiles/r06_zone_hoist.txt; nucleotides at bound 3: 2.69 -> 2.54 ms, kept at 8e-14)
         const double zone_s = db->W == 2 && db->alphabet == SMAFA_ALPHABET_AA ? 2.4e-14 : 8e-14;
-        const double scan_s = db->W <= 4 && use_zone(db, thr0, prunes) ? zone_s * std::min(1.0, std::max(0.02, zone_pass_share(db, thr0)))
-                              : fold_rejects(db, thr0) || prunes        ? 8e-14
-                                                                        : 1.2e-13;
+        // (up to 128 columns: scan_zone_kernel; longer stores have the zone level inside scan_wide_kernel, not counted here)
+        const bool zone = db->W <= 4 && zone_pays(shape, db->knobs, thr0, prunes, {db->zone_hist});
+        const double scan_s = zone ? zone_s * std::min(1.0, std::max(0.02, zone_pass_share(db->zone_hist, thr0)))
+                              : fold_rejects(shape, db->knobs, thr0) || prunes ? 8e-14
+                                                                               : 1.2e-13;
         per_subject = 0.45 * scan_s / 0.025e-9;
     }
     return std::max(16.0, per_subject * (double)db->n);
@@ -914,7 +734,7 @@ static double index_cand_limit(const smafa_db *db, uint32_t thr0) {
 // ones (longest run within index_max_run), the ones with the fewest expected candidates.
 static bool index_plan(const smafa_db *db, uint32_t thr0, uint32_t nq, uint8_t *probe_block) {
     const auto &ix = db->index;
-    if (!db->index_mode || !db->use_filter || !index_current(db) || nq <= 64u || thr0 + 1u > ix.B) return false;
+    if (!db->index_mode || !db->knobs.use_filter || !index_current(db) || nq <= 64u || thr0 + 1u > ix.B) return false;
     uint8_t usable[kIndexMaxBlocks];
     uint32_t nu = 0;
     for (uint32_t b = 0; b < ix.B; b++)
@@ -967,16 +787,12 @@ static int index_probe(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t 
         x.q_end = qe;
         const uint64_t groups = (uint64_t)(qe - qb) * x.n_probes;
         const uint64_t grid = (groups * kIndexGroup + kIndexWg - 1u) / kIndexWg;
-        bool launched = false;
-#define SMAFA_PROBE(PS_, PQ_, W_)                                                                                             \
-    if (!launched && db->P == PS_ && db->PQ == PQ_ && db->W == W_) {                                                          \
-        hipLaunchKernelGGL((index_probe_kernel<PS_, PQ_, W_>), dim3((uint32_t)grid), dim3(kIndexWg), 0, db->stream, db->d_planes, qrec, x, a); \
-        note_kernel(db, "smafa::index_probe_kernel<%d, %d, %d>", PS_, PQ_, W_);                                               \
-        launched = true;                                                                                                      \
-    }
-        SMAFA_PROBE(2, 3, 1) SMAFA_PROBE(3, 3, 1) SMAFA_PROBE(5, 5, 1) SMAFA_PROBE(2, 3, 2) SMAFA_PROBE(3, 3, 2) SMAFA_PROBE(5, 5, 2)
-        SMAFA_PROBE(2, 3, 3) SMAFA_PROBE(3, 3, 3) SMAFA_PROBE(5, 5, 3) SMAFA_PROBE(2, 3, 4) SMAFA_PROBE(3, 3, 4) SMAFA_PROBE(5, 5, 4)
-#undef SMAFA_PROBE
+        const bool launched = for_shape(db->shape(), [&](auto ps, auto pq, auto w) {
+            constexpr int PS = decltype(ps)::value, PQ = decltype(pq)::value, W = decltype(w)::value;
+            hipLaunchKernelGGL((index_probe_kernel<PS, PQ, W>), dim3((uint32_t)grid), dim3(kIndexWg), 0, db->stream, db->d_planes, qrec, x, a);
+            note_kernel(db, "smafa::index_probe_kernel<%d, %d, %d>", PS, PQ, W);
+            return true;
+        });
         if (!launched) return set_error(SMAFA_ERR_INVALID, "no index probe for %u/%u planes x %u words", db->P, db->PQ, db->W);
         HIP_TRY(hipGetLastError());
         db->last_launches++;
@@ -996,36 +812,28 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
                         uint32_t tile_end, uint32_t k_tight, uint32_t thr0, smafa_hit *d_rows, uint64_t rows_cap,
                         unsigned long long *publish, bool per_query_bounds = false, unsigned long long *own_counter = nullptr) {
     ScanArgs a;
-    const bool specialised = db->W <= 4;  // else scan_wide_kernel / scan_generic_kernel
-    const bool wide = use_wide(db, thr0);
-    bool lazy = wide || (specialised && use_lazy(db, thr0));
-    const bool seed = d_rows == nullptr && k_tight == 1;  // the seed pass covers a few tiles: no zone level
-    // a sorted store whose tiles share enough bits takes the zone kernel at any length up to 128 columns — also where
-    // scan_wide_kernel would otherwise run (one-word stores)
-    const bool zone = specialised && !seed && use_zone(db, thr0, prefilter_prunes(db, thr0));
-    lazy = lazy || zone;  // (the plan reported by smafa_last_scan_plan: a filter-plane-resident kernel)
-    // (the unstaged form of the zone kernel — launch_zone_t's `direct` — has its own tile count per shape)
-    const bool zone_is_direct = !(k_tight || per_query_bounds) && db->zone_direct && d_rows != nullptr;
-    const uint32_t T = zone ? (q_end - q_begin <= 64u ? (uint32_t)kFewTiles : (uint32_t)zone_tiles((int)db->P, (int)db->W, zone_is_direct))
-                     : wide ? (uint32_t)kWideTiles : specialised ? tiles_per_wave(db, lazy, thr0) : (uint32_t)kGenericTiles;
+    const uint32_t nq = q_end - q_begin, n_tiles = tile_end - tile_begin;
+    const bool per_query = k_tight || per_query_bounds;
+    // which kernel, how many tiles per wave and waves per workgroup: decided once, in scan_plan.h
+    const ScanPlan plan = plan_scan(db->shape(), db->knobs, {thr0, nq, d_rows == nullptr && k_tight == 1, d_rows != nullptr, per_query, {db->zone_hist}});
+    const uint32_t T = plan.T;
     a.tile_begin = tile_begin;
     a.tile_end = tile_end;
-    const uint32_t wg_waves = (zone && q_end - q_begin > 64u) ? (uint32_t)kZoneWgWaves : (uint32_t)kWgWaves;
-    a.n_wg_tiles = (tile_end - tile_begin + wg_waves * T - 1) / (wg_waves * T);
+    a.n_wg_tiles = (n_tiles + plan.wg_waves * T - 1) / (plan.wg_waves * T);
     a.n_subjects = (uint32_t)db->n;
     a.q_begin = q_begin;
     a.q_end = q_end;
-    // (the block size is chosen per 4-wave share of the store whatever the workgroup size, so that it does not change
-    // with kZoneWgWaves: profiles/r02_zone_variants.txt)
-    a.qb_size = choose_query_block(db, (tile_end - tile_begin + kWgWaves * T - 1) / (kWgWaves * T), q_end - q_begin,
-                                   zone && q_end - q_begin > 64u);
+    // queries per workgroup pass (query_block_size, engine.h).  (The block size is chosen per 4-wave share of the store whatever
+    // the workgroup size, so that it does not change with kZoneWgWaves: profiles/r02_zone_variants.txt)
+    a.qb_size = query_block_size(db->qb_override, (uint32_t)db->n_cu, (n_tiles + kWgWaves * T - 1) / (kWgWaves * T), nq,
+                                 plan.whole_chunks ? (uint32_t)kChunk : 1u);
     // fixed common bound: no per-query array, no fill launch; per_query_bounds: fixed bounds read from thr
-    a.thr = (k_tight || per_query_bounds) ? qs->thr.as<uint32_t>() : nullptr;
+    a.thr = per_query ? qs->thr.as<uint32_t>() : nullptr;
     a.thr0 = thr0;
     a.cnt = qs->cnt.as<uint32_t>();
     a.cnt_stride = db->L + 1;
     a.k_tight = k_tight;
-    a.use_filter = db->use_filter ? 1u : 0u;
+    a.use_filter = db->knobs.use_filter ? 1u : 0u;
     a.hits = d_rows;
     a.cap = rows_cap;
     a.count = db->ctrs.as<unsigned long long>();
@@ -1038,7 +846,7 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
     }
     a.order = db->d_order;
     a.zone = db->d_zone;
-    a.zone_on = (wide && !zone && !seed && db->W > 4 && zone_pays(db, thr0, true)) ? 1u : 0u;
+    a.zone_on = plan.zone_on ? 1u : 0u;
     // the key sets of scan_zone_kernel<.., DIRECT> (two-word stores): X and Z split filter word 1's L - 32 columns, KB each where
     // they fit (60 columns, KB = 12: X = columns 32..43, Z = 44..55); Y, word 0's last KB columns, is fixed
     {
@@ -1054,7 +862,7 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
     // non-temporal loads (scan_lazy_kernel's filter words, scan_kernel's tiles): where a cached copy is never read again — one
     // query block, or more bytes per query block than the 256 MiB Infinity Cache holds until the next one comes round
     // (bytes one query block reads: the filter plane's words for the filter-plane-resident kernels, whole tiles for scan_kernel)
-    const uint64_t range_bytes = (uint64_t)(tile_end - tile_begin) * (lazy ? db->W : db->P * db->W) * 1024u;
+    const uint64_t range_bytes = (uint64_t)n_tiles * (plan.reported_lazy ? db->W : db->P * db->W) * 1024u;
     a.stream_once = (db->stream_nt && (n_qblocks == 1 || range_bytes >= (256ull << 20))) ? 1u : 0u;
     const uint64_t grid = n_qblocks * a.n_wg_tiles;
     if (grid > 0x7fffffffull)
@@ -1064,8 +872,12 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
         db->launch_device = cur_dev;
         if (cur_dev != db->device) db->launches_off_device++;
     }
-    launch_scan(db, qs->qrec.as<uint32_t>(), a, (uint32_t)grid, T, lazy, zone);
-    db->plan_lazy = lazy ? 1u : 0u;
+    const std::string id = scan_kernel_name(plan, db->shape());
+    note_kernel(db, "%s", id.c_str());
+    // (the call's list names scan_wide_kernel's zone-level form as a marker of its own, after the template-id)
+    if (plan.zone_on) note_kernel(db, "%s (zone level on)", id.c_str());
+    if (!launch_scan(db, qs->qrec.as<uint32_t>(), a, (uint32_t)grid, plan)) return set_error(SMAFA_ERR_INVALID, "no kernel %s", id.c_str());
+    db->plan_lazy = plan.reported_lazy ? 1u : 0u;
     db->plan_tiles = T;
     db->plan_qblocks = (uint32_t)n_qblocks;
     HIP_TRY(hipGetLastError());
@@ -1103,7 +915,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
     if (k_tight == 0) {
         // A store with a current block index answers a tight fixed bound from it: bound + 1 probes per query instead of a
         // pass over every tile (index.hip.h).  Mode 2 builds the index the first time such a scan arrives.
-        if (db->index_mode >= 2 && db->use_filter && nq > 64u && db->W <= (uint32_t)kIndexMaxWords && thr0 + 1u <= std::min<uint32_t>(kIndexMaxBlocks, db->L) &&
+        if (db->index_mode >= 2 && db->knobs.use_filter && nq > 64u && db->W <= (uint32_t)kIndexMaxWords && thr0 + 1u <= std::min<uint32_t>(kIndexMaxBlocks, db->L) &&
             db->n >= db->index_min_rows && db->n < (1ull << 31) && (!index_current(db) || db->index.B < thr0 + 1u)) {
             bool build = db->index_mode == 2;
             if (!build) {
@@ -1152,7 +964,7 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
     // when the bound starts loose — of which the filter pass keeps the ones within the final bound: the scratch list
     // is sized for the appended volume, the caller's buffer only has to hold what is kept.
     // (k >= 2 with a loose bound counts first and appends only the final rows, straight into the caller's list.)
-    const bool count_first = k_tight >= db->count_first_k && !prefilter_prunes(db, thr0);
+    const bool count_first = k_tight >= db->count_first_k && !prefilter_prunes(db->shape(), db->knobs, thr0);
     // Counting first costs TWO passes over every pair (count, then append with the exact bounds).  On a big store the first
     // one is cut to a SAMPLE — the first 1/32 of the tiles: the k-th smallest distance within any subset of the subjects is an
     // upper bound of the k-th smallest over all of them — and the rest of the store is scanned ONCE, counting, tightening and
@@ -1213,22 +1025,15 @@ static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q
         const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
         const uint32_t *qrec = qs->qrec.as<uint32_t>();
         uint32_t *thr = qs->thr.as<uint32_t>();
-#define SMAFA_SEED(PS_, PQ_, W_)                                                                                              \
-    if (db->P == PS_ && db->PQ == PQ_ && db->W == W_) {                                                                       \
-        note_kernel(db, "smafa::kth_seed_kernel<%d, %d, %d>", PS_, PQ_, W_);                                                  \
-        note_counts();                                                                                                        \
-        hipLaunchKernelGGL((kth_seed_kernel<PS_, PQ_, W_>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ,    \
-                           db->W, tiles, (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt,      \
-                           (uint32_t)cnt_stride);                                                                             \
-        return;                                                                                                               \
-    }
-        SMAFA_SEED(2, 3, 1) SMAFA_SEED(3, 3, 1) SMAFA_SEED(5, 5, 1) SMAFA_SEED(2, 3, 2) SMAFA_SEED(3, 3, 2) SMAFA_SEED(5, 5, 2)
-        SMAFA_SEED(2, 3, 3) SMAFA_SEED(3, 3, 3) SMAFA_SEED(5, 5, 3) SMAFA_SEED(2, 3, 4) SMAFA_SEED(3, 3, 4) SMAFA_SEED(5, 5, 4)
-#undef SMAFA_SEED
-        note_kernel(db, "smafa::kth_seed_kernel<0, 0, 0>");
+        auto launch = [&](auto ps, auto pq, auto w) {
+            constexpr int PS = decltype(ps)::value, PQ = decltype(pq)::value, W = decltype(w)::value;
+            note_kernel(db, "smafa::kth_seed_kernel<%d, %d, %d>", PS, PQ, W);
+            hipLaunchKernelGGL((kth_seed_kernel<PS, PQ, W>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ, db->W, tiles,
+                               (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt, (uint32_t)cnt_stride);
+            return true;
+        };
+        if (!for_shape(db->shape(), launch)) launch(ic<0>{}, ic<0>{}, ic<0>{});  // more than four words per plane: the any-shape form
         note_counts();
-        hipLaunchKernelGGL((kth_seed_kernel<0, 0, 0>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ, db->W, tiles,
-                           (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt, (uint32_t)cnt_stride);
     };
     if (!rc && hist_sample) {
         launch_hist(sample_tiles, qs->cnt.as<uint32_t>());
@@ -1400,7 +1205,7 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
             if (!k_tight) break;
             k = k_tight;
             // counting first, the scan returns k rows per query plus ties: make room for them up front (up to 64M rows)
-            if (k >= db->count_first_k && !prefilter_prunes(db, std::min<uint32_t>(max_div, db->L))) {
+            if (k >= db->count_first_k && !prefilter_prunes(db->shape(), db->knobs, std::min<uint32_t>(max_div, db->L))) {
                 const uint64_t want = std::min<uint64_t>((uint64_t)(q_end - q_begin) * ((uint64_t)k + 64u), 1ull << 26);
                 if (db->hits_cap() < want) {
                     int erc = db->hits.ensure(want * sizeof(smafa_hit));
@@ -1517,7 +1322,7 @@ int scan_to_host(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, u
     // such calls have cost what an index for the ladder's first steps would, it is built — blocks as narrow as the store's size
     // leaves selective (~log2(n) - 2 bits of letters per block: 4 aa columns, 10 nucleotides at 10M subjects), so that it serves
     // the widest bounds it can (aa: up to 14).  Only where that index would take at least the ladder's first step.
-    if (db->index_mode == 3 && k_mode >= 1 && n_queries > 64 && db->use_filter && db->lazy && db->two_phase && !ladder.empty() &&
+    if (db->index_mode == 3 && k_mode >= 1 && n_queries > 64 && db->knobs.use_filter && db->knobs.lazy && db->two_phase && !ladder.empty() &&
         limit > ladder[0] && db->W <= (uint32_t)kIndexMaxWords && db->n >= db->index_min_rows && db->n < (1ull << 31) &&
         db->index_failed_generation != db->generation + 1u) {
         const double letter_bits = db->alphabet == SMAFA_ALPHABET_AA ? 4.3 : db->P == 2 ? 2.0 : 2.3;
@@ -1566,7 +1371,7 @@ int scan_to_host(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, u
         std::merge(done.begin(), done.end(), more.begin(), more.end(), all.begin(), hit_less);
         done.swap(all);
     };
-    const bool laddered = k_mode >= 1 && db->use_filter && db->lazy && db->two_phase && n_queries >= 16;
+    const bool laddered = k_mode >= 1 && db->knobs.use_filter && db->knobs.lazy && db->two_phase && n_queries >= 16;
     // Which LATER steps pay is estimated once, on a sample of the queries the first step left open: every (cur_n / 256)-th
     // open query is scanned in the k-th mode at the ladder's last bound, and the distribution of their k-th distances says
     // what share of the open queries each later step would finish.  A step costs about 0.37 (bounds the OR-fold still
@@ -1867,32 +1672,32 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     }
     db->W = (seq_len + 31) / 32;
     db->QS = (uint32_t)qrec_stride((int)db->PQ, (int)db->W);
-    if (const char *fv = getenv("SMAFA_FILTER")) db->use_filter = atoi(fv) != 0;
+    if (const char *fv = getenv("SMAFA_FILTER")) db->knobs.use_filter = atoi(fv) != 0;
     if (const char *tv = getenv("SMAFA_TILES")) {
         const int t = atoi(tv);
-        db->tiles_override = (t == 1 || t == 2 || t == 4) ? (uint32_t)t : 0u;
+        db->knobs.tiles_override = (t == 1 || t == 2 || t == 4) ? (uint32_t)t : 0u;
     }
-    if (const char *lv = getenv("SMAFA_LAZY")) db->lazy = atoi(lv) != 0;
+    if (const char *lv = getenv("SMAFA_LAZY")) db->knobs.lazy = atoi(lv) != 0;
     if (const char *pv2 = getenv("SMAFA_TWO_PHASE")) db->two_phase = atoi(pv2) != 0;
-    if (const char *f3 = getenv("SMAFA_FOLD3")) db->fold3 = atoi(f3) != 0;
+    if (const char *f3 = getenv("SMAFA_FOLD3")) db->knobs.fold3 = atoi(f3) != 0;
     if (const char *sn = getenv("SMAFA_STREAM_NT")) db->stream_nt = atoi(sn) != 0;
     if (const char *cv = getenv("SMAFA_COUNT_FIRST_K")) db->count_first_k = (uint32_t)std::max(2, atoi(cv));
     if (const char *lp = getenv("SMAFA_LADDER_PROBE")) db->ladder_probe = atoi(lp) != 0;
-    if (const char *zd = getenv("SMAFA_ZONE_DIRECT")) db->zone_direct = atoi(zd) != 0;
+    if (const char *zd = getenv("SMAFA_ZONE_DIRECT")) db->knobs.zone_direct = atoi(zd) != 0;
     if (const char *kg = getenv("SMAFA_ZONE_KEY_GATE")) db->zone_key_gate = std::min(65, std::max(0, atoi(kg)));
-    if (const char *lf = getenv("SMAFA_LAZY_FOLD")) db->lazy_fold = atoi(lf) != 0;
+    if (const char *lf = getenv("SMAFA_LAZY_FOLD")) db->knobs.lazy_fold = atoi(lf) != 0;
     if (const char *ks = getenv("SMAFA_KTH_HIST_SEED")) db->kth_hist_seed = atoi(ks) != 0;
     if (const char *ks = getenv("SMAFA_KTH_SAMPLE")) db->kth_sample_div = (uint32_t)std::max(0, atoi(ks));
     if (const char *ks = getenv("SMAFA_KTH_SAMPLE_MIN_TILES")) db->kth_sample_min_tiles = (uint32_t)std::max(1, atoi(ks));
     if (const char *ks = getenv("SMAFA_KTH_GROUPS")) db->kth_groups = (uint32_t)std::max(0, atoi(ks));
-    if (const char *ov = getenv("SMAFA_WIDE_ONE")) db->wide_one = atoi(ov) != 0;
-    if (const char *wv = getenv("SMAFA_WIDE_FROM")) db->wide_from = (uint32_t)std::max(3, atoi(wv));
-    if (const char *zv = getenv("SMAFA_ZONE")) db->zone = std::min(2, std::max(0, atoi(zv)));
+    if (const char *ov = getenv("SMAFA_WIDE_ONE")) db->knobs.wide_one = atoi(ov) != 0;
+    if (const char *wv = getenv("SMAFA_WIDE_FROM")) db->knobs.wide_from = (uint32_t)std::max(3, atoi(wv));
+    if (const char *zv = getenv("SMAFA_ZONE")) db->knobs.zone = std::min(2, std::max(0, atoi(zv)));
     if (const char *sv = getenv("SMAFA_SORT")) db->sort_rows = atoi(sv) != 0;
     if (const char *sv = getenv("SMAFA_RESORT")) db->resort = atoi(sv) != 0;
-    if (const char *sv = getenv("SMAFA_PRUNE_P")) db->prune_p = atof(sv);
+    if (const char *sv = getenv("SMAFA_PRUNE_P")) db->knobs.prune_p = atof(sv);
     if (const char *sv = getenv("SMAFA_RESORT_MIN")) db->resort_min = std::max<uint64_t>(2, strtoull(sv, nullptr, 10));
-    if (const char *zl = getenv("SMAFA_ZONE_LOOSE")) db->zone_loose = atof(zl);
+    if (const char *zl = getenv("SMAFA_ZONE_LOOSE")) db->knobs.zone_loose = atof(zl);
     if (const char *iv = getenv("SMAFA_INDEX")) db->index_mode = std::min(3, std::max(0, atoi(iv)));
     if (const char *iv = getenv("SMAFA_INDEX_MAX_RUN")) db->index_max_run = std::max<uint64_t>(1, strtoull(iv, nullptr, 10));
     if (const char *iv = getenv("SMAFA_INDEX_CAND")) db->index_cand_per_subject = atof(iv);
@@ -2148,7 +1953,7 @@ const char *smafa_build_id(void) {
 
 int smafa_set_zone_level(smafa_db *db, int mode) try {
     if (!db || mode < 0 || mode > 2) return set_error(SMAFA_ERR_INVALID, "smafa_set_zone_level: bad argument");
-    db->zone = mode;
+    db->knobs.zone = mode;
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_set_zone_level");
@@ -2216,7 +2021,7 @@ int smafa_index_info(const smafa_db *db, smafa_index_info_t *info) try {
 
 int smafa_set_prefilter(smafa_db *db, int enabled) try {
     if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_set_prefilter: NULL handle");
-    db->use_filter = enabled != 0;
+    db->knobs.use_filter = enabled != 0;
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_set_prefilter");
@@ -2325,7 +2130,7 @@ int smafa_scan_each(smafa_db *db, smafa_qset *qs, uint32_t max_div, void *d_hits
     memset(&key, 0, sizeof key);  // (padding bytes take part in the comparison below)
     key.qs = qs, key.qrec = qs->qrec.p, key.qs_serial = qs->serial;
     key.hits = d_hits, key.counts = d_counts, key.cap = cap_per_query, key.nq = qs->nq, key.generation = db->generation;
-    key.max_div = max_div, key.qb = db->qb_override, key.zone = db->zone, key.filter = db->use_filter;
+    key.max_div = max_div, key.qb = db->qb_override, key.zone = db->knobs.zone, key.filter = db->knobs.use_filter;
     if (!db->each_graph || memcmp(&key, &db->each_key, sizeof key) != 0) {
         if (db->each_graph) (void)hipGraphExecDestroy(db->each_graph);
         db->each_graph = nullptr;

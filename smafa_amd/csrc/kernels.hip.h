@@ -41,12 +41,10 @@
 #include <stdint.h>
 
 #include "../../include/smafa_amd.h"
+#include "scan_plan.h"  // the geometry the host's kernel choice shares with the kernels: kWaveTile, kWgWaves, kChunk, tile counts
 
 namespace smafa {
 
-constexpr int kWaveTile = 256;  // subjects per wave tile
-constexpr int kWgWaves = 4;     // waves per workgroup
-constexpr int kChunk = 64;      // queries staged in LDS at a time
 constexpr int kStageRows = 256;  // rows a workgroup parks in LDS (per chunk parity) before ONE reservation in the row list
 // __launch_bounds__ second argument (waves per SIMD the register budget must allow) for the scan kernel:
 // the subject words held per lane plus ~40 working registers, mapped through the gfx950 allocation steps.
@@ -62,9 +60,6 @@ __host__ __device__ constexpr int scan_min_waves(int ps, int w, int t) {
                                // level 1 prunes at, where the form is the cheaper one (one-word stores, 10M x 20 aa, bound 3:
                                // 7.1 ms vs 8.6 ms per subject — profiles/r02_short_check.txt)
 #endif
-#ifndef SMAFA_SUM_FOLD
-#define SMAFA_SUM_FOLD 1  // scan_kernel<.., FOLD = 1 | 2 | 3> for two-word launches with a bound of 13..17 | 18..32 | above (engine.hip launch_scan_t)
-#endif
 #ifndef SMAFA_SIGN_COMPARE
 #define SMAFA_SIGN_COMPARE 1  // scan_kernel's full comparison: one sign test per query instead of a compare per subject
 #endif
@@ -75,9 +70,6 @@ __host__ __device__ constexpr int scan_min_waves(int ps, int w, int t) {
                           // queries x 10M aa, bound 10: 28.7 -> 8.4 ms (profiles/r02_bound_probe.txt)
 #endif
 
-__host__ __device__ constexpr int round_up4(int x) { return (x + 3) & ~3; }
-// query record stride in u32 words: the plane words plus the bound slot, rounded up to whole uint4s
-__host__ __device__ constexpr int qrec_stride(int planes, int words) { return round_up4(planes * words + 1); }
 // The plane the prefilter looks at: always plane 0.  Codes are re-coded PER COLUMN when a store is laid out (the
 // distance only depends on equality of codes within a column, so any per-column injective map keeps every result):
 // bit 0 of the re-coded symbol splits the column's letters into two sets of nearly equal total frequency, which makes
@@ -942,30 +934,7 @@ __device__ __forceinline__ void emit_direct(const ScanArgs &a, uint32_t q, uint3
     if (g < a.cap) a.hits[g] = h;
 }
 
-#ifndef SMAFA_ZONE_TILES
-#define SMAFA_ZONE_TILES 4
-#endif
 constexpr int kZoneTiles = SMAFA_ZONE_TILES;
-// ... per shape and form.  The UNSTAGED five-plane two-word kernel (60-column amino acids, fixed bound) takes 2 tiles per wave at
-// 7 waves per SIMD (72 VGPRs): without LDS staging and barriers there is little per-chunk work left to amortise over more tiles,
-// and every resident wave more hides more of the survivor loop's dependent slow-class chain.  Same box, ms per launch, 10M x 10k /
-// 50M x 125k (profiles/r04_zone_variants.txt): 5 waves x 4 tiles 1.795 / 53.5, 5 x 6 1.77 / 52.0, 6 x 3 1.71 / 50.6, 6 x 2 1.72 /
-// 51.5, **7 x 2 1.68 / 49.3**, 7 x 3 1.76 / 64.6 (spills), 8 x 2 1.78 / 78.4 (spills), 4 x 6 1.95, 6 x 4 2.01.  Nucleotides keep 4
-// tiles (3: 2.80, 6: 3.12 vs 2.70 ms).  SMAFA_ZONE_TILES != 4 overrides for every shape.
-#ifndef SMAFA_ZONE_TILES_DIRECT_AA
-#define SMAFA_ZONE_TILES_DIRECT_AA 2  // tiles per wave of the unstaged five-plane two-word kernel alone (nucleotide shapes keep theirs)
-#endif
-__host__ __device__ constexpr int zone_tiles(int ps, int w, bool direct) {
-    return SMAFA_ZONE_TILES != 4 ? SMAFA_ZONE_TILES : (direct && ps == 5 && w == 2 ? SMAFA_ZONE_TILES_DIRECT_AA : 4);
-}
-#ifndef SMAFA_ZONE_WG_WAVES
-#define SMAFA_ZONE_WG_WAVES 2
-#endif
-constexpr int kZoneWgWaves = SMAFA_ZONE_WG_WAVES;
-#ifndef SMAFA_FEW_TILES
-#define SMAFA_FEW_TILES 4
-#endif
-constexpr int kFewTiles = SMAFA_FEW_TILES;  // wave tiles per wave in scan_zone_few_kernel
 
 // Waves per SIMD the register budget must allow.  The survivor loop is a chain of dependent slow-class instructions
 // (v_readlane -> scalar-operand xor -> bcnt -> or -> cmp -> branch), so one more resident wave pays as long as the hot
@@ -1789,11 +1758,8 @@ __global__ __launch_bounds__(256) void scan_zone_few_kernel(const uint4 *__restr
 // the second register word of a subject is word 0 of ANOTHER plane and level 2 bounds the two-plane fold — a
 // mismatch in either plane is a mismatching column, so it is still a lower bound on the distance.
 // ---------------------------------------------------------------------------------------------
-constexpr int kWideTiles = 4;
-constexpr int kWideStage = 768;  // uint4 per LDS buffer
 // queries per tile load on the dense path: 4 * group distances live in registers next to the tile's planes
 __host__ __device__ constexpr int wide_group(int ps) { return ps >= 5 ? 4 : ps == 3 ? 6 : 8; }
-__host__ __device__ constexpr bool wide_fits(int planes, int words) { return qrec_stride(planes, words) / 4 <= kWideStage; }
 
 template <int PS, int PQ, bool SEED, int FW, int WC>
 __global__ __launch_bounds__(256, 4) void scan_wide_kernel(const uint4 *__restrict__ planes,
@@ -2188,8 +2154,6 @@ __global__ __launch_bounds__(256, 4) void scan_wide_kernel(const uint4 *__restri
 // of the prefilter plane of its 16 subjects (4 wave tiles) in registers and applies the level-1 bound of the
 // specialised kernels (exact: popcount over the first 32 columns of one plane <= distance); only for queries
 // that survive it are the subjects' words re-read from L2/HBM, plane by plane, for the full comparison.
-constexpr int kGenericTiles = 4;
-
 __global__ __launch_bounds__(256) void scan_generic_kernel(const uint4 *__restrict__ planes,
                                                            const uint32_t *__restrict__ qrec, ScanArgs a, uint32_t PS,
                                                            uint32_t PQ, uint32_t W, uint32_t QS) {
@@ -2578,7 +2542,7 @@ __global__ __launch_bounds__(256) void zone_kernel(const uint4 *__restrict__ pla
     if (lane == 0) {
         uint4 z;
         // bits past the last column are zero in every subject and every query: they never mismatch, and counting them as
-        // shared would make the store look better sorted than it is (use_zone works from these words)
+        // shared would make the store look better sorted than it is (zone_pays works from these words)
         const uint32_t cols0 = L >= 32u ? 0xffffffffu : (1u << L) - 1u;
         const uint32_t cols1 = L >= 64u ? 0xffffffffu : L > 32u ? (1u << (L - 32u)) - 1u : 0u;
         z.y = ~(land[0] ^ lor[0]) & cols0;

@@ -10,6 +10,9 @@ prefilter, the zone level (0 off, 2 forced), whether a block index is built, `ma
 the template-id for one form of the kernel: "zone level on", "sample counts"), E — the bound its edge pairs are planted at
 (tests/kernel_edges.py) — and `spread` (fillers at distances 0..spread, so every step of the near-hit ladder finishes some).
 
+Which instantiation a launch runs is decided in smafa_amd/csrc/scan_plan.h (plan_scan, scan_kernel_name) and nowhere else;
+tests/test_scan_plan_model.py asks that header, compiled for the host, for the name of every fixed-bound case below.
+
 Every fixed-bound case here launches over the whole store (first tile 0).  The fixed-bound forms at a non-zero first tile — the
 self-join's triangular cut, for every word count and the wide, generic, zone and few-query kernels — are covered by the self-join
 shape tests (tests/test_gpu_self_join_shapes.py).

@@ -87,7 +87,7 @@ def test_every_engine_one_answer(name, monkeypatch):
     kind = kind_of(name)
     store = make_store(codes, kind)
     assert store.self_pairs(D, first_cap=1 << 20).tobytes() == want.tobytes()  # (room at once: the kernel list is this call's)
-    # (which scan kernel the default takes is the engine's measured rule, use_zone: at 20 020 rows and bound 5 the tiles share
+    # (which scan kernel the default takes is the engine's measured rule, zone_pays in scan_plan.h: at 20 020 rows and bound 5 the tiles share
     # too few filter bits for the zone level to pay and the filter-plane-resident kernel runs; the zone kernel is asserted by
     # name below at zone level 2, and as the default's own choice in test_default_takes_the_zone_kernel_where_it_pays)
     assert store.last_call_kernels()[0].startswith("smafa::scan_"), store.last_call_kernels()

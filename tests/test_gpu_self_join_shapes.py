@@ -73,7 +73,7 @@ def test_spans_off_the_tile_grid(name, monkeypatch):
 @pytest.mark.parametrize("name", ["aa200", "nt520"])
 def test_wide_and_generic_kernels_past_tile_0(name, bound, monkeypatch):
     """(c) more than four words per plane: scan_wide_kernel while level 1 of the prefilter prunes (bound 5), scan_generic_kernel
-    above (bound 20, members planted up to 10 columns from their seed; engine.hip use_wide — the rule
+    above (bound 20, members planted up to 10 columns from their seed; scan_plan.h plan_scan — the rule
     test_wide_lengths_all_modes_equal_oracle pins), each over spans past tile 0"""
     codes, want = shape_case(name, SPANS_FAMILIES, bound, LOOSE_SUBS if bound == LOOSE_BOUND else 4)
     set_spans(monkeypatch)

@@ -58,7 +58,7 @@ def _source(name):
 
 
 def test_the_restated_layout_is_the_headers():
-    k = _source("kernels.hip.h")
+    k = _source("scan_plan.h") + " " + _source("kernels.hip.h")  # (the strides and tile sizes the host shares: scan_plan.h)
     for text in (
         "constexpr int kWaveTile = %d;" % WAVE_TILE,
         "constexpr int round_up4(int x) { return (x + 3) & ~3; }",
