@@ -473,6 +473,49 @@ int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_
 int smafa_db_self_neighbours_launch(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, void *d_offsets /* n_subjects + 1 uint64 */, void *d_neighbours /* cap uint32, may be NULL if cap == 0 */, void *d_dists /* cap uint32 or NULL */, uint64_t cap, void *d_total /* uint64 */);
 int smafa_db_self_neighbours(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, uint64_t *offsets, uint32_t *neighbours, uint32_t *dists /* may be NULL */, uint64_t cap, uint64_t *n_out);
 
+/* ------------------------------------------------- delta self-join: pairs and components of the rows appended since a mark */
+/*
+ * "I appended m rows; which pairs are new, and what are the components now?" — without joining the whole store again.
+ * Subjects are numbered in append order and keep their numbers through every re-sort, so a mark is a subject number:
+ * first_row, 0 <= first_row <= n_subjects, and "the new rows" are first_row .. n_subjects - 1.  The work is m x n pair
+ * tests, not n x n / 2.
+ *
+ * Delta pairs (smafa_db_self_since_launch / smafa_db_self_hits_since): every unordered pair {i, j}, i < j, with
+ * j >= first_row and distance <= max_div, exactly once, as {query = i, subject = j, dist}.  The pairs of the store's first
+ * first_row rows and the delta pairs are disjoint, and together they are the pairs of the whole store.  first_row =
+ * n_subjects gives no rows; first_row = 0 the rows of smafa_db_self_hits.  Capacity as for smafa_db_self_hits: the count is
+ * exact at any capacity, SMAFA_ERR_CAPACITY names the rows needed, cap = 0 with a NULL list asks for the count alone.  The
+ * host form orders its rows by (query, dist, subject); the device form leaves them unordered.
+ *
+ * Components update (smafa_db_self_components_update_launch / smafa_db_self_components_update): labels[] holds n_subjects
+ * entries, in and out.  On entry labels[0 .. first_row) are the labels smafa_db_self_components gave for the store's first
+ * first_row rows at the same max_div; the entries from first_row on are ignored.  On return all n_subjects entries and
+ * *n_components are byte for byte what smafa_db_self_components(db, max_div) returns on the store as it is now.  What can be
+ * checked of the labels given is checked on the device — labels[i] <= i, labels[i] < first_row, labels[labels[i]] ==
+ * labels[i] — and a violation is SMAFA_ERR_INVALID with the number of bad entries in smafa_last_error(); labels[] is then
+ * untouched and the handle stays usable.  (Labels that pass these checks and still are not the labels of the first rows at
+ * this bound give labels of no meaning.)  first_row = 0 is the full call; first_row = n_subjects returns the labels as given
+ * and counts their representatives; max_div >= seq_len gives all labels 0.
+ *
+ * Not in the reference.  The new rows' query records are gathered from the sorted store on the device
+ * (smafa_dl::gather_records_kernel, through the position of every subject number), a span of them at a time, and every block
+ * of a span is scanned against the whole store by the scan kernels smafa_db_self_launch uses — or answered from a current
+ * block index.  The exactly-once rule needs no positions: a row {new row a, partner s} of a block's list is kept iff s < a
+ * (smafa_dl::delta_filter_kernel).  The update seeds the union-find of smafa_db_self_components with the labels given
+ * (smafa_dl::seed_parents_kernel) and links only the delta join's rows.  Scratch, SMAFA_JOIN_* settings and the one failure of
+ * the self-join (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list) are those of smafa_db_self_launch.
+ * SMAFA_ERR_INVALID, with the argument named in smafa_last_error(): a NULL handle, count or labels; a NULL row buffer with a
+ * capacity; max_div = SMAFA_NONE; first_row > n_subjects; cap < n_subjects (update).  Synchronisation of the device forms as
+ * for smafa_db_self_launch; d_labels = device buffer of n_subjects uint32, d_count / d_n_components = device uint64.
+ * smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of the gather, the scans and the consumer
+ * passes; smafa_last_call_kernels lists the scan-family instantiations first, then smafa_dl::gather_records_kernel, then
+ * smafa_join::inverse_order_kernel if it ran, then the call's own kernels.
+ */
+int smafa_db_self_since_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count);
+int smafa_db_self_hits_since(smafa_db *db, uint64_t first_row, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out);
+int smafa_db_self_components_update_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_labels, void *d_n_components);
+int smafa_db_self_components_update(smafa_db *db, uint64_t first_row, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -608,6 +651,10 @@ int smafa_cluster_multi(const char *input_fasta, uint32_t max_divergence, int ou
  * loaded on `device`, and every pair of its subjects within max_divergence (smafa_db_self_hits) is written to out_fd as
  * "{i}\t{j}\t{distance}\n", i < j, in (i, distance, j) order. */
 int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa pairs --since ROW` (not in the reference): the same DB, and the pairs whose larger subject number is >= first_row
+ * (smafa_db_self_hits_since) in the same format and order: exactly the lines of smafa_pairs with j >= first_row.  first_row
+ * above the number of subjects is SMAFA_ERR_INVALID. */
+int smafa_pairs_since(const char *db_path, uint64_t first_row, uint32_t max_divergence, int out_fd, int device);
 /* `smafa components` (not in the reference): the DB file (version 2 / 3 or a packed store file), loaded on `device` as for
  * smafa_pairs, and per subject its label (smafa_db_self_components: the smallest subject number of its single-linkage
  * component at max_divergence) as "{i}\t{label}\n", in subject order, to out_fd.  An empty DB writes nothing. */

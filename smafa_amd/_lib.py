@@ -38,6 +38,8 @@ EXPORTS = [
     "smafa_db_self_density_launch", "smafa_db_self_density", "smafa_density",
     "smafa_db_self_peaks_launch", "smafa_db_self_peaks", "smafa_peaks",
     "smafa_db_self_neighbours_launch", "smafa_db_self_neighbours", "smafa_neighbours",
+    "smafa_db_self_since_launch", "smafa_db_self_hits_since", "smafa_db_self_components_update_launch",
+    "smafa_db_self_components_update", "smafa_pairs_since",
     "smafa_makedb", "smafa_makedb_packed", "smafa_query", "smafa_query_multi", "smafa_cluster", "smafa_cluster_multi", "smafa_cluster_sharded", "smafa_count",
 ]
 
@@ -180,6 +182,11 @@ def lib() -> C.CDLL:
     l.smafa_peaks.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
     l.smafa_db_self_neighbours_launch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]
     l.smafa_db_self_neighbours.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
+    l.smafa_db_self_since_launch.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]
+    l.smafa_db_self_hits_since.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
+    l.smafa_db_self_components_update_launch.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
+    l.smafa_db_self_components_update.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
+    l.smafa_pairs_since.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int]
     l.smafa_neighbours.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
     l.smafa_count.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_int]
     _lib = l

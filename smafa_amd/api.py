@@ -232,6 +232,50 @@ class SubjectStore:
         check(lib().smafa_db_self_components_launch(self._h, _opt(max_divergence), C.c_void_p(d_labels) if d_labels else None,
                                                     C.c_void_p(d_n_components) if d_n_components else None))
 
+    # ---- delta self-join: the rows appended since a mark ------------------------------------
+    def self_pairs_since(self, first_row: int, max_divergence: int, first_cap: int = 1 << 16) -> np.ndarray:
+        """Every unordered pair within max_divergence whose larger subject number is >= first_row — the pairs that the rows
+        appended since the store had first_row rows have added — once, rows as self_pairs gives them, ordered (query, dist,
+        subject) — smafa_db_self_hits_since.  self_pairs of the first first_row rows and these rows are disjoint and together
+        self_pairs of the whole store."""
+        cap = max(int(first_cap), 0)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            n_out = C.c_uint64(0)
+            rc = lib().smafa_db_self_hits_since(self._h, int(first_row), _opt(max_divergence), out.ctypes.data, cap, C.byref(n_out))
+            if rc == _lib.ERR_CAPACITY:
+                cap = int(n_out.value)
+                continue
+            check(rc)
+            return out[: n_out.value]
+
+    def self_since_launch(self, first_row: int, max_divergence: int, d_hits: int, cap: int, d_count: int) -> None:
+        """device-resident form (smafa_db_self_since_launch): rows unordered in d_hits, the exact pair count in *d_count"""
+        check(lib().smafa_db_self_since_launch(self._h, int(first_row), _opt(max_divergence), C.c_void_p(d_hits) if d_hits else None, cap,
+                                               C.c_void_p(d_count) if d_count else None))
+
+    def self_components_update(self, first_row: int, max_divergence: int, labels) -> tuple[np.ndarray, int]:
+        """(labels, n_components) of the store as it is now, byte for byte those of self_components(max_divergence), from
+        `labels`, whose first first_row entries are what self_components(max_divergence) gave when the store had first_row
+        rows (entries behind them are ignored, and need not be there) — smafa_db_self_components_update: only the rows from
+        first_row on are joined against the store.  `labels` itself is not written."""
+        n = self.info().n_subjects
+        given = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        if len(given) < min(int(first_row), n):
+            raise ValueError("labels holds %d entries, first_row is %d" % (len(given), first_row))
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        out[: min(len(given), n)] = given[:n]
+        count = C.c_uint64(0)
+        check(lib().smafa_db_self_components_update(self._h, int(first_row), _opt(max_divergence), out.ctypes.data, n, C.byref(count)))
+        return out[:n], int(count.value)
+
+    def self_components_update_launch(self, first_row: int, max_divergence: int, d_labels: int, d_n_components: int) -> None:
+        """device-resident form (smafa_db_self_components_update_launch): n_subjects uint32 labels in d_labels, in and out,
+        the number of components in *d_n_components (device uint64)"""
+        check(lib().smafa_db_self_components_update_launch(self._h, int(first_row), _opt(max_divergence),
+                                                           C.c_void_p(d_labels) if d_labels else None,
+                                                           C.c_void_p(d_n_components) if d_n_components else None))
+
     # ---- single-linkage levels -------------------------------------------------------------
     def self_component_levels(self, max_divergence: int) -> tuple[np.ndarray, list[int]]:
         """(labels, counts): labels[t, i] = the label self_components(t) gives subject i, for every t = 0 .. max_divergence
@@ -600,6 +644,11 @@ def count(paths, out_fd: int = 1) -> None:
 def pairs(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
     """`smafa pairs`: every pair i < j of the DB file's own subjects within max_divergence, "i\\tj\\tdist" lines to out_fd."""
     check(lib().smafa_pairs(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def pairs_since(db_path: str, first_row: int, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa pairs --since ROW`: the lines of `pairs` whose larger subject number is >= first_row."""
+    check(lib().smafa_pairs_since(os.fsencode(db_path), int(first_row), _opt(max_divergence), out_fd, device))
 
 
 def components(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:

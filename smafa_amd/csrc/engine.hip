@@ -25,6 +25,7 @@
 #include "density.hip.h"
 #include "peaks.hip.h"
 #include "neighbours.hip.h"
+#include "delta.hip.h"
 
 namespace smafa {
 
@@ -214,6 +215,9 @@ struct smafa_db {
         DevBuf entries;
         uint64_t entries_cap = 0;  // entries the list has room for
         uint32_t growths = 0;      // how often the last call grew it
+        // delta join (delta.hip.h): the subject numbers of the new rows, 4 B each — the order[] of its pieces; ctl[0] counts the
+        // labels seed_parents_kernel refused
+        DevBuf rows;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1243,7 +1247,7 @@ static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_
 }
 
 // ---------------------------------------------------------------------------------------------
-#include "self_join.hip.h"  // the self-join: its driver and the six calls that consume its pieces
+#include "self_join.hip.h"  // the self-join: its two drivers and the calls that consume their pieces
 
 void db_life_stats(const smafa_db *db, double *kernel_ms, uint64_t *launches) {
     *kernel_ms = db ? db->life_ms : 0.0;
@@ -2266,21 +2270,18 @@ int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t 
     return smafa::exception_code("smafa_db_self_launch");
 }
 
-int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL handle");
-    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL count");
-    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL row buffer with a capacity");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: a self-join needs a bound (max_div)");
-    *n_out = 0;
+// The host form of a pair-list call: `join` fills J.out (room rows: cap, or all_pairs if that is less) and J.cnt on the device;
+// the count comes back, then — where it fits cap — the rows, ordered (query, dist, subject) on the device or the host.
+static int pairs_to_host(smafa_db *db, uint64_t all_pairs, smafa_hit *out, uint64_t cap, uint64_t *n_out,
+                         const std::function<int(smafa_hit *, uint64_t, unsigned long long *)> &join) {
     int rc = use_device(db);
     if (rc) return rc;
     auto &J = db->join;
-    const uint64_t all_pairs = db->n < 2 ? 0 : db->n * (db->n - 1) / 2;
     const uint64_t room = std::min<uint64_t>(cap, all_pairs);
     rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));
     if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
     if (rc) return rc;
-    rc = join_pairs(db, max_div, J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
+    rc = join(J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
     if (rc) return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
@@ -2306,6 +2307,18 @@ int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t 
         db->sort_tmp.release();
     }
     return SMAFA_OK;
+}
+
+int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL handle");
+    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL count");
+    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL row buffer with a capacity");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: a self-join needs a bound (max_div)");
+    *n_out = 0;
+    const uint64_t all_pairs = db->n < 2 ? 0 : db->n * (db->n - 1) / 2;
+    return pairs_to_host(db, all_pairs, out, cap, n_out, [&](smafa_hit *d_hits, uint64_t room, unsigned long long *d_count) {
+        return join_pairs(db, max_div, d_hits, room, d_count);
+    });
 } catch (...) {
     return smafa::exception_code("smafa_db_self_hits");
 }
@@ -2347,6 +2360,84 @@ int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, u
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_components");
+}
+
+int smafa_db_self_since_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL handle");
+    if (!d_count) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL count");
+    if (!d_hits && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL row buffer with a capacity");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: a self-join needs a bound (max_div)");
+    if (first_row > db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: first_row %llu, the store has %llu subjects",
+                         (unsigned long long)first_row, (unsigned long long)db->n);
+    return delta_pairs(db, (uint32_t)first_row, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_since_launch");
+}
+
+int smafa_db_self_hits_since(smafa_db *db, uint64_t first_row, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL handle");
+    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL count");
+    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL row buffer with a capacity");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: a self-join needs a bound (max_div)");
+    *n_out = 0;
+    if (first_row > db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: first_row %llu, the store has %llu subjects",
+                         (unsigned long long)first_row, (unsigned long long)db->n);
+    // pairs whose larger number is j: j of them, for every new row j
+    const uint64_t all_pairs = (db->n - first_row) * (db->n + first_row - (db->n > first_row ? 1 : 0)) / 2;
+    return pairs_to_host(db, all_pairs, out, cap, n_out, [&](smafa_hit *d_hits, uint64_t room, unsigned long long *d_count) {
+        return delta_pairs(db, (uint32_t)first_row, max_div, d_hits, room, d_count);
+    });
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_hits_since");
+}
+
+int smafa_db_self_components_update_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_labels, void *d_n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL handle");
+    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL labels");
+    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL count");
+    if (max_div == SMAFA_NONE)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: components need a bound (max_div)");
+    if (first_row > db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: first_row %llu, the store has %llu subjects",
+                         (unsigned long long)first_row, (unsigned long long)db->n);
+    return delta_components(db, (uint32_t)first_row, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_components_update_launch");
+}
+
+int smafa_db_self_components_update(smafa_db *db, uint64_t first_row, uint32_t max_div, uint32_t *labels, uint64_t cap,
+                                    uint64_t *n_components) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL handle");
+    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL labels");
+    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL count");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: components need a bound (max_div)");
+    *n_components = 0;
+    if (first_row > db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: first_row %llu, the store has %llu subjects",
+                         (unsigned long long)first_row, (unsigned long long)db->n);
+    if (cap < db->n)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: labels holds %llu entries, the store has %llu subjects",
+                         (unsigned long long)cap, (unsigned long long)db->n);
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    rc = J.out.ensure(std::max<uint64_t>(db->n, 1) * sizeof(uint32_t));  // the labels on their way in and out: 4 B per subject
+    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
+    if (rc) return rc;
+    if (first_row) HIP_TRY(hipMemcpyAsync(J.out.p, labels, first_row * sizeof(uint32_t), hipMemcpyHostToDevice, db->stream));
+    rc = delta_components(db, (uint32_t)first_row, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
+    if (rc) return rc;  // (labels[] is as it came)
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    *n_components = count;
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_components_update");
 }
 
 int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components) try {

@@ -622,19 +622,26 @@ static int load_db_store(const char *db_path, int device, DbGuard *store, bool *
 }
 
 // -------------------------------------------------------------------------------------- pairs
-// The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair.
-int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_pairs: a bound (max_divergence) is needed");
+// The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair — or, since a row
+// (smafa_db_self_hits_since), the pairs whose larger number is at least that row.
+static int print_pairs(const char *who, const char *db_path, bool since, uint64_t first_row, uint32_t max_divergence, int out_fd, int device) {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL path", who);
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: a bound (max_divergence) is needed", who);
     const double t_start = now_seconds();
     DbGuard store;
     bool empty = false;
     int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;  // (an empty DB has no pairs)
+    if (rc) return rc;
+    if (empty)  // (an empty DB has no pairs)
+        return since && first_row ? set_error(SMAFA_ERR_INVALID, "%s: first_row %llu, the store has 0 subjects", who, (unsigned long long)first_row)
+                                  : SMAFA_OK;
     std::vector<smafa_hit> pairs((size_t)1 << 16);
     uint64_t count = 0;
-    while ((rc = smafa_db_self_hits(store.db, max_divergence, pairs.data(), pairs.size(), &count)) == SMAFA_ERR_CAPACITY)
-        pairs.resize(count);
+    const auto join = [&] {
+        return since ? smafa_db_self_hits_since(store.db, first_row, max_divergence, pairs.data(), pairs.size(), &count)
+                     : smafa_db_self_hits(store.db, max_divergence, pairs.data(), pairs.size(), &count);
+    };
+    while ((rc = join()) == SMAFA_ERR_CAPACITY) pairs.resize(count);
     if (rc) return rc;
     std::string text;
     const size_t block = (size_t)1 << 18;  // rows per write
@@ -654,8 +661,18 @@ int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int de
     log_line(1, "%llu pairs within %u, took %llu seconds", (unsigned long long)count, max_divergence,
              (unsigned long long)(now_seconds() - t_start));
     return SMAFA_OK;
+}
+
+int smafa_pairs(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    return print_pairs("smafa_pairs", db_path, false, 0, max_divergence, out_fd, device);
 } catch (...) {
     return smafa::exception_code("smafa_pairs");
+}
+
+int smafa_pairs_since(const char *db_path, uint64_t first_row, uint32_t max_divergence, int out_fd, int device) try {
+    return print_pairs("smafa_pairs_since", db_path, true, first_row, max_divergence, out_fd, device);
+} catch (...) {
+    return smafa::exception_code("smafa_pairs_since");
 }
 
 // --------------------------------------------------------------------------------- components

@@ -5,7 +5,8 @@
 //           [--limit-per-sequence INT]
 //   cluster -i/--input FILE  -d/--max-divergence INT
 //   count   -i/--input FILE...
-//   pairs   -d/--database FILE  --max-divergence INT   (this build only: every pair of the DB's own subjects within the bound)
+//   pairs   -d/--database FILE  --max-divergence INT  [--since ROW]   (this build only: every pair of the DB's own subjects
+//           within the bound; --since: those whose larger sequence number is at least ROW)
 //   components -d/--database FILE  --max-divergence INT  [--levels]   (this build only: the single-linkage component of
 //           every subject; --levels: at every bound 0 .. INT)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
@@ -19,6 +20,7 @@
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
 // --alphabet nt|aa (makedb, cluster), --packed (makedb: the packed store file, host/packed.cpp).
 // Exit status: 0 ok, 101 where the reference panics (a Rust panic exits 101), 1 other failures, 2 usage.
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +52,7 @@ static int usage(const char *msg, FILE *to = stderr) {
             "count   -i, --input <FILE>...\n"
             "pairs   -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: every pair i < j of the\n"
             "        database's own sequences within the bound, one \"i<TAB>j<TAB>divergence\" line each)\n"
+            "        [--since <ROW>]: only the pairs with j >= ROW, the pairs that the sequences from number ROW on have added\n"
             "components -d, --database <FILE>  --max-divergence <INT>  [--levels] [--device <N>]  (not in the reference: single-linkage\n"
             "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
             "        smallest sequence number of its component; --levels: one label column per bound 0 .. <INT>,\n"
@@ -107,7 +110,8 @@ int main(int argc, char **argv) {
     const char *input = nullptr, *database = nullptr, *query = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0;
-    bool have_min_pts = false;
+    bool have_min_pts = false, have_since = false;
+    unsigned long long since = 0;
     bool have_max_div = false, packed = false, no_gpu = false, levels = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
@@ -146,6 +150,14 @@ int main(int argc, char **argv) {
             have_min_pts = true;
         } else if (a == "--radius" && cmd == "peaks") {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
+        } else if (a == "--since" && cmd == "pairs") {
+            const char *v = value();
+            char *end = nullptr;
+            if (!v || !*v || *v == '-' || *v == '+') return usage("--since needs an unsigned integer");
+            errno = 0;
+            since = strtoull(v, &end, 10);
+            if (*end || errno == ERANGE) return usage("--since needs an unsigned integer");
+            have_since = true;
         } else if (a == "--levels" && cmd == "components") {
             levels = true;
         } else if (a == "--no-gpu") {
@@ -207,7 +219,7 @@ int main(int argc, char **argv) {
     } else if (cmd == "pairs") {
         if (!database) return usage("pairs needs --database");
         if (!have_max_div) return usage("pairs needs --max-divergence");
-        rc = smafa_pairs(database, max_div, 1, (int)device);
+        rc = have_since ? smafa_pairs_since(database, since, max_div, 1, (int)device) : smafa_pairs(database, max_div, 1, (int)device);
     } else if (cmd == "components") {
         if (!database) return usage("components needs --database");
         if (!have_max_div) return usage("components needs --max-divergence");

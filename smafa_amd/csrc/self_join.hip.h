@@ -1,6 +1,7 @@
 // self_join.hip.h — host code of the self-join of a resident store: one driver that walks the store and knows no consumer
 // (join_pass), and the six calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks,
-// join_neighbours).
+// join_neighbours); and the driver of the delta join (delta_pass: the rows appended since a mark against the whole store), with
+// its two calls (delta_pairs, delta_components).  Both drivers scan their pieces through one loop, join_pieces.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
 #pragma once
 
@@ -10,6 +11,7 @@ struct JoinCall {
     bool no_scans = false;  // one row, or a bound no two rows can exceed: nothing to scan (a scan would list all n^2 pairs to learn "one set")
     bool nothing = false;   // join_begin: too few rows for any work, the zeroed counters are the result
     bool inverted = false;  // this call launched inverse_order_kernel
+    bool delta = false;     // a delta call: its records come from smafa_dl::gather_records_kernel
     double *slot = nullptr;      // the timed pass whose events are not read yet: the J.*_ms it is booked to ...
     const char *what = nullptr;  // ... and its level-3 trace text (nullptr: none)
     unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned; neighbours: the
@@ -126,18 +128,61 @@ static int join_positions(JoinCall &c) {
     return SMAFA_OK;
 }
 
+// The scans of one block: records [q0, q_end) of the set in db->join_q against the wave tiles from tile_begin on, into the
+// handle's scratch list, `piece` records per scan, each finished list handed to the consumer as `shape` with its list and
+// count filled in.  The host waits for each piece's scan to learn its row count, and join_piece_rule (engine.h) says what
+// follows: a piece that overflowed the scratch list is scanned again with the list grown to that count (exact at any
+// capacity; a truncated list never reaches a consumer), or cut in half once the list would pass join_scratch_max rows; the
+// reduced piece size is kept — by the caller, across its blocks — until a piece's count falls under a quarter of that
+// ceiling.  rec_timed: the time of the records' pass (ev[0]..ev[1]) has been booked; where: the block, for the level-3 trace.
+static int join_pieces(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer, uint64_t q0, const uint64_t q_end, uint64_t &piece,
+                       JoinPiece shape, uint32_t tile_begin, bool &rec_timed, const char *where) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    smafa_qset *qs = &db->join_q;
+    while (q0 < q_end) {
+        const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
+        RC_TRY(scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
+                        db->count.as<unsigned long long>(), tile_begin));
+        unsigned long long count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
+        if (consumer.before_wait) RC_TRY(consumer.before_wait());
+        RC_TRY(timed_sync(c));  // (with it ends the consumer's pass over the piece before)
+        const float before = db->call_ms;
+        note_call_scan(db);
+        const double scan_ms = db->call_ms - before;
+        J.scan_ms += scan_ms;
+        float ms = 0.f;
+        if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
+        rec_timed = true;
+        log_line(3, "self-join: %s, records %llu..%llu: %llu rows, scan %.3f ms", where, (unsigned long long)q0, (unsigned long long)q1,
+                 count, scan_ms);
+        const PieceRule rule = join_piece_rule(count, db->hits_cap(), db->join_scratch_max, q1 - q0, piece, db->join_block);
+        piece = rule.piece;
+        if (rule.verdict != kPieceTake) J.rescans++;
+        if (rule.verdict == kPieceFail)
+            // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
+            return set_error(SMAFA_ERR_NOMEM,
+                             "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
+                             "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
+        if (rule.verdict == kPieceGrow) RC_TRY(db->hits.ensure(count * sizeof(smafa_hit)));
+        if (rule.verdict != kPieceTake) continue;  // the same rows, or their first half, once more
+        shape.list = db->hits.as<smafa_hit>(), shape.count = count;
+        if (count) RC_TRY(consume(consumer, shape));
+        J.blocks++;
+        q0 = q1;
+    }
+    return SMAFA_OK;
+}
+
 // The driver: every pair of the store's rows within scan_div of each other, once or twice, as the lists of PIECES to `consumer`.
 // The store is walked in SPANS of join_stride x join_block consecutive positions.  A span's rows become query records on
 // the device (store_records_kernel), dealt round-robin into join_stride BLOCKS: block b holds the span's positions b,
 // b + S, b + 2S, ...  Per block the fixed-bound scan runs its records against the wave tiles from the span's first one to the
 // end of the store — tiles in front of the span could only repeat pairs an earlier span has found — into the handle's
-// scratch list, and the consumer's kernel reads that list behind the scan, on the same stream.
+// scratch list, and the consumer's kernel reads that list behind the scan, on the same stream (join_pieces).
 // Why interleaved: the store is sorted by filter bits, so a block of CONSECUTIVE positions is 65 536 rows whose surviving work
 // sits in a few workgroups (profiles/r07_self_join.txt, stride 1 against 16).
-// The host waits for each piece's scan to learn its row count, and join_piece_rule (engine.h) says what follows: a piece that
-// overflowed the scratch list is scanned again with the list grown to that count (exact at any capacity; a truncated list
-// never reaches a consumer), or cut in half once the list would pass join_scratch_max rows; the reduced piece size is kept
-// until a piece's count falls under a quarter of that ceiling.
 static int join_pass(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer) {
     smafa_db *db = c.db;
     auto &J = db->join;
@@ -168,37 +213,58 @@ static int join_pass(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer) {
         bool rec_timed = false;
         for (uint32_t b = 0; b < S; b++) {
             const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
-            for (uint64_t q0 = (uint64_t)b * R, q_end = q0 + rows_b; q0 < q_end;) {
-                const uint64_t q1 = std::min<uint64_t>(q_end, q0 + piece);
-                RC_TRY(scan_range(db, qs, (uint32_t)q0, (uint32_t)q1, scan_div, 0, db->hits.as<smafa_hit>(), db->hits_cap(),
-                                db->count.as<unsigned long long>(), t0));
-                unsigned long long count = 0;
-                HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-                if (consumer.before_wait) RC_TRY(consumer.before_wait());
-                RC_TRY(timed_sync(c));  // (with it ends the consumer's pass over the piece before)
-                const float before = db->call_ms;
-                note_call_scan(db);
-                const double scan_ms = db->call_ms - before;
-                J.scan_ms += scan_ms;
-                float ms = 0.f;
-                if (!rec_timed && hipEventElapsedTime(&ms, J.ev[0], J.ev[1]) == hipSuccess) J.rec_ms += ms;
-                rec_timed = true;
-                log_line(3, "self-join: span at %llu, block %u of %u, records %llu..%llu: %llu rows, scan %.3f ms", (unsigned long long)p0, b, S,
-                         (unsigned long long)q0, (unsigned long long)q1, count, scan_ms);
-                const PieceRule rule = join_piece_rule(count, db->hits_cap(), db->join_scratch_max, q1 - q0, piece, db->join_block);
-                piece = rule.piece;
-                if (rule.verdict != kPieceTake) J.rescans++;
-                if (rule.verdict == kPieceFail)
-                    // (not SMAFA_ERR_CAPACITY: that code tells the caller of smafa_db_self_hits to grow ITS buffer and call again)
-                    return set_error(SMAFA_ERR_NOMEM,
-                                     "self-join: %llu rows of the store have %llu rows within %u of them, more than the scratch list may "
-                                     "hold (%llu rows)", (unsigned long long)(q1 - q0), count, scan_div, (unsigned long long)db->join_scratch_max);
-                if (rule.verdict == kPieceGrow) RC_TRY(db->hits.ensure(count * sizeof(smafa_hit)));
-                if (rule.verdict != kPieceTake) continue;  // the same rows, or their first half, once more
-                if (count) RC_TRY(consume(consumer, {db->hits.as<smafa_hit>(), count, (uint32_t)p0, S, R, db->d_order}));
-                J.blocks++;
-                q0 = q1;
-            }
+            char where[64];
+            snprintf(where, sizeof where, "span at %llu, block %u of %u", (unsigned long long)p0, b, S);
+            RC_TRY(join_pieces(c, scan_div, consumer, (uint64_t)b * R, (uint64_t)b * R + rows_b, piece,
+                               {nullptr, 0, (uint32_t)p0, S, R, db->d_order}, t0, rec_timed, where));
+        }
+        RC_TRY(timed_sync(c));  // the span's records are overwritten next
+    }
+    return SMAFA_OK;
+}
+
+// The driver of the delta join: every pair within scan_div that a NEW row — subject numbers first_row .. n-1 — forms with any
+// row of the store, new or old, as the lists of pieces to `consumer`; a pair of two new rows comes twice, once from each
+// side, the self-pairs come too.  The new rows are walked in subject-number order — the order they were appended in — in
+// spans of join_stride x join_block rows, cut into blocks of join_block consecutive ones.  A span's rows, wherever the
+// sort has put them, become query records on the device (gather_records_kernel through pos_of[], which the caller has
+// made current), and every block is scanned against ALL tiles: the same scans as the full join's, chosen by the same
+// scan_plan.h, and an index probe where a current block index serves the bound.  A piece is shaped {p0 = the span's first
+// row, counted from first_row, S = 1, R = 0xffffffff, order = J.rows}: list query r is J.rows[p0 + r] for the consumers
+// of the full join too, unchanged.  The piece protocol is join_pieces', the reduced piece size carried across the blocks.
+static int delta_pass(JoinCall &c, uint32_t first_row, uint32_t scan_div, JoinConsumer &consumer) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    smafa_qset *qs = &db->join_q;
+    qs->db = db;
+    const uint64_t new_rows = db->n - first_row, span_rows = db->join_block * db->join_stride;
+    uint64_t piece = db->join_block;  // rows per scan
+    RC_TRY(J.rows.ensure(new_rows * sizeof(uint32_t)));
+    J.joins++;
+    for (uint64_t a0 = 0; a0 < new_rows; a0 += span_rows) {
+        const uint64_t m = std::min<uint64_t>(span_rows, new_rows - a0);
+        const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
+        // padded as join_pass pads: whole 64-record chunks plus one, zeros
+        const uint64_t padded = std::max<uint64_t>((m + 63) / 64 * 64, 64) + 64;
+        qs->nq = m;
+        qs->serial = g_qset_serial.fetch_add(1);
+        RC_TRY(qs->qrec.ensure(padded * db->QS * sizeof(uint32_t)));
+        RC_TRY(qs->thr.ensure(padded * sizeof(uint32_t)));
+        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
+        hipLaunchKernelGGL(smafa_dl::gather_records_kernel, list_grid(m * db->P * db->W), dim3(256), 0, db->stream, db->d_planes,
+                           J.pos_of.as<uint32_t>(), db->P, db->PQ, db->W, db->QS, (uint32_t)(first_row + a0), (uint32_t)m,
+                           qs->qrec.as<uint32_t>(), J.rows.as<uint32_t>() + a0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+        db->call_launches++;
+        bool rec_timed = false;
+        for (uint32_t b = 0; b < S; b++) {
+            const uint64_t q0 = (uint64_t)b * db->join_block;
+            char where[64];
+            snprintf(where, sizeof where, "new rows from %llu, block %u of %u", (unsigned long long)(first_row + a0), b, S);
+            RC_TRY(join_pieces(c, scan_div, consumer, q0, std::min<uint64_t>(m, q0 + db->join_block), piece,
+                               {nullptr, 0, (uint32_t)a0, 1u, 0xffffffffu, J.rows.as<uint32_t>()}, 0u, rec_timed, where));
         }
         RC_TRY(timed_sync(c));  // the span's records are overwritten next
     }
@@ -211,7 +277,7 @@ static void join_finish(JoinCall &c) {
     const auto &J = db->join;
     db->call_ms += (float)(J.rec_ms + J.filter_ms + J.count_ms + J.link_ms + J.flatten_ms);
     db->call_timed = true;  // (scan_range cleared it)
-    if (!c.no_scans) note_call_kernel(db, "smafa_join::store_records_kernel");
+    if (!c.no_scans) note_call_kernel(db, c.delta ? "smafa_dl::gather_records_kernel" : "smafa_join::store_records_kernel");
     if (c.inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
 }
 
@@ -337,6 +403,90 @@ static int join_components(smafa_db *db, uint32_t max_div, uint32_t *d_labels, u
     note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
     log_line(2, "components of %u rows at bound %u: %u scans (%u of them repeats), records %.3f ms, scans %.3f ms, link %.3f ms, "
              "flatten %.3f ms", n, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms, J.flatten_ms);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_since_launch (delta.hip.h): every unordered pair within max_div whose larger subject number is >= first_row,
+// once.  delta_filter_kernel keeps the rows of a piece's list whose subject number is below their query's.
+// first_row <= n
+static int delta_pairs(smafa_db *db, uint32_t first_row, uint32_t max_div, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count) {
+    auto &J = db->join;
+    JoinCall c{db, first_row >= db->n};  // no new row: no pair
+    c.delta = true;
+    RC_TRY(join_begin(c, d_count, 1, 2));
+    if (c.nothing || c.no_scans) return SMAFA_OK;
+    RC_TRY(join_positions(c));
+    JoinConsumer filter = timed_consumer(c, &J.filter_ms, nullptr, [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_dl::delta_filter_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.order,
+                           d_hits, (unsigned long long)cap, d_count);
+    });
+    RC_TRY(delta_pass(c, first_row, max_div, filter));
+    join_finish(c);
+    if (filter.used) note_call_kernel(db, "smafa_dl::delta_filter_kernel");
+    log_line(2, "delta self-join of %u rows from row %u at bound %u: %u scans (%u of them repeats), gather %.3f ms, scans %.3f ms, "
+             "filter %.3f ms", (uint32_t)db->n, first_row, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.filter_ms);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_components_update_launch (delta.hip.h, components.hip.h): d_labels holds, in its first first_row entries, the
+// labels of the store's first first_row rows at this bound, and leaves as the labels of the whole store.  seed_parents_kernel
+// makes parent[] of them — and counts the entries that cannot be such labels —, link_rows_kernel unites the two subjects of
+// every row of the delta join's pieces, and flatten_labels_kernel writes the labels and counts the representatives: two sets of
+// old rows can only have become one through a new row, and every pair with a new row is in the delta join.  The count of
+// bad entries is read at every piece's wait and in front of the flatten launch, which does not run — d_labels is not
+// written — once it is non-zero.
+// first_row <= n
+static int delta_components(smafa_db *db, uint32_t first_row, uint32_t max_div, uint32_t *d_labels, unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool all_near = max_div >= db->L;
+    JoinCall c{db, db->n < 2 || all_near || first_row >= db->n};
+    c.delta = true;
+    RC_TRY(join_begin(c, d_count, 1, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(sizeof(unsigned long long)));
+    RC_TRY(timed_begin(c, &J.link_ms, "components update: parent[] seeded"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, sizeof(unsigned long long), db->stream));
+    if (all_near)  // every row is within the bound of row 0
+        HIP_TRY(hipMemsetAsync(J.parent.p, 0, (size_t)n * sizeof(uint32_t), db->stream));
+    else
+        hipLaunchKernelGGL(smafa_dl::seed_parents_kernel, row_grid(n), dim3(256), 0, db->stream, d_labels, first_row, n,
+                           J.parent.as<uint32_t>(), J.ctl.as<unsigned long long>());
+    RC_TRY(timed_end(c, all_near ? 0u : 1u));
+    unsigned long long &bad = c.kept_seen;
+    const auto read_bad = [&c] {
+        HIP_TRY(hipMemcpyAsync(&c.kept_seen, c.db->join.ctl.p, sizeof c.kept_seen, hipMemcpyDeviceToHost, c.db->stream));
+        return SMAFA_OK;
+    };
+    const auto bad_labels = [&] {
+        return set_error(SMAFA_ERR_INVALID, "components update: %llu of the first %u labels are no labels of a store of %u rows (a label is "
+                         "at most its row's number, and its own label)", bad, first_row, first_row);
+    };
+    JoinConsumer link = timed_consumer(c, &J.link_ms, "components update: parent[] linked with a piece's rows", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_cc::link_rows_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           J.parent.as<uint32_t>());
+    });
+    link.before_wait = read_bad;
+    link.take = [&, timed = link.take](const JoinPiece &p) { return bad ? bad_labels() : timed(p); };
+    if (!c.no_scans) {
+        RC_TRY(join_positions(c));
+        RC_TRY(delta_pass(c, first_row, max_div, link));
+    }
+    RC_TRY(read_bad());
+    RC_TRY(timed_sync(c));
+    if (bad) return bad_labels();
+    RC_TRY(timed_pass(c, &J.flatten_ms, nullptr, [&] {
+        hipLaunchKernelGGL(smafa_cc::flatten_labels_kernel, row_grid(n), dim3(256), 0, db->stream, J.parent.as<uint32_t>(), n, d_labels, d_count);
+    }));
+    RC_TRY(timed_sync(c));
+    join_finish(c);
+    if (!all_near) note_call_kernel(db, "smafa_dl::seed_parents_kernel");
+    if (link.used) note_call_kernel(db, "smafa_cc::link_rows_kernel");
+    note_call_kernel(db, "smafa_cc::flatten_labels_kernel");
+    log_line(2, "components update of %u rows from row %u at bound %u: %u scans (%u of them repeats), gather %.3f ms, scans %.3f ms, "
+             "seed + link %.3f ms, flatten %.3f ms", n, first_row, max_div, J.blocks + J.rescans, J.rescans, J.rec_ms, J.scan_ms, J.link_ms,
+             J.flatten_ms);
     return SMAFA_OK;
 }
 

@@ -1,0 +1,51 @@
+"""The kernel census of the delta join's namespace (CPU): the smafa_dl:: kernels in the gfx950 code object of the built
+libsmafa_amd.so must be exactly the three tabled here, each beside the GPU test that runs it.  The delta calls add nothing to
+smafa::, smafa_join::, smafa_cc::, smafa_lv::, smafa_dn::, smafa_pk:: or smafa_nb:: — pinned here at 199 / 3 / 3 / 3 / 4 / 6 / 4
+as the other census files pin them — and none of the three names carries a word those files forbid outside their namespaces."""
+import os
+import re
+
+from test_join_kernel_census import ROOT, binary_kernels  # noqa: F401  (the fixture that lists the code object's kernels)
+from test_neighbours_kernel_census import FORBIDDEN, NB_KERNELS
+from test_peaks_kernel_census import PK_KERNELS
+
+# kernel -> the GPU test that runs it and asserts it by name (smafa_last_call_kernels)
+DL_KERNELS = {
+    "smafa_dl::gather_records_kernel": "tests/test_gpu_delta_join.py::test_every_engine_one_answer",
+    "smafa_dl::delta_filter_kernel": "tests/test_gpu_delta_join.py::test_every_engine_one_answer",
+    "smafa_dl::seed_parents_kernel": "tests/test_gpu_delta_join.py::test_components_update_over_three_appends",
+}
+NB_WORDS = ("mirror_pack", "row_bounds", "cut_degrees", "emit_kernel")
+
+
+def test_delta_kernels_are_the_tabled_ones(binary_kernels):  # noqa: F811
+    found = {n for n in binary_kernels if n.startswith("smafa_dl::")}
+    assert found == set(DL_KERNELS), (sorted(found - set(DL_KERNELS)), sorted(set(DL_KERNELS) - found))
+    assert not [n for n in DL_KERNELS if any(w in n for w in FORBIDDEN + NB_WORDS)]
+
+
+def test_other_namespaces_are_unchanged(binary_kernels):  # noqa: F811
+    assert len({n for n in binary_kernels if n.startswith("smafa::")}) == 199
+    assert {n for n in binary_kernels if n.startswith("smafa_join::")} == {
+        "smafa_join::store_records_kernel", "smafa_join::inverse_order_kernel", "smafa_join::join_filter_kernel"}
+    assert {n for n in binary_kernels if n.startswith("smafa_cc::")} == {
+        "smafa_cc::init_labels_kernel", "smafa_cc::link_rows_kernel", "smafa_cc::flatten_labels_kernel"}
+    assert {n for n in binary_kernels if n.startswith("smafa_lv::")} == {
+        "smafa_lv::init_levels_kernel", "smafa_lv::hook_levels_kernel", "smafa_lv::flatten_levels_kernel"}
+    assert {n for n in binary_kernels if n.startswith("smafa_dn::")} == {
+        "smafa_dn::init_density_kernel", "smafa_dn::count_keep_kernel", "smafa_dn::link_cores_kernel",
+        "smafa_dn::flatten_density_kernel"}
+    assert {n for n in binary_kernels if n.startswith("smafa_pk::")} == set(PK_KERNELS) and len(PK_KERNELS) == 6
+    assert {n for n in binary_kernels if n.startswith("smafa_nb::")} == set(NB_KERNELS) and len(NB_KERNELS) == 4
+    others = {n for n in binary_kernels if not n.startswith(("smafa::", "smafa_join::", "smafa_cc::", "smafa_lv::", "smafa_dn::",
+                                                              "smafa_pk::", "smafa_nb::"))}
+    assert not [n for n in others if any(w in n for w in FORBIDDEN + NB_WORDS)], others
+
+
+def test_tabled_tests_exist_and_name_their_kernel():
+    for name, test in DL_KERNELS.items():
+        path, func = test.split("::")
+        with open(os.path.join(ROOT, path)) as f:
+            text = f.read()
+        assert re.search(r"^def %s\(" % re.escape(func), text, re.M), (name, test)
+        assert name in text, name
