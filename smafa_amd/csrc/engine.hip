@@ -16,6 +16,7 @@
 
 #include "engine.h"
 #include "scan_plan.h"
+#include "kth_plan.h"
 #include "host/packed.h"
 #include "kernels.hip.h"
 #include "index.hip.h"
@@ -34,6 +35,7 @@ namespace smafa {
         hipError_t e_ = (expr);                                                                           \
         if (e_ != hipSuccess) return set_error(SMAFA_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 // planes per query record: 3 code bits for ACGTN, 5 for the amino-acid codes 0..27
 static int query_planes_for(int alphabet) { return alphabet == SMAFA_ALPHABET_AA ? 5 : 3; }
@@ -889,364 +891,8 @@ static int launch_tiles(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t
     return SMAFA_OK;
 }
 
-// Scan queries [q_begin, q_end) of a resident set against the whole store; rows and their count stay on
-// the device.
-// k_tight = 0: ONE launch (up to 64 queries: a one-workgroup kernel zeroes *d_count first and nobody takes a ticket), fixed
-// bound max_div: the kernel appends straight into the caller's list and — big batches — its last
-// workgroup publishes the total in *d_count (which may exceed cap: the rows past it are dropped, the count is exact).
-// k_tight >= 1: the bound of each query is lowered to its running k-th smallest distance while the scan proceeds.
-// Workgroups of one launch run side by side and would all start from the loose initial bound, so the store is walked
-// in segments that grow 8x per launch (bounds tighten between launches), after a seed launch over the first segment
-// that only lowers the bounds and appends nothing.  Rows are appended to a scratch list while the bounds are still
-// running; filter_rows_kernel then keeps the ones within the final bounds.
-// tile_begin (fixed-bound form only): the scan kernels start at that wave tile — the self-join's triangular cut; an index
-// probe has no tile range and answers over the whole store.
-static int scan_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q_end, uint32_t max_div,
-                      uint32_t k_tight, smafa_hit *d_hits, uint64_t cap, unsigned long long *d_count, uint32_t tile_begin = 0) {
-    const uint32_t nq = q_end - q_begin;
-    db->last_launches = 0;
-    db->timed = false;
-    db->call_timed = false;
-    if (nq == 0 || db->n == 0) {
-        HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
-        return SMAFA_OK;
-    }
-    int prc = maybe_resort(db);
-    if (prc) return prc;
-    unsigned long long *d_ctr = db->ctrs.as<unsigned long long>();
-    const uint32_t thr0 = std::min<uint32_t>(max_div, db->L);  // a distance never exceeds seq_len
-    const uint32_t n_tiles = (uint32_t)((db->n + kWaveTile - 1) / kWaveTile);
-    if (k_tight == 0) {
-        // A store with a current block index answers a tight fixed bound from it: bound + 1 probes per query instead of a
-        // pass over every tile (index.hip.h).  Mode 2 builds the index the first time such a scan arrives.
-        if (db->index_mode >= 2 && db->knobs.use_filter && nq > 64u && db->W <= (uint32_t)kIndexMaxWords && thr0 + 1u <= std::min<uint32_t>(kIndexMaxBlocks, db->L) &&
-            db->n >= db->index_min_rows && db->n < (1ull << 31) && (!index_current(db) || db->index.B < thr0 + 1u)) {
-            bool build = db->index_mode == 2;
-            if (!build) {
-                // rent or buy: the scans that could have used an index are charged at the batched kernels' measured rate
-                // (1.7e-12 ms per pair and stored vector: profiles/r04_bench_full.json), the build at ~1 ms per block and 10M
-                // subjects (profiles/r04_index.txt); the index is built once the rent paid equals its price
-                if (db->index_debt_generation != db->generation) db->index_debt_ms = 0.0, db->index_debt_generation = db->generation;
-                db->index_debt_ms += (double)nq * (double)db->n * (double)(db->P * db->W) * 1.7e-12;
-                build = db->index_debt_ms >= 0.3 + (double)(thr0 + 1u) * (double)db->n * 1.0e-7;
-            }
-            if (build && db->index_failed_generation != db->generation + 1u) {
-                // (a build that fails — no room for another 8 B x blocks + a row copy per subject — is not the scan's failure:
-                // the scan kernels answer, and the automatic modes do not try again until the store changes)
-                if (index_build(db, thr0 + 1u) != SMAFA_OK) {
-                    log_line(1, "block index not built (%s): scanning as before", smafa_last_error());
-                    index_drop(db);
-                    db->index_failed_generation = db->generation + 1u;
-                }
-            }
-        }
-        uint8_t probe_block[kIndexMaxBlocks];
-        if (index_plan(db, thr0, nq, probe_block)) {
-            hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, db->stream, (uint32_t *)d_count, 0u, (uint64_t)2);
-            HIP_TRY(hipEventRecord(db->ev0, db->stream));
-            int rc = index_probe(db, qs, q_begin, q_end, thr0, probe_block, d_hits, cap, d_count);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(db->ev1, db->stream));
-            db->timed = true;
-            return SMAFA_OK;
-        }
-        // A handful of queries against a big store is a grid of many short-lived workgroups: there the ticket every workgroup
-        // takes at its end (to find the last one, which publishes the total) costs more than a tiny fill kernel in front of the launch —
-        // the rows are then reserved straight from *d_count (one-query pass over the 50M store: 65 -> 57 us streaming,
-        // 22.4 -> 18.5 us with the zone level; profiles/r03_stream_nt.txt).  Big batches keep the one-launch form.
-        const bool own = nq <= 64u;
-        if (own) hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, db->stream, (uint32_t *)d_count, 0u, (uint64_t)2);
-        HIP_TRY(hipEventRecord(db->ev0, db->stream));
-        int rc = launch_tiles(db, qs, q_begin, q_end, tile_begin, n_tiles, 0, thr0, d_hits, cap, own ? nullptr : d_count, false,
-                              own ? d_count : nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(db->ev1, db->stream));
-        db->timed = true;
-        return SMAFA_OK;
-    }
-    // Tightening modes append every pair that is within its query's bound at that moment — 50-100 rows per query
-    // when the bound starts loose — of which the filter pass keeps the ones within the final bound: the scratch list
-    // is sized for the appended volume, the caller's buffer only has to hold what is kept.
-    // (k >= 2 with a loose bound counts first and appends only the final rows, straight into the caller's list.)
-    const bool count_first = k_tight >= db->count_first_k && !prefilter_prunes(db->shape(), db->knobs, thr0);
-    // Counting first costs TWO passes over every pair (count, then append with the exact bounds).  On a big store the first
-    // one is cut to a SAMPLE — the first 1/32 of the tiles: the k-th smallest distance within any subset of the subjects is an
-    // upper bound of the k-th smallest over all of them — and the rest of the store is scanned ONCE, counting, tightening and
-    // appending to the scratch list from that bound on; the counts are then complete up to the k-th distance (the bound never
-    // dropped below it), so kth_from_counts_kernel gives the exact bounds, the sample's own tiles are scanned again with
-    // those fixed (appending), and filter_rows_kernel keeps what is within them: (1 + 1/32) passes instead of 2
-    // (10 000 queries x 10M aa, k = 5 / 50, sample 1/8: 34 / 39 ms, 1/16: 30 / 35, 1/32: 28 / 35; profiles/r04_kth.txt).
-    // Rows parked meanwhile: ~k x (segment / store seen before it) per segment, a few k per query (SMAFA_KTH_SAMPLE=0: two passes).
-    const uint32_t sample_tiles = (count_first && db->kth_sample_div && n_tiles >= db->kth_sample_min_tiles &&
-                                   n_tiles / db->kth_sample_div >= 1u &&
-                                   (uint64_t)k_tight * 4u <= (uint64_t)(n_tiles / db->kth_sample_div) * kWaveTile)
-                                      ? n_tiles / db->kth_sample_div : 0u;
-    uint64_t scratch_rows = 0;
-    if (!count_first || sample_tiles) {
-        const uint64_t per_query = sample_tiles ? 16ull * k_tight + 128u : 128u;
-        scratch_rows = std::max<uint64_t>(2 * cap, std::min<uint64_t>((uint64_t)nq * per_query, 1ull << 27));
-        int src = db->scratch.ensure(scratch_rows * sizeof(smafa_hit));
-        if (src) return src;
-    }
-    smafa_hit *d_scratch = db->scratch.as<smafa_hit>();
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(unsigned long long), db->stream));
-    hipLaunchKernelGGL(fill_u32_kernel, dim3((nq + 255) / 256), dim3(256), 0, db->stream, qs->thr.as<uint32_t>() + q_begin,
-                       thr0, (uint64_t)nq);
-    const size_t cnt_stride = db->L + 1;
-    auto zero_cnt = [&]() -> int {
-        if (k_tight < 2) return SMAFA_OK;
-        int rc = qs->cnt.ensure(std::max<uint64_t>(qs->nq, 64) * cnt_stride * sizeof(uint32_t));
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(qs->cnt.as<uint32_t>() + (size_t)q_begin * cnt_stride, 0,
-                               (size_t)nq * cnt_stride * sizeof(uint32_t), db->stream));
-        return SMAFA_OK;
-    };
-    HIP_TRY(hipEventRecord(db->ev0, db->stream));
-    int rc = zero_cnt();
-    // seed: k = 1 reduces each wave's minimum before its single atomicMin, so a whole workgroup tile is
-    // cheap; the k >= 2 seed counts every pair in its histogram, so keep it to one wave tile
-    const uint32_t seed_tiles = std::min<uint32_t>(k_tight == 1 ? kWgWaves : 1, n_tiles);
-    // k >= 2: the k-th smallest distance within the first (up to) 1024 subjects, from an LDS histogram per query
-    // (kth_seed_kernel: no global atomics; the counting launch it replaces put every pair of its tile through them)
-    const bool hist_seed = k_tight >= 2 && db->L < (uint32_t)kSeedBins && db->kth_hist_seed;
-    // ... and where a sample is counted first (sample_tiles), the same kernel counts the WHOLE sample: every pair of it, in LDS
-    // histograms that are added to cnt[q][d] — exactly what the counting launches would have counted, without their global
-    // atomics per pair and their growing segments (k = 50, 10 000 queries: 12 ms -> ~2 ms for a 1/32 sample)
-    const bool hist_sample = hist_seed && sample_tiles != 0;
-    auto launch_hist = [&](uint32_t tiles, uint32_t *d_cnt) {
-        const uint32_t n_chunks = (nq + kSeedQueries - 1) / kSeedQueries;
-        const uint32_t steps = (tiles + kWgWaves - 1) / kWgWaves;
-        // enough workgroups to fill the chip (8 per CU), never more tile groups than 4-tile steps
-        uint32_t n_groups = d_cnt ? std::max(1u, std::min(steps, ((uint32_t)db->n_cu * 8u + n_chunks - 1) / n_chunks)) : 1u;
-        if (d_cnt && db->kth_groups) n_groups = std::min(n_groups, db->kth_groups);  // (1: one workgroup per chunk walks every step)
-        // (the call's list names the counting form as a marker of its own, after the template-id — as scan_wide_kernel's zone level)
-        auto note_counts = [&]() {
-            if (!d_cnt) return;
-            const std::string id = db->plan_kernel;
-            note_kernel(db, "%s (sample counts)", id.c_str());
-        };
-        const dim3 grid(n_chunks * n_groups), block(256);
-        const uint4 *planes = reinterpret_cast<const uint4 *>(db->d_planes);
-        const uint32_t *qrec = qs->qrec.as<uint32_t>();
-        uint32_t *thr = qs->thr.as<uint32_t>();
-        auto launch = [&](auto ps, auto pq, auto w) {
-            constexpr int PS = decltype(ps)::value, PQ = decltype(pq)::value, W = decltype(w)::value;
-            note_kernel(db, "smafa::kth_seed_kernel<%d, %d, %d>", PS, PQ, W);
-            hipLaunchKernelGGL((kth_seed_kernel<PS, PQ, W>), grid, block, 0, db->stream, planes, qrec, db->QS, db->P, db->PQ, db->W, tiles,
-                               (uint32_t)db->n, q_begin, q_end, n_chunks, n_groups, k_tight, thr0, thr, d_cnt, (uint32_t)cnt_stride);
-            return true;
-        };
-        if (!for_shape(db->shape(), launch)) launch(ic<0>{}, ic<0>{}, ic<0>{});  // more than four words per plane: the any-shape form
-        note_counts();
-    };
-    if (!rc && hist_sample) {
-        launch_hist(sample_tiles, qs->cnt.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-    } else if (!rc && hist_seed) {
-        launch_hist(std::min<uint32_t>(kWgWaves, n_tiles), nullptr);
-        HIP_TRY(hipGetLastError());
-    } else {
-        if (!rc) rc = launch_tiles(db, qs, q_begin, q_end, 0, seed_tiles, k_tight, thr0, nullptr, 0, nullptr);
-        if (!rc) rc = zero_cnt();  // the seed's subjects are counted again below
-    }
-    uint32_t begin = 0, len = hist_seed ? 8u * kWgWaves : kWgWaves;  // (the histogram seed already stands for the first 4 tiles)
-    const uint32_t count_end = sample_tiles ? sample_tiles : n_tiles;  // the tiles that are only counted
-    if (hist_sample) begin = count_end;  // counted already, every pair of them
-    while (!rc && begin < count_end) {
-        const uint32_t end = (uint32_t)std::min<uint64_t>((uint64_t)begin + len, count_end);
-        rc = launch_tiles(db, qs, q_begin, q_end, begin, end, k_tight, thr0, count_first ? nullptr : d_scratch,
-                          count_first ? 0 : scratch_rows, nullptr);
-        begin = end;
-        len = len > (1u << 28) ? len : len * 8;
-    }
-    if (rc) return rc;
-    if (sample_tiles) {
-        // bounds from the sample's counts (a query with fewer than k subjects in range so far keeps its bound)
-        hipLaunchKernelGGL(kth_from_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, db->stream, qs->cnt.as<uint32_t>(),
-                           (uint32_t)cnt_stride, k_tight, qs->thr.as<uint32_t>(), q_begin, nq);
-        // the rest of the store, once: count, tighten, append to the scratch list — in segments growing 4x, so that the
-        // workgroups of one launch do not all start from the sample's bound
-        len = 3u * sample_tiles;
-        while (!rc && begin < n_tiles) {
-            const uint32_t end = (uint32_t)std::min<uint64_t>((uint64_t)begin + len, n_tiles);
-            rc = launch_tiles(db, qs, q_begin, q_end, begin, end, k_tight, thr0, d_scratch, scratch_rows, nullptr);
-            begin = end;
-            len = len > (1u << 28) ? len : len * 4;
-        }
-        if (rc) return rc;
-        // every pair within the k-th distance has been counted once: the exact bounds; then the sample's own tiles with
-        // those bounds fixed, appending to the same list
-        hipLaunchKernelGGL(kth_from_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, db->stream, qs->cnt.as<uint32_t>(),
-                           (uint32_t)cnt_stride, k_tight, qs->thr.as<uint32_t>(), q_begin, nq);
-        rc = launch_tiles(db, qs, q_begin, q_end, 0, sample_tiles, 0, thr0, d_scratch, scratch_rows, nullptr, true);
-        if (rc) return rc;
-        // (falls through to the filter pass below: rows within the exact bounds go to the caller's list)
-    } else if (count_first) {
-        hipLaunchKernelGGL(kth_from_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, db->stream, qs->cnt.as<uint32_t>(),
-                           (uint32_t)cnt_stride, k_tight, qs->thr.as<uint32_t>(), q_begin, nq);
-        rc = launch_tiles(db, qs, q_begin, q_end, 0, n_tiles, 0, thr0, d_hits, cap, d_count, true);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(db->ev1, db->stream));
-        db->timed = true;
-        return SMAFA_OK;
-    }
-    HIP_TRY(hipEventRecord(db->ev1, db->stream));  // smafa_last_scan_ms: the scan kernels, not the filter pass below
-    db->timed = true;
-    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), db->stream));
-    hipLaunchKernelGGL(filter_rows_kernel, dim3((uint32_t)std::min<uint64_t>(1024, (scratch_rows + 255) / 256)), dim3(256), 0,
-                       db->stream, d_scratch, d_ctr, (unsigned long long)scratch_rows, d_hits, (unsigned long long)cap,
-                       d_count, qs->thr.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(unsigned long long), db->stream));  // counters are zero between scans
-    return SMAFA_OK;
-}
-
-// the stream has just been synchronised after a scan_range: fold its kernel time into the call's totals
-static void note_call_scan(smafa_db *db) {
-    db->call_scans++;
-    db->call_launches += db->last_launches;
-    float ms = 0.f;
-    if (db->timed && hipEventElapsedTime(&ms, db->ev0, db->ev1) == hipSuccess) db->call_ms += ms;
-    db->life_ms += ms;
-    db->life_launches += db->last_launches;
-}
-
-static bool hit_less(const smafa_hit &x, const smafa_hit &y) {
-    if (x.query != y.query) return x.query < y.query;
-    if (x.dist != y.dist) return x.dist < y.dist;
-    return x.subject < y.subject;
-}
-
-// ---- ordering rows on the device: (query, dist, subject) packed into one 64-bit radix key -------------
-__global__ void rows_to_keys_kernel(const smafa_hit *rows, uint64_t n, uint32_t q_begin, uint32_t dist_bits,
-                                    unsigned long long *keys) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const smafa_hit h = rows[i];
-    keys[i] = ((unsigned long long)(h.query - q_begin) << (32 + dist_bits)) | ((unsigned long long)h.dist << 32) | h.subject;
-}
-
-__global__ void keys_to_rows_kernel(const unsigned long long *keys, uint64_t n, uint32_t q_begin, uint32_t dist_bits,
-                                    smafa_hit *rows) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long k = keys[i];
-    smafa_hit h;
-    h.subject = (uint32_t)k;
-    h.dist = (uint32_t)(k >> 32) & ((1u << dist_bits) - 1u);
-    h.query = (uint32_t)(k >> (32 + dist_bits)) + q_begin;
-    rows[i] = h;
-}
-
-// Sort db->hits[0..count) by (query, dist, subject) in place with a device radix sort; returns false (and leaves
-// the rows untouched) when the key does not fit 64 bits — the caller then orders them on the host.
-static int sort_rows_on_device(smafa_db *db, uint64_t count, uint32_t q_begin, uint32_t q_end, bool *sorted,
-                               smafa_hit *rows = nullptr) {
-    *sorted = false;
-    if (!rows) rows = db->hits.as<smafa_hit>();  // (the self-join orders its own list)
-    uint32_t dist_bits = 1;
-    while ((1u << dist_bits) <= db->L) dist_bits++;
-    uint32_t q_bits = 1;
-    while (q_bits < 32 && (1ull << q_bits) < (uint64_t)(q_end - q_begin)) q_bits++;
-    if (dist_bits + q_bits > 32 || count > 0x7fffffffull) return SMAFA_OK;
-    int rc = db->keys_a.ensure(count * sizeof(unsigned long long));
-    if (!rc) rc = db->keys_b.ensure(count * sizeof(unsigned long long));
-    if (rc) return rc;
-    unsigned long long *ka = db->keys_a.as<unsigned long long>(), *kb = db->keys_b.as<unsigned long long>();
-    const uint32_t blocks = (uint32_t)((count + 255) / 256);
-    hipLaunchKernelGGL(rows_to_keys_kernel, dim3(blocks), dim3(256), 0, db->stream, rows, count, q_begin, dist_bits, ka);
-    size_t tmp_bytes = 0;
-    const int end_bit = (int)(32 + dist_bits + q_bits);
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ka, kb, (int)count, 0, end_bit, db->stream));
-    rc = db->sort_tmp.ensure(tmp_bytes);
-    if (rc) return rc;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(db->sort_tmp.p, tmp_bytes, ka, kb, (int)count, 0, end_bit, db->stream));
-    hipLaunchKernelGGL(keys_to_rows_kernel, dim3(blocks), dim3(256), 0, db->stream, kb, count, q_begin, dist_bits, rows);
-    HIP_TRY(hipGetLastError());
-    *sorted = true;
-    return SMAFA_OK;
-}
-
-// Append db->hits[0..count) — rows of queries [q_begin, q_end) — to `out`, ordered by (query, dist, subject).
-static int fetch_rows(smafa_db *db, uint64_t count, uint32_t q_begin, uint32_t q_end, std::vector<smafa_hit> &out) {
-    if (count == 0) return SMAFA_OK;
-    bool sorted = false;
-    if (count >= 4096) {  // small lists are cheaper to order on the host
-        int rc = sort_rows_on_device(db, count, q_begin, q_end, &sorted);
-        if (rc) return rc;
-    }
-    const double t0 = now_seconds();
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    const double t1 = now_seconds();
-    const size_t old = out.size();
-    out.resize(old + count);
-    const double t2 = now_seconds();
-    HIP_TRY(hipMemcpyAsync(out.data() + old, db->hits.p, count * sizeof(smafa_hit), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    const double t3 = now_seconds();
-    if (!sorted) std::sort(out.begin() + old, out.end(), hit_less);  // each range ordered => `out` ordered
-    if (count >= (1u << 20))
-        log_line(2, "%llu rows: scan + device sort %.2f ms, host buffer %.2f ms, copy back %.2f ms", (unsigned long long)count,
-                 (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3);
-    return SMAFA_OK;
-}
-
-// Collect all qualifying rows of queries [q_begin, q_end) into `out` (host).  First the plain bound when there
-// is one (rows within max_div are usually few); if they do not fit, tighten to the k-th smallest distance; if
-// that still does not fit, halve the query range.  Ranges are visited in ascending query order and each is
-// ordered by (query, dist, subject) — on the device when it is big enough to matter — so `out` is ordered.
-static int collect_range(smafa_db *db, smafa_qset *qs, uint32_t q_begin, uint32_t q_end, uint32_t max_div,
-                         uint32_t max_num_hits, std::vector<smafa_hit> &out) {
-    const uint32_t k_tight = max_num_hits == SMAFA_NONE ? 0u : max_num_hits;
-    unsigned long long count = 0;
-    bool done = false;
-    for (int attempt = 0; attempt < 2 && !done; attempt++) {
-        uint32_t k;
-        if (attempt == 0) {
-            if (max_div == SMAFA_NONE && k_tight) continue;  // no bound at all: go straight to tightening
-            k = 0;
-        } else {
-            if (!k_tight) break;
-            k = k_tight;
-            // counting first, the scan returns k rows per query plus ties: make room for them up front (up to 64M rows)
-            if (k >= db->count_first_k && !prefilter_prunes(db->shape(), db->knobs, std::min<uint32_t>(max_div, db->L))) {
-                const uint64_t want = std::min<uint64_t>((uint64_t)(q_end - q_begin) * ((uint64_t)k + 64u), 1ull << 26);
-                if (db->hits_cap() < want) {
-                    int erc = db->hits.ensure(want * sizeof(smafa_hit));
-                    if (erc) return erc;
-                }
-            }
-        }
-        int rc = scan_range(db, qs, q_begin, q_end, max_div, k, db->hits.as<smafa_hit>(), db->hits_cap(),
-                            db->count.as<unsigned long long>());
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        note_call_scan(db);
-        done = count <= db->hits_cap();
-    }
-    if (!done) {
-        // a fixed-bound scan reports its exact total: make room for it and scan once more (up to 128M rows = 1.5 GB)
-        if (!k_tight && count <= (1ull << 27)) {
-            int rc = db->hits.ensure(count * sizeof(smafa_hit));
-            if (rc) return rc;
-            return collect_range(db, qs, q_begin, q_end, max_div, max_num_hits, out);
-        }
-        if (q_end - q_begin > 1) {
-            const uint32_t mid = q_begin + (q_end - q_begin) / 2;
-            int rc = collect_range(db, qs, q_begin, mid, max_div, max_num_hits, out);
-            if (rc) return rc;
-            return collect_range(db, qs, mid, q_end, max_div, max_num_hits, out);
-        }
-        // one query with more rows than the buffer: it can have at most one row per subject
-        int rc = db->hits.ensure(std::max<uint64_t>(count, db->n) * sizeof(smafa_hit));
-        if (rc) return rc;
-        return collect_range(db, qs, q_begin, q_end, max_div, max_num_hits, out);
-    }
-    return fetch_rows(db, count, q_begin, q_end, out);
-}
-
 // ---------------------------------------------------------------------------------------------
+#include "scan_host.hip.h"  // one scan of a resident set (scan_range), rows to the host, the host-buffer call (scan_to_host)
 #include "self_join.hip.h"  // the self-join: its two drivers and the calls that consume their pieces
 
 void db_life_stats(const smafa_db *db, double *kernel_ms, uint64_t *launches) {
@@ -1271,324 +917,6 @@ int db_clear(smafa_db *db) {
     db->tile_bits.clear();
     for (uint64_t &h : db->zone_hist) h = 0;
     db->generation++;
-    return SMAFA_OK;
-}
-
-int scan_to_host(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div,
-                 uint32_t max_num_hits, std::vector<smafa_hit> &out) {
-    out.clear();
-    db->call_ms = 0.f;
-    db->call_launches = db->call_scans = 0;
-    if (n_queries == 0) return SMAFA_OK;
-    if (n_queries > 0xfffffff0ull) return set_error(SMAFA_ERR_INVALID, "too many queries in one batch");
-    int rc = use_device(db);
-    if (rc) return rc;
-    rc = db->count.ensure(sizeof(unsigned long long));
-    if (!rc && db->hits_cap() < (1ull << 22)) rc = db->hits.ensure((1ull << 22) * sizeof(smafa_hit));  // 4M rows = 48 MiB
-    if (rc) return rc;
-    rc = validate_codes(db, query_codes, n_queries);
-    if (rc) return rc;
-    rc = qset_fill(&db->scratch_q, db, query_codes, n_queries);
-    if (rc) return rc;
-    // k-th-distance modes whose bound is loose or absent (`smafa query` without --max-divergence — the reference's
-    // default): the scan would run the all-planes kernel until each query's running bound has tightened.  Most queries
-    // of real inputs have their k nearest subjects within a few mismatches, so first ask the cheap questions: a LADDER of
-    // scans whose bound starts at a value the prefilters still handle well (5 of the first 32 columns: level 1 prunes,
-    // zone kernel; then 12, and 30 (two planes: 16) at two words per plane: the folded bounds of the all-planes kernel still reject
-    // nearly every pair there), each over the queries the step before left open.  A query with at least k rows within a step's bound is
-    // finished: its k-th smallest distance is <= that bound, so every row it may print is among them.  Whoever is
-    // left takes the tightening path, as a compacted batch.  Exact at every step.  A step that finishes fewer than an
-    // eighth of its queries is the last one (data without near neighbours pays for one cheap step only).
-    // Measured, 10 000 queries x 10M aa subjects, best hit, per step (tools/bound_probe.py, profiles/
-    // r02_bound_probe.txt): bound 5 2.1 ms, 8 8.1 ms, 12 9.2 ms, 14 14.3 ms, no bound 28 ms; nucleotides 1.8, 6.6, 7.7,
-    // 10.4, 16.7.
-    const uint32_t k_mode = max_num_hits == SMAFA_NONE ? 0u : max_num_hits;
-    const uint32_t cols = std::min<uint32_t>(32u, db->L);
-    // first step: level 1 looks at `cols` columns of one plane; at a bound of a sixth of them it still rejects all but
-    // a few percent of the (wave, query) steps
-    std::vector<uint32_t> ladder = {(cols - 1u) / 6u, 3u * cols / 8u};
-    if (db->W == 2 && db->L >= 33) {  // two words: scan_kernel's FOLD 1 / FOLD 2 forms still reject at 13..17 / 18..32
-        // (a step at 16 in front of the one at 30 costs nearly as much and is redundant: queries 0..30 substitutions away
-        // from their subject, 10 000 x 10M aa: 35 ms with both, profiles/r02_besthit_ladder.txt)
-        // (three planes and more: a step at 17, the top of FOLD 1's range — 12 ms where the step at 30 costs 15 — is there for
-        // the planner below to choose when most open queries lie within it)
-        // — only where the planner will run (plan_later_steps needs 2048 open queries): a small batch would otherwise run the
-        // steps at 17 AND 30 back to back, which the measurement above found redundant
-        if (db->P >= 3 && n_queries >= 2048) ladder.push_back(17u);
-        ladder.push_back(db->P >= 3 ? 30u : 16u);
-    }
-    const uint32_t limit = std::min<uint32_t>(max_div, db->L);
-    // A store with a current block index answers "every pair within d" for the largest bound d its blocks serve in a few
-    // microseconds per thousand queries: that fixed-bound scan goes first, in place of every tightening step at or below d
-    // (a query with k rows within d is finished exactly as after any other step).
-    // Rent or buy (mode 3 — what `smafa query` sets) for calls WITHOUT a usable bound too: the ladder and the loose path cost the
-    // scan kernels ~1.6e-11 ms per pair and stored vector (10 000 queries x 10M aa: 16-19 ms, profiles/r04_bench_full.json); once
-    // such calls have cost what an index for the ladder's first steps would, it is built — blocks as narrow as the store's size
-    // leaves selective (~log2(n) - 2 bits of letters per block: 4 aa columns, 10 nucleotides at 10M subjects), so that it serves
-    // the widest bounds it can (aa: up to 14).  Only where that index would take at least the ladder's first step.
-    if (db->index_mode == 3 && k_mode >= 1 && n_queries > 64 && db->knobs.use_filter && db->knobs.lazy && db->two_phase && !ladder.empty() &&
-        limit > ladder[0] && db->W <= (uint32_t)kIndexMaxWords && db->n >= db->index_min_rows && db->n < (1ull << 31) &&
-        db->index_failed_generation != db->generation + 1u) {
-        const double letter_bits = db->alphabet == SMAFA_ALPHABET_AA ? 4.3 : db->P == 2 ? 2.0 : 2.3;
-        const uint32_t width = (uint32_t)std::max(2.0, std::floor((std::log2((double)db->n) - 2.0) / letter_bits));
-        const uint32_t want = std::min<uint32_t>((uint32_t)kIndexMaxBlocks, db->L / width);
-        if (want >= ladder[0] + 1u && (!index_current(db) || db->index.B < want)) {
-            if (db->index_debt_generation != db->generation) db->index_debt_ms = 0.0, db->index_debt_generation = db->generation;
-            db->index_debt_ms += (double)n_queries * (double)db->n * (double)(db->P * db->W) * 1.6e-11;
-            if (db->index_debt_ms >= 0.3 + (double)want * (double)db->n * 1.0e-7) {
-                if (index_build(db, want) != SMAFA_OK) {
-                    log_line(1, "block index not built (%s): scanning as before", smafa_last_error());
-                    index_drop(db);
-                    db->index_failed_generation = db->generation + 1u;
-                }
-            }
-        }
-    }
-    uint32_t index_step = UINT32_MAX;  // position in the ladder of the step the index answers
-    if (k_mode >= 1 && n_queries > 64) {
-        uint8_t blocks[kIndexMaxBlocks];
-        uint32_t d = index_current(db) ? db->index.B : 0u;
-        while (d > 0 && !index_plan(db, d - 1u, (uint32_t)n_queries, blocks)) d--;
-        // (only where it replaces the ladder's first step: a lower bound than that finishes too few queries to pay for the
-        // extra round of compaction — nucleotides, 10M x 100 000 queries, index served up to 2: 27 -> 45 ms; profiles/r04_index.txt)
-        if (d > 0 && d - 1u < limit && !ladder.empty() && d - 1u >= ladder[0]) {
-            const uint32_t served = d - 1u;
-            std::vector<uint32_t> kept = {served};
-            for (uint32_t b : ladder)
-                if (b > served) kept.push_back(b);
-            ladder.swap(kept);
-            index_step = 0;
-        }
-    }
-    std::vector<smafa_hit> done;      // rows of the finished queries (the caller's query numbers), ordered
-    std::vector<uint32_t> ids;        // open queries: position in the current batch -> the caller's number (empty: same)
-    std::vector<uint8_t> open_codes;  // ... and their code rows
-    const uint8_t *cur = query_codes;
-    uint32_t cur_n = (uint32_t)n_queries;
-    smafa_qset *qs = &db->scratch_q;
-    auto merge_done = [&](std::vector<smafa_hit> &more) {  // both ordered, disjoint queries
-        if (done.empty()) {
-            done.swap(more);
-            return;
-        }
-        std::vector<smafa_hit> all(done.size() + more.size());
-        std::merge(done.begin(), done.end(), more.begin(), more.end(), all.begin(), hit_less);
-        done.swap(all);
-    };
-    const bool laddered = k_mode >= 1 && db->knobs.use_filter && db->knobs.lazy && db->two_phase && n_queries >= 16;
-    // Which LATER steps pay is estimated once, on a sample of the queries the first step left open: every (cur_n / 256)-th
-    // open query is scanned in the k-th mode at the ladder's last bound, and the distribution of their k-th distances says
-    // what share of the open queries each later step would finish.  A step costs about 0.37 (bounds the OR-fold still
-    // rejects at), 0.5 (FOLD 1: the filter plane's per-word sums) or 0.53 (FOLD 2: two planes) of what the loose path costs
-    // per query (10M x 60 aa, 10 000 queries, best-hit launches: 9.1 / 12.5 / 13.2 ms against 25 ms for queries nothing is near to,
-    // profiles/r04_bound_probe.txt; round 3's 0.3 / 0.4 / 0.5 were taken against a 29 ms loose path: with half the queries
-    // unrelated the step at 12 then cost 7.4 ms to finish what the loose path does in 5.5, profiles/r04_kth.txt); the cheapest
-    // sequence of steps + loose path for the rest wins.
-    // (Round 2 stopped after any step that finished less than an eighth: queries 9-14 columns away from their nearest
-    // subject — novel members of a family — then paid the loose path in full: 33 ms per 10 000 instead of ~17.)
-    std::vector<char> run_step(ladder.size(), 1);
-    bool planned = false;
-    auto plan_later_steps = [&](size_t from) -> int {
-        planned = true;
-        size_t last = from;
-        while (last + 1 < ladder.size() && ladder[last + 1] < limit) last++;
-        if (from >= ladder.size() || ladder[from] >= limit) return SMAFA_OK;
-        const uint32_t ns = std::min<uint32_t>(256u, cur_n / 8u);  // (a share estimated to +-3 %; ~0.7 ms at 10M subjects)
-        const uint32_t stride = cur_n / ns;
-        std::vector<uint8_t> sample((size_t)ns * db->L);
-        for (uint32_t i = 0; i < ns; i++) memcpy(&sample[(size_t)i * db->L], cur + (size_t)i * stride * db->L, db->L);
-        int prc = qset_fill(&db->scratch_q3, db, sample.data(), ns);
-        if (prc) return prc;
-        unsigned long long count = 0;
-        // (one fixed-bound launch: every pair of the sample within the last bound; the tightening form's seed and growing
-        // segments — up to a dozen small launches — cost a 256-query sample 0.9 ms where this costs 0.4)
-        prc = scan_range(db, &db->scratch_q3, 0, ns, ladder[last], 0, db->hits.as<smafa_hit>(), db->hits_cap(),
-                         db->count.as<unsigned long long>());
-        if (prc) return prc;
-        HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        note_call_scan(db);
-        std::vector<uint32_t> kth(ns, UINT32_MAX);  // k-th smallest distance of each sample query within the last bound
-        if (count > db->hits_cap()) {
-            std::fill(kth.begin(), kth.end(), 0u);  // too dense to look at: every step will finish plenty
-        } else if (count) {
-            std::vector<smafa_hit> rows;
-            prc = fetch_rows(db, count, 0, ns, rows);
-            if (prc) return prc;
-            for (size_t i = 0; i < rows.size();) {
-                size_t j = i;
-                while (j < rows.size() && rows[j].query == rows[i].query) j++;
-                if (j - i >= k_mode) kth[rows[i].query] = rows[i + k_mode - 1].dist;
-                i = j;
-            }
-        }
-        const size_t n_later = last - from + 1;  // at most two steps today: every subset is tried
-        double best_cost = 1.0;                   // no further step: the loose path for everybody
-        uint32_t best_mask = 0;
-        for (uint32_t mask = 1; mask < (1u << n_later); mask++) {
-            double cost = 0.0, open_share = 1.0;
-            for (size_t t = 0; t < n_later; t++) {
-                if (!((mask >> t) & 1u)) continue;
-                const uint32_t b = ladder[from + t];
-                size_t fin = 0;
-                for (uint32_t v : kth) fin += v <= b;
-                cost += open_share * (b <= 3u * cols / 8u ? 0.37 : b <= 17u ? 0.5 : 0.53);
-                open_share = 1.0 - (double)fin / (double)ns;
-            }
-            cost += open_share;
-            if (cost < best_cost) {
-                best_cost = cost;
-                best_mask = mask;
-            }
-        }
-        for (size_t t = from; t < ladder.size(); t++) run_step[t] = t <= last && ((best_mask >> (t - from)) & 1u);
-        std::string chosen;
-        for (size_t t = 0; t < n_later; t++)
-            if ((best_mask >> t) & 1u) chosen += " " + std::to_string(ladder[from + t]);
-        log_line(2, "near-hit plan from a sample of %u open queries: further steps at bounds [%s ] -> %.2f of the loose path's cost",
-                 ns, chosen.c_str(), best_cost);
-        return SMAFA_OK;
-    };
-    // Does the FIRST step finish anybody?  On queries unrelated to the store (or a k that wants more neighbours than a family has)
-    // it costs a full zone-kernel pass and finishes nobody (2.2 ms per 10 000 queries at 10M subjects: 14 % of a batch of unrelated
-    // queries, 7 % of a k = 5 call).  Asked of every (n / 256)-th query first (0.1-0.2 ms): below a sixteenth of the sample finished,
-    // the step is skipped and the later steps are planned right away.  Exact either way (a skipped step only moves queries to a
-    // later, looser scan).
-    if (laddered && db->ladder_probe && n_queries >= 2048 && !ladder.empty() && limit > ladder[0] && index_step != 0) {
-        const uint32_t ns = 256, stride = (uint32_t)(n_queries / ns);
-        std::vector<uint8_t> sample((size_t)ns * db->L);
-        for (uint32_t i = 0; i < ns; i++) memcpy(&sample[(size_t)i * db->L], query_codes + (size_t)i * stride * db->L, db->L);
-        rc = qset_fill(&db->scratch_q3, db, sample.data(), ns);
-        if (rc) return rc;
-        unsigned long long count = 0;
-        // (a plain fixed-bound launch — every pair within the bound — not the step's tightening form with its seed and growing
-        // segments: seven small launches cost the sample more than the answer is worth)
-        rc = scan_range(db, &db->scratch_q3, 0, ns, ladder[0], 0, db->hits.as<smafa_hit>(), db->hits_cap(),
-                        db->count.as<unsigned long long>());
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        note_call_scan(db);
-        uint32_t finished = ns;  // (too dense to look at: the step will finish plenty)
-        if (count <= db->hits_cap()) {
-            std::vector<smafa_hit> rows;
-            rc = fetch_rows(db, count, 0, ns, rows);
-            if (rc) return rc;
-            std::vector<uint32_t> have(ns, 0);
-            for (const smafa_hit &h : rows) have[h.query]++;
-            finished = 0;
-            for (uint32_t v : have) finished += v >= k_mode;
-        }
-        if (finished * 16u < ns) {
-            run_step[0] = 0;
-            log_line(2, "near-hit probe: %u of %u sampled queries finish at bound %u: the step is skipped", finished, ns, ladder[0]);
-            rc = plan_later_steps(1);
-            if (rc) return rc;
-        }
-    }
-    for (size_t step = 0; laddered && step < ladder.size() && cur_n >= 16; step++) {
-        const uint32_t bound = ladder[step];
-        if (limit <= bound || (step > 0 && bound <= ladder[step - 1])) break;
-        if (!run_step[step]) continue;
-        unsigned long long count = 0;
-        // the step itself runs in the tightening mode (bound lowered to each query's k-th distance as the scan
-        // proceeds), so on dense stores only the rows within the final bound come back, not every pair within it
-        // (the index's step is a fixed-bound scan: every pair within the bound, from bound + 1 probes per query)
-        rc = scan_range(db, qs, 0, cur_n, bound, step == index_step ? 0u : k_mode, db->hits.as<smafa_hit>(), db->hits_cap(),
-                        db->count.as<unsigned long long>());
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(&count, db->count.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        note_call_scan(db);
-        if (count > db->hits_cap()) {
-            if (step == index_step) continue;  // (more rows than the buffer holds: the tightening steps take over)
-            break;  // too dense to look at: the full path decides
-        }
-        if (count == 0) {  // nobody within this bound: do the later steps pay?
-            if (!planned && cur_n >= 2048 && step + 1 < ladder.size()) {
-                rc = plan_later_steps(step + 1);
-                if (rc) return rc;
-                continue;
-            }
-            break;
-        }
-        std::vector<smafa_hit> near;
-        rc = fetch_rows(db, count, 0, cur_n, near);
-        if (rc) return rc;
-        std::vector<uint32_t> have(cur_n, 0);
-        for (const smafa_hit &h : near) have[h.query]++;
-        std::vector<uint32_t> open;  // positions in the current batch that still need an answer, ascending
-        for (uint32_t q = 0; q < cur_n; q++)
-            if (have[q] < k_mode) open.push_back(q);
-        if (open.size() == cur_n) {
-            if (!planned && cur_n >= 2048 && step + 1 < ladder.size()) {
-                rc = plan_later_steps(step + 1);
-                if (rc) return rc;
-                continue;
-            }
-            break;
-        }
-        std::vector<smafa_hit> fin;
-        fin.reserve(near.size());
-        for (smafa_hit h : near)
-            if (have[h.query] >= k_mode) {
-                if (!ids.empty()) h.query = ids[h.query];  // ascending map: the order is kept
-                fin.push_back(h);
-            }
-        merge_done(fin);
-        log_line(2, "near-hit step at bound %u finished %u of %u queries", bound, cur_n - (uint32_t)open.size(), cur_n);
-        // (the step at 30 costs half of what the loose path costs: it is taken only after a step that finished a quarter)
-        const bool paid = (uint64_t)(cur_n - open.size()) * (step + 1 < ladder.size() && ladder[step + 1] >= 30u ? 4u : 8u) >= cur_n;
-        std::vector<uint32_t> next_ids(open.size());
-        std::vector<uint8_t> next_codes(open.size() * (size_t)db->L);
-        for (size_t i = 0; i < open.size(); i++) {
-            next_ids[i] = ids.empty() ? open[i] : ids[open[i]];
-            memcpy(&next_codes[i * db->L], cur + (size_t)open[i] * db->L, db->L);
-        }
-        ids.swap(next_ids);
-        open_codes.swap(next_codes);
-        cur = open_codes.data();
-        cur_n = (uint32_t)open.size();
-        if (cur_n == 0) break;
-        rc = qset_fill(&db->scratch_q2, db, cur, cur_n);
-        if (rc) return rc;
-        qs = &db->scratch_q2;
-        if (!planned && cur_n >= 2048 && step + 1 < ladder.size()) {
-            rc = plan_later_steps(step + 1);  // (the sample is drawn from the compacted batch of open queries)
-            if (rc) return rc;
-        } else if (!planned && !paid) {
-            break;  // a small batch: round 2's rule of thumb
-        }
-    }
-    if (cur_n > 0) {
-        std::vector<smafa_hit> far;
-        rc = collect_range(db, qs, 0, cur_n, max_div, max_num_hits, far);
-        if (rc) return rc;
-        if (!ids.empty())
-            for (smafa_hit &h : far) h.query = ids[h.query];
-        merge_done(far);
-    }
-    out.swap(done);
-    if (max_num_hits != SMAFA_NONE && max_num_hits >= 1) {
-        // drop rows above the k-th smallest distance of their query (the device bound only tightens)
-        size_t w = 0, i = 0;
-        while (i < out.size()) {
-            size_t j = i;
-            while (j < out.size() && out[j].query == out[i].query) j++;
-            const size_t cnt = j - i;
-            const uint32_t kth = cnt >= max_num_hits ? out[i + max_num_hits - 1].dist : UINT32_MAX;
-            for (size_t t = i; t < j && out[t].dist <= kth; t++) out[w++] = out[t];
-            i = j;
-        }
-        out.resize(w);
-    }
-    // scratch of an unusually large answer is not worth keeping (the buffers regrow on demand)
-    if (db->scratch.cap > (512ull << 20)) db->scratch.release();
-    if (db->keys_a.cap > (512ull << 20)) {
-        db->keys_a.release();
-        db->keys_b.release();
-        db->sort_tmp.release();
-    }
     return SMAFA_OK;
 }
 

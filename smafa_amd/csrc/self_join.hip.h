@@ -34,8 +34,6 @@ struct JoinConsumer {
     bool used = false;                           // some piece was taken: the kernel belongs on the call's list
 };
 
-#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
-
 static dim3 row_grid(uint32_t n) { return dim3((n + 255u) / 256u); }
 static dim3 list_grid(unsigned long long count) { return dim3((uint32_t)std::min<uint64_t>(2048, (count + 255) / 256)); }
 

@@ -100,7 +100,7 @@ def main(kind):
     def c():
         store = make(kind, 3, 1, s)
         big, big_want = np.ascontiguousarray(np.tile(q, (TILE, 1))), tiled(want, TILE, NQ).tobytes()
-        # rent or buy (engine.hip scan_range): 1.7e-12 ms per pair and stored vector against 0.3 ms + 1e-7 ms per block and subject
+        # rent or buy (kth_plan.h index_rent_charge / index_rent_due): 1.7e-12 ms per pair and stored vector against 0.3 ms + 1e-7 ms per block and subject
         due = int(np.ceil((0.3 + (D + 1) * N * 1.0e-7) / (NQ * TILE * N * planes_words * 1.7e-12)))
         assert 3 <= due < 200, due
         for call in range(due + 3):  # .. the call where the build comes due, and two more

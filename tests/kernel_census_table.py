@@ -38,7 +38,7 @@ L_WIDE = 150  # five words per plane
 
 
 def ladder_top(kind, L):
-    """the last bound of the near-hit ladder (engine.hip scan_to_host) for a batch under 2048 queries"""
+    """the last bound of the near-hit ladder (kth_plan.h ladder_bounds) for a batch under 2048 queries"""
     cols = min(32, L)
     top = 3 * cols // 8
     if (L + 31) // 32 == 2 and L >= 33:

@@ -1,5 +1,5 @@
-"""Stores and planted queries for the sampled counting path of the k-th distance modes (engine.hip scan_range with
-sample_tiles != 0: kth_seed_kernel counting a sample, kth_from_counts_kernel, one counting-and-appending pass over the rest,
+"""Stores and planted queries for the sampled counting path of the k-th distance modes (scan_host.hip.h scan_kth with
+kth_sample_tiles != 0: kth_seed_kernel counting a sample, kth_from_counts_kernel, one counting-and-appending pass over the rest,
 the sample's tiles again, filter_rows_kernel).  Used by tests/test_kth_sample_model.py (CPU: the planted structure is what
 this text says, by brute force) and tests/test_gpu_kth_sample.py (GPU: rows == the oracle's).  Test helpers only.
 
@@ -60,7 +60,7 @@ SEED_BINS = 256       # kernels.hip.h kSeedBins: rows of up to 255 columns are c
 
 
 def seed_kernel(kind, L):
-    """the kth_seed_kernel instantiation of a shape (engine.hip launch_hist), None where the histogram is not used"""
+    """the kth_seed_kernel instantiation of a shape (scan_host.hip.h launch_kth_hist), None where the histogram is not used"""
     if L >= SEED_BINS:
         return None
     W = (L + 31) // 32
@@ -69,7 +69,7 @@ def seed_kernel(kind, L):
 
 
 def level1_prunes(L, bound, prune_p=2e-3):
-    """mirror of engine.hip prefilter_prunes: the k-th modes count first only where this is false"""
+    """mirror of scan_plan.h prefilter_prunes (kth_plan.h kth_count_first): the k-th modes count first only where this is false"""
     cols = min(32, L)
     if bound >= cols:
         return False

@@ -123,7 +123,7 @@ def test_mode_3_fixed_bound_rents_then_buys(auto_env, kind, L):
     D, nq0 = 3, 256
     s, q0 = make(kind, L, 300 + L, nq=nq0, max_subs=5)
     vectors = KINDS[kind][1] * ((L + 31) // 32)
-    # rent or buy (engine.hip scan_range): every eligible scan is charged nq x n x (planes x words) x 1.7e-12 ms, and the index
+    # rent or buy (kth_plan.h index_rent_charge / index_rent_due): every eligible scan is charged nq x n x (planes x words) x 1.7e-12 ms, and the index
     # is built by the call at which the sum reaches 0.3 ms + (D + 1) blocks x n x 1e-7 ms = 0.3024 ms.  The batch is the 256
     # queries `times` over (the rows of a copy are the oracle's with the query number shifted), as many times as bring the
     # build to about the 100th call: a two-plane one-word store needs 579 copies, 148 224 queries, a five-plane four-word one 57.

@@ -1,5 +1,5 @@
-"""The sampled counting path of the k-th distance modes (k >= 3 without a bound level 1 prunes at; engine.hip scan_range with
-sample_tiles != 0) below benchmark size, on the planted stores of tests/kth_sample_cases.py (checked on the CPU by
+"""The sampled counting path of the k-th distance modes (k >= 3 without a bound level 1 prunes at; scan_host.hip.h scan_kth with
+kth_sample_tiles != 0) below benchmark size, on the planted stores of tests/kth_sample_cases.py (checked on the CPU by
 tests/test_kth_sample_model.py): kth_seed_kernel counting a whole sample into cnt[q][d] — every instantiation, the run-time
 shape one included —, kth_from_counts_kernel, the one counting-and-appending pass over the rest, the sample's tiles again,
 filter_rows_kernel.  Rows are compared byte for byte with the oracle's, and the call's kernel list says which form ran

@@ -192,7 +192,7 @@ def test_kth_bound_modes(k, max_div):
 def test_kth_modes_counting_a_sample_first(alphabet, n_letters, div, hist_seed, monkeypatch):
     """k >= 3 without a usable bound: the counting pass covers the first 1/div of the tiles only (an upper bound of every
     query's k-th distance), the rest of the store is counted, tightened and appended in one pass, the exact bounds come from
-    the complete counts and the sample's tiles are scanned again with them (engine.hip scan_range).  Forced here on a small
+    the complete counts and the sample's tiles are scanned again with them (scan_host.hip.h scan_kth, kth_plan.h kth_schedule).  Forced here on a small
     store (SMAFA_KTH_SAMPLE_MIN_TILES; div 0 = everything counted first): rows == the oracle's, ties, dense spots, bounds."""
     monkeypatch.setenv("SMAFA_KTH_SAMPLE", str(div))
     monkeypatch.setenv("SMAFA_KTH_HIST_SEED", str(hist_seed))  # the seed bound: LDS histogram over the first tiles / a counting launch
@@ -331,7 +331,7 @@ def test_dense_hits_overflow_path():
     store.close()
 
 
-# Host answers to a full row list (engine.hip collect_range / scan_to_host / filter_rows_kernel) at their real sizes: the list
+# Host answers to a full row list (scan_host.hip.h collect_range / scan_to_host, filter_rows_kernel) at their real sizes: the list
 # starts at 2^22 rows, the tightening scratch holds max(2 cap, min(nq * 128, 2^27)) rows.  The buffers only grow on a handle,
 # so each scenario has a fresh store.  Every scenario proves its path by the number of scans of the call.
 LIST = 1 << 22
@@ -904,7 +904,7 @@ def test_big_fastq_and_gzip_query_files_take_the_threaded_loader(tmp_path):
 @pytest.mark.parametrize("alphabet,n_letters", [(0, 4), (1, 20)])
 def test_near_hit_ladder_planned_from_a_sample(alphabet, n_letters):
     """the k-th-distance modes without a tight bound on a BIG query batch: after the first bounded step the later steps are
-    chosen from a sample of the open queries (engine.hip plan_later_steps) — near, middling (8..20 columns away) and
+    chosen from a sample of the open queries (scan_host.hip.h plan_later, kth_plan.h choose_later_steps) — near, middling (8..20 columns away) and
     unrelated queries mixed; every mix against the exhaustive answer (all distances, numpy, the k-th rule of
     src/lib.rs:250-262 applied to them)"""
     rng = np.random.default_rng(77 + alphabet)

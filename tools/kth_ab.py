@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of the k-th modes without a bound (`smafa query --max-num-hits k`, src/lib.rs:242-295) on the metric's store:
-SMAFA_KTH_SAMPLE = 0 (count every pair first, append in a second pass) against 1/div samples (engine.hip scan_range).
+SMAFA_KTH_SAMPLE = 0 (count every pair first, append in a second pass) against 1/div samples (scan_host.hip.h scan_kth).
     python3 tools/kth_ab.py [aa|nt] [queries]   -> one line per (div, k): wall / kernel ms of smafa_scan_hits, rows; rows must agree"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
