@@ -322,6 +322,52 @@ int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, u
 int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components);
 int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
 
+/* ------------------------------------------------- minimum spanning forest: the merge tree of single linkage */
+/*
+ * "Which pair joined them, and at which bound": smafa_db_self_levels says which rows belong together at every bound
+ * t = 0 .. max_div, as (max_div + 1) x n_subjects labels; this call gives the same hierarchy as the TREE behind it, at most
+ * n_subjects - 1 edges of 12 bytes: what a dendrogram, a cut at a height chosen afterwards or a linkage matrix is made from.
+ * The graph is the one of smafa_db_self_components — vertices the store's subjects, edges the pairs within max_div — with an
+ * edge's weight its distance, and the result is a minimum spanning forest of it:
+ *   edges       smafa_hit{query = a, subject = b, dist}, a < b, dist = the true distance of subjects a and b, ordered by dist
+ *               ascending;
+ *   level_ends  max_div + 1 uint64: level_ends[t] = the number of edges with dist <= t.
+ * For every t the edges [0, level_ends[t]) are acyclic and their connected components are exactly the components of
+ * smafa_db_self_components(db, t); hence level_ends[t] = n_subjects - n_components[t], and level_ends[max_div] is the number
+ * of edges written.  WHICH of several edges of equal weight is chosen is not fixed and may differ from run to run and
+ * between settings; the number of edges per level and the partitions after every level are functions of the store alone,
+ * the same under smafa_set_prefilter / smafa_set_zone_level / smafa_set_index and every SMAFA_JOIN_* setting.  Not in the
+ * reference.
+ * The store is joined ONCE, at bound min(max_div, seq_len - 1); the join only moves its pairs, each once, to a handle-owned
+ * list on the device (12 B per pair, at most SMAFA_DENSITY_KEEP_MAX rows — the list and the knob of smafa_db_self_density).
+ * Kruskal's algorithm then runs by weight class on the device: one launch per distance 0, 1, .. over that list, a concurrent
+ * union-find (4 B per subject) in which the lane whose own compare-and-swap hooked two sets together writes the edge.  Where
+ * the pairs exceed the list, the store is instead joined once more per class, at the bounds 0, 1, ..: the same forest
+ * property at the cost of those joins.  The pairs never leave the device.
+ * Bounds no two rows can exceed (max_div >= seq_len): the components call says "one component" there, and the forest is a
+ * spanning tree — after the level seq_len - 1 every remaining component's smallest subject r != 0 gets the edge
+ * (0, r, seq_len), whose distance is exactly seq_len, and level_ends[t] = n_subjects - 1 for t >= seq_len.  Nothing is
+ * scanned above seq_len - 1.
+ * An empty store or one row gives no edge and level_ends all 0 (nothing is scanned); max_div = SMAFA_NONE, a NULL handle,
+ * NULL edges or NULL level_ends is SMAFA_ERR_INVALID, and smafa_last_error() names the argument.  The self-join's one failure
+ * is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list; the handle stays usable); a partial
+ * list is never spanned.
+ *
+ * smafa_db_self_forest_launch: device-resident form.  d_edges = device buffer of n_subjects - 1 smafa_hit (fewer are
+ * written where the forest has several trees; the edges inside a level are in no particular order), d_level_ends = device
+ * buffer of max_div + 1 uint64.  Synchronisation as for smafa_db_self_components_launch.  smafa_last_scan_ms /
+ * smafa_last_call_stats hold the device time and launches of record building, scans, keep passes, the span launches and the
+ * star launch; smafa_last_call_kernels lists the scan-family instantiations first, then smafa_join::store_records_kernel and
+ * smafa_join::inverse_order_kernel where it ran, then the smafa_sf:: kernels that ran.  No smafa_cc::, smafa_lv:: or
+ * smafa_dn:: kernel is launched.
+ *
+ * smafa_db_self_forest: host form.  cap = capacity of `edges` in rows; cap < n_subjects - 1 is SMAFA_ERR_INVALID and nothing
+ * is written.  The edges of one level are additionally ordered by (query, subject), so a given forest prints one way;
+ * level_ends holds max_div + 1 entries.
+ */
+int smafa_db_self_forest_launch(smafa_db *db, uint32_t max_div, void *d_edges /* n_subjects - 1 smafa_hit */, void *d_level_ends /* max_div + 1 uint64 */);
+int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint64_t cap, uint64_t *level_ends);
+
 /* ------------------------------------------------- density clusters of the store (DBSCAN over the self-join) */
 /*
  * "Which of the store's rows belong together at bound max_div, where enough rows agree": single linkage chains — one sparse
@@ -663,6 +709,11 @@ int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, i
  * max_divergence (smafa_db_self_levels), "{i}\t{label_0}\t...\t{label_N}\n" in subject order.  Column t + 1 is the label
  * column of smafa_components at bound t.  An empty DB prints nothing. */
 int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa forest` (not in the reference): the same DB, and the minimum spanning forest of its subjects up to max_divergence
+ * (smafa_db_self_forest), "{a}\t{b}\t{distance}\n" per edge, a < b, ordered by distance, then a, then b.  The lines with
+ * distance <= t are the merge tree of `smafa components --max-divergence t`; which of several pairs of equal distance joins
+ * two components may differ from run to run.  An empty DB prints nothing. */
+int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int device);
 /* `smafa density` (not in the reference): the same DB, and per subject its density-cluster label and its degree
  * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
  * is printed as -1.  An empty DB prints nothing. */

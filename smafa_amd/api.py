@@ -378,6 +378,29 @@ class SubjectStore:
                                                     C.c_void_p(d_dists) if d_dists else None, cap,
                                                     C.c_void_p(d_total) if d_total else None))
 
+    # ---- minimum spanning forest -----------------------------------------------------------
+    def self_forest(self, max_divergence: int) -> tuple[np.ndarray, np.ndarray]:
+        """(edges, level_ends) — smafa_db_self_forest: a minimum spanning forest of the graph whose edges are the store's pairs
+        within max_divergence, weighted by distance: the merge tree of single linkage.  edges are rows as self_pairs gives them
+        (query = a < subject = b, dist = their distance), ordered by (dist, query, subject); level_ends (uint64, max_divergence
+        + 1) counts the edges with dist <= t.  The edges [0, level_ends[t]) are acyclic and connect exactly the components of
+        self_components(t), so level_ends[t] = n_subjects - n_components[t].  Which of several pairs of equal distance is
+        chosen may differ from run to run; the counts and the partitions do not.  forest_linkage makes a linkage matrix of
+        them.  The pairs stay on the device."""
+        n = self.info().n_subjects
+        levels = int(max_divergence) + 1 if max_divergence is not None and 0 <= int(max_divergence) < _lib.NONE else 1
+        edges = np.zeros(max(n - 1, 1), dtype=HIT_DTYPE)
+        level_ends = np.zeros(levels, dtype=np.uint64)
+        check(lib().smafa_db_self_forest(self._h, _opt(max_divergence), edges.ctypes.data, max(n - 1, 0),
+                                         level_ends.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return edges[: int(level_ends[-1])], level_ends
+
+    def self_forest_launch(self, max_divergence: int, d_edges: int, d_level_ends: int) -> None:
+        """device-resident form (smafa_db_self_forest_launch): up to n_subjects - 1 rows of three uint32 in d_edges, ordered by
+        distance, max_divergence + 1 level ends in d_level_ends (device uint64 each); the last of them is the number of rows"""
+        check(lib().smafa_db_self_forest_launch(self._h, _opt(max_divergence), C.c_void_p(d_edges) if d_edges else None,
+                                                C.c_void_p(d_level_ends) if d_level_ends else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -679,3 +702,59 @@ def component_levels(db_path: str, max_divergence: int, out_fd: int = 1, device:
     """`smafa components --levels`: "i\\tlabel_0\\t...\\tlabel_N" per subject of the DB file, label_t = its label at bound t, to
     out_fd."""
     check(lib().smafa_component_levels(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def forest(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa forest`: "a\\tb\\tdist" per edge of a minimum spanning forest of the DB file's subjects up to max_divergence
+    (smafa_db_self_forest), ordered by (dist, a, b), to out_fd."""
+    check(lib().smafa_forest(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:
+    """The linkage matrix of a forest, numpy only: (n - 1, 4) float64 rows [id_a, id_b, height, size] in the layout
+    scipy.cluster.hierarchy documents — the rows 0 .. n - 1 are clusters 0 .. n - 1, merge k makes cluster n + k, id_a < id_b
+    are the two clusters it joins, size the rows of the new one.  `edges` (SubjectStore.self_forest's rows, or an (m, 3) array
+    of a, b, dist) are taken in the order given, each at height dist; an edge inside one cluster is an error.  Trees left
+    apart at the bound — no pair within max_divergence joins them — are then merged at height max_divergence + 1, in order
+    of their smallest member: a cut at any height <= max_divergence never sees those merges."""
+    n = int(n)
+    if isinstance(edges, np.ndarray) and edges.dtype.names:
+        a, b, d = (np.asarray(edges[k]).reshape(-1) for k in ("query", "subject", "dist"))
+    else:
+        rows = np.asarray(edges).reshape(-1, 3)
+        a, b, d = rows[:, 0], rows[:, 1], rows[:, 2]
+    parent = list(range(n))                # union-find over the rows
+    cluster = list(range(n))               # root row -> the id of its cluster
+    size = [1] * n
+    smallest = list(range(n))              # root row -> the smallest row of its cluster
+    out = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
+    merges = 0
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    def merge(ra, rb, height):
+        nonlocal merges
+        if size[ra] < size[rb]:
+            ra, rb = rb, ra
+        parent[rb] = ra
+        out[merges] = (min(cluster[ra], cluster[rb]), max(cluster[ra], cluster[rb]), height, size[ra] + size[rb])
+        size[ra] += size[rb]
+        smallest[ra] = min(smallest[ra], smallest[rb])
+        cluster[ra] = n + merges
+        merges += 1
+
+    for x, y, h in zip(a.tolist(), b.tolist(), d.tolist()):
+        if not (0 <= x < n and 0 <= y < n):
+            raise ValueError("edge (%d, %d) names a row outside 0 .. %d" % (x, y, n - 1))
+        rx, ry = find(x), find(y)
+        if rx == ry:
+            raise ValueError("edge (%d, %d) closes a cycle: the edges are no forest" % (x, y))
+        merge(rx, ry, float(h))
+    roots = sorted({find(i) for i in range(n)}, key=lambda r: smallest[r])
+    for r in roots[1:]:
+        merge(find(roots[0]), r, float(int(max_divergence) + 1))
+    return out

@@ -27,6 +27,7 @@
 #include "peaks.hip.h"
 #include "neighbours.hip.h"
 #include "delta.hip.h"
+#include "forest.hip.h"
 
 namespace smafa {
 
@@ -220,6 +221,9 @@ struct smafa_db {
         // delta join (delta.hip.h): the subject numbers of the new rows, 4 B each — the order[] of its pieces; ctl[0] counts the
         // labels seed_parents_kernel refused
         DevBuf rows;
+        // forest (forest.hip.h): parent holds one union-find, 4 B per subject, live for one call; kept as for density; ctl[0] is the
+        // kept total, ctl[1] the running edge total; count_ms (keep passes), link_ms (init + span launches), flatten_ms (the star
+        // launch) and joins (1, or 1 + the scanned classes on the slow path)
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1807,6 +1811,54 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_levels");
+}
+
+int smafa_db_self_forest_launch(smafa_db *db, uint32_t max_div, void *d_edges, void *d_level_ends) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL handle");
+    if (!d_edges) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL edges");
+    if (!d_level_ends) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL level_ends");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: a forest needs a bound (max_div)");
+    return join_forest(db, max_div, (smafa_hit *)d_edges, (unsigned long long *)d_level_ends);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_forest_launch");
+}
+
+int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint64_t cap, uint64_t *level_ends) try {
+    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL handle");
+    if (!edges) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL edges");
+    if (!level_ends) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL level_ends");
+    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: a forest needs a bound (max_div)");
+    const uint64_t T = (uint64_t)max_div + 1u, room = db->n ? db->n - 1 : 0;
+    if (cap < room)  // (nothing is written, level_ends included)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: edges holds %llu rows, a forest of %llu subjects may need %llu",
+                         (unsigned long long)cap, (unsigned long long)db->n, (unsigned long long)room);
+    std::fill(level_ends, level_ends + T, (uint64_t)0);
+    int rc = use_device(db);
+    if (rc) return rc;
+    auto &J = db->join;
+    rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));  // the edges on their way to the caller
+    if (!rc) rc = J.cnt.ensure(T * sizeof(unsigned long long));
+    if (rc) return rc;
+    rc = join_forest(db, max_div, J.out.as<smafa_hit>(), J.cnt.as<unsigned long long>());
+    if (rc) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
+    HIP_TRY(hipMemcpyAsync(level_ends, J.cnt.p, T * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    const uint64_t total = level_ends[T - 1];
+    if (total > room) return set_error(SMAFA_ERR_DEVICE, "smafa_db_self_forest: %llu edges among %llu subjects are no forest",
+                                       (unsigned long long)total, (unsigned long long)db->n);
+    if (total) HIP_TRY(hipMemcpyAsync(edges, J.out.p, total * sizeof(smafa_hit), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    // a level's edges arrive in any order: (query, subject) inside each level, so that a given forest prints one way
+    for (uint64_t t = 0, begin = 0; t < T && begin < total; begin = level_ends[t++])
+        std::sort(edges + begin, edges + level_ends[t], [](const smafa_hit &x, const smafa_hit &y) {
+            return x.query != y.query ? x.query < y.query : x.subject < y.subject;
+        });
+    if (db->hits.cap > (512ull << 20)) db->hits.release();
+    if (J.kept.cap > (512ull << 20)) J.kept.release();
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_forest");
 }
 
 int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_labels, void *d_degrees,

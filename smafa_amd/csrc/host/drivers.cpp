@@ -752,6 +752,48 @@ int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out
     return smafa::exception_code("smafa_component_levels");
 }
 
+// ------------------------------------------------------------------------------------ forest
+// The minimum spanning forest of a DB file's subjects up to max_divergence (smafa_db_self_forest), printed
+// "{a}\t{b}\t{distance}\n" per edge in the host form's order: by distance, then a, then b.
+int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_forest: NULL path");
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_forest: a bound (max_divergence) is needed");
+    const double t_start = now_seconds();
+    DbGuard store;
+    bool empty = false;
+    int rc = load_db_store(db_path, device, &store, &empty);
+    if (rc || empty) return rc;
+    smafa_db_info_t info;
+    rc = smafa_db_info(store.db, &info);
+    if (rc) return rc;
+    const size_t n = (size_t)info.n_subjects, T = (size_t)max_divergence + 1;
+    std::vector<smafa_hit> edges(std::max<size_t>(n, 2) - 1);  // (one row at least: the call takes no NULL buffer)
+    std::vector<uint64_t> level_ends(T);
+    rc = smafa_db_self_forest(store.db, max_divergence, edges.data(), edges.size(), level_ends.data());
+    if (rc) return rc;
+    const size_t count = (size_t)level_ends[T - 1];
+    std::string text;
+    const size_t block = (size_t)1 << 18;  // rows per write
+    for (size_t b0 = 0; b0 < count; b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min<size_t>(count, b0 + block); i < e; i++) {
+            append_u32(text, edges[i].query);
+            text.push_back('\t');
+            append_u32(text, edges[i].subject);
+            text.push_back('\t');
+            append_u32(text, edges[i].dist);
+            text.push_back('\n');
+        }
+        rc = write_all(out_fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    log_line(1, "%llu edges among %llu sequences within %u, took %llu seconds", (unsigned long long)count, (unsigned long long)n,
+             max_divergence, (unsigned long long)(now_seconds() - t_start));
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_forest");
+}
+
 // ------------------------------------------------------------------------------------ density
 // The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
 // "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.

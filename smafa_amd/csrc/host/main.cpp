@@ -9,6 +9,8 @@
 //           within the bound; --since: those whose larger sequence number is at least ROW)
 //   components -d/--database FILE  --max-divergence INT  [--levels]   (this build only: the single-linkage component of
 //           every subject; --levels: at every bound 0 .. INT)
+//   forest  -d/--database FILE  --max-divergence INT   (this build only: the minimum spanning forest of the subjects up to
+//           the bound, the merge tree of the components at every bound 0 .. INT)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
@@ -57,6 +59,10 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
             "        smallest sequence number of its component; --levels: one label column per bound 0 .. <INT>,\n"
             "        \"i<TAB>label_0<TAB>...<TAB>label_INT\", from one join)\n"
+            "forest  -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: a minimum spanning forest of\n"
+            "        the database's own sequences under the pairs within the bound, one \"a<TAB>b<TAB>divergence\" line per edge, a < b,\n"
+            "        ordered by divergence, then a, then b; the lines up to divergence t are the merge tree of `components` at t;\n"
+            "        which of several pairs of equal divergence joins two components may differ from run to run)\n"
             "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
@@ -224,6 +230,10 @@ int main(int argc, char **argv) {
         if (!database) return usage("components needs --database");
         if (!have_max_div) return usage("components needs --max-divergence");
         rc = levels ? smafa_component_levels(database, max_div, 1, (int)device) : smafa_components(database, max_div, 1, (int)device);
+    } else if (cmd == "forest") {
+        if (!database) return usage("forest needs --database");
+        if (!have_max_div) return usage("forest needs --max-divergence");
+        rc = smafa_forest(database, max_div, 1, (int)device);
     } else if (cmd == "density") {
         if (!database) return usage("density needs --database");
         if (!have_max_div) return usage("density needs --max-divergence");

@@ -1,6 +1,6 @@
 // self_join.hip.h — host code of the self-join of a resident store: one driver that walks the store and knows no consumer
-// (join_pass), and the six calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks,
-// join_neighbours); and the driver of the delta join (delta_pass: the rows appended since a mark against the whole store), with
+// (join_pass), and the seven calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks,
+// join_neighbours, join_forest); and the driver of the delta join (delta_pass: the rows appended since a mark against the whole store), with
 // its two calls (delta_pairs, delta_components).  Both drivers scan their pieces through one loop, join_pieces.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
 #pragma once
@@ -846,6 +846,87 @@ static int join_neighbours(smafa_db *db, uint32_t max_div, uint32_t k, unsigned 
              entries && key.sorts == 1u ? "" : "s", J.link_ms, J.flatten_ms, entries, total, J.growths);
     if (!fits)
         return set_error(SMAFA_ERR_CAPACITY, "neighbour lists too small: %llu entries needed, capacity %llu", total, (unsigned long long)cap);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_forest_launch (forest.hip.h): d_edges is n - 1 rows, d_level_ends max_div + 1 counters, J.parent one union-find,
+// J.ctl the kept total and the running edge total.  The join runs ONCE at bound E - 1 (E = min(max_div, L - 1) + 1 scanned
+// classes, as join_levels) with keep_pairs_kernel per piece (the exactly-once rule, so pos_of[]), which only moves the kept
+// pairs to J.kept; the kept total then decides (kept_plan) how span_edges_kernel gets them: E launches over the kept list, one
+// per weight class — Kruskal by class, a kernel boundary between two classes — or, where the list could not hold every
+// pair, the store joined once more PER CLASS, at bound t with the raw piece lists spanned at only_dist = t (the slow path: the
+// sum of the joins at 0 .. E - 1).  Behind class t the running edge total is copied into level_ends[t] on the stream.
+// max_div >= L: star_roots_kernel hangs every surviving root under row 0 and fills level_ends[L ..].
+static int join_forest(smafa_db *db, uint32_t max_div, smafa_hit *d_edges, unsigned long long *d_level_ends) {
+    auto &J = db->join;
+    const uint32_t n_levels = max_div + 1u, E = std::min(n_levels, std::max<uint32_t>(db->L, 1u)), scan_div = E - 1u;
+    const bool all_near = max_div >= db->L;
+    JoinCall c{db};
+    RC_TRY(join_begin(c, d_level_ends, n_levels, 2));
+    if (c.nothing) return SMAFA_OK;  // no row, or one: no edge, every level ends at 0
+    const uint32_t n = (uint32_t)db->n;
+    const unsigned long long room = n - 1u;
+    RC_TRY(J.parent.ensure((size_t)n * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(2 * sizeof(unsigned long long)));
+    uint32_t *const parent = J.parent.as<uint32_t>();
+    unsigned long long *const n_edges = J.ctl.as<unsigned long long>() + 1;
+    RC_TRY(timed_begin(c, &J.link_ms, "forest: parent[] initialised"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 2 * sizeof(unsigned long long), db->stream));
+    hipLaunchKernelGGL(smafa_sf::init_forest_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n);
+    RC_TRY(timed_end(c));
+    RC_TRY(join_positions(c));
+    JoinConsumer keep = keeping_consumer(c, &J.count_ms, "forest: parent[] untouched, a piece's rows kept", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_sf::keep_pairs_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, J.pos_of.as<uint32_t>(), J.kept.as<smafa_hit>(), (unsigned long long)kept_room(db),
+                           J.ctl.as<unsigned long long>());
+    });
+    uint32_t only_dist = 0;  // the class the span launches handle
+    const auto launch_span = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_sf::span_edges_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, parent, only_dist, d_edges, room, n_edges);
+    };
+    const auto end_class = [&] {  // (stream-ordered: behind the class's last launch, in front of the next class's first)
+        HIP_TRY(hipMemcpyAsync(d_level_ends + only_dist, n_edges, sizeof(unsigned long long), hipMemcpyDeviceToDevice, db->stream));
+        return SMAFA_OK;
+    };
+    JoinConsumer span = timed_consumer(c, &J.link_ms, "forest: a class of a piece's rows spanned", launch_span);
+    RC_TRY(join_pass(c, scan_div, keep));
+    unsigned long long kept_total = 0;
+    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    const KeptPlan plan = kept_plan(db, kept_total, "forest", "span");
+    if (plan == kKeptOnce) {
+        RC_TRY(timed_begin(c, &J.link_ms, "forest: the kept list spanned, class by class"));
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            launch_span(kept_piece(db, kept_total));
+            RC_TRY(end_class());
+        }
+        RC_TRY(timed_end(c, E));
+        span.used = true;
+    } else if (plan == kKeptJoinAgain) {
+        log_line(2, "forest: %llu pairs, the kept list holds %llu: the store is joined once more per class, at the bounds 0 .. %u",
+                 kept_total, (unsigned long long)kept_room(db), scan_div);
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            RC_TRY(join_pass(c, only_dist, span));
+            RC_TRY(end_class());
+        }
+    }
+    RC_TRY(timed_sync(c));
+    if (all_near) {
+        RC_TRY(timed_pass(c, &J.flatten_ms, "forest: the surviving roots hung under row 0", [&] {
+            hipLaunchKernelGGL(smafa_sf::star_roots_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n, db->L, d_edges, room, n_edges,
+                               d_level_ends, n_levels);
+        }));
+        RC_TRY(timed_sync(c));
+    }
+    join_finish(c);
+    note_call_kernel(db, "smafa_sf::init_forest_kernel");
+    if (keep.used) note_call_kernel(db, "smafa_sf::keep_pairs_kernel");
+    if (span.used) note_call_kernel(db, "smafa_sf::span_edges_kernel");
+    if (all_near) note_call_kernel(db, "smafa_sf::star_roots_kernel");
+    log_line(2, "forest of %u rows up to bound %u, joined at bound %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, "
+             "scans %.3f ms, keep %.3f ms, span %.3f ms, star %.3f ms, %llu pairs kept", n, max_div, scan_div, J.blocks + J.rescans, J.rescans,
+             J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, kept_total);
     return SMAFA_OK;
 }
 #undef RC_TRY
