@@ -67,6 +67,20 @@ struct DevBuf {
     T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// Scratch of an unusually large answer is not worth keeping (the buffers regrow on demand): behind a call, each of `bufs` that has
+// grown past kTrimBytes is released (trim) — or all of `rest` with `lead`, where `lead` has (trim_together: the sort's buffers).
+// Which buffers a call names decides what the next call allocates.
+constexpr size_t kTrimBytes = 512ull << 20;
+static void trim(std::initializer_list<DevBuf *> bufs) {
+    for (DevBuf *b : bufs)
+        if (b->cap > kTrimBytes) b->release();
+}
+static void trim_together(DevBuf &lead, std::initializer_list<DevBuf *> rest) {
+    if (lead.cap <= kTrimBytes) return;
+    lead.release();
+    for (DevBuf *b : rest) b->release();
+}
+
 }  // namespace smafa
 
 using namespace smafa;
@@ -1592,431 +1606,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
     return smafa::exception_code("smafa_scan_hits");
 }
 
-int smafa_db_self_launch(smafa_db *db, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL handle");
-    if (!d_count) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL count");
-    if (!d_hits && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: NULL row buffer with a capacity");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_launch: a self-join needs a bound (max_div)");
-    return join_pairs(db, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_launch");
-}
-
-// The host form of a pair-list call: `join` fills J.out (room rows: cap, or all_pairs if that is less) and J.cnt on the device;
-// the count comes back, then — where it fits cap — the rows, ordered (query, dist, subject) on the device or the host.
-static int pairs_to_host(smafa_db *db, uint64_t all_pairs, smafa_hit *out, uint64_t cap, uint64_t *n_out,
-                         const std::function<int(smafa_hit *, uint64_t, unsigned long long *)> &join) {
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    const uint64_t room = std::min<uint64_t>(cap, all_pairs);
-    rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));
-    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join(J.out.as<smafa_hit>(), room, J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    unsigned long long count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    *n_out = count;
-    if (count > cap)
-        return set_error(SMAFA_ERR_CAPACITY, "hit buffer too small: %llu rows needed, capacity %llu", count, (unsigned long long)cap);
-    if (count) {
-        bool sorted = false;
-        if (count >= 4096) {
-            rc = sort_rows_on_device(db, count, 0, (uint32_t)db->n, &sorted, J.out.as<smafa_hit>());
-            if (rc) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(out, J.out.p, count * sizeof(smafa_hit), hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        if (!sorted) std::sort(out, out + count, hit_less);
-    }
-    if (J.out.cap > (512ull << 20)) J.out.release();
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    if (db->keys_a.cap > (512ull << 20)) {
-        db->keys_a.release();
-        db->keys_b.release();
-        db->sort_tmp.release();
-    }
-    return SMAFA_OK;
-}
-
-int smafa_db_self_hits(smafa_db *db, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL handle");
-    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL count");
-    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: NULL row buffer with a capacity");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits: a self-join needs a bound (max_div)");
-    *n_out = 0;
-    const uint64_t all_pairs = db->n < 2 ? 0 : db->n * (db->n - 1) / 2;
-    return pairs_to_host(db, all_pairs, out, cap, n_out, [&](smafa_hit *d_hits, uint64_t room, unsigned long long *d_count) {
-        return join_pairs(db, max_div, d_hits, room, d_count);
-    });
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_hits");
-}
-
-int smafa_db_self_components_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL handle");
-    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL labels");
-    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: NULL count");
-    if (max_div == SMAFA_NONE)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_launch: components need a bound (max_div)");
-    return join_components(db, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_components_launch");
-}
-
-int smafa_db_self_components(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL handle");
-    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL labels");
-    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: NULL count");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: components need a bound (max_div)");
-    *n_components = 0;
-    if (cap < db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components: labels holds %llu entries, the store has %llu subjects",
-                         (unsigned long long)cap, (unsigned long long)db->n);
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    rc = J.out.ensure(std::max<uint64_t>(db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller: 4 B per subject
-    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join_components(db, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    unsigned long long count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    *n_components = count;
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_components");
-}
-
-int smafa_db_self_since_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_hits, uint64_t cap, void *d_count) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL handle");
-    if (!d_count) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL count");
-    if (!d_hits && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: NULL row buffer with a capacity");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: a self-join needs a bound (max_div)");
-    if (first_row > db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_since_launch: first_row %llu, the store has %llu subjects",
-                         (unsigned long long)first_row, (unsigned long long)db->n);
-    return delta_pairs(db, (uint32_t)first_row, max_div, (smafa_hit *)d_hits, cap, (unsigned long long *)d_count);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_since_launch");
-}
-
-int smafa_db_self_hits_since(smafa_db *db, uint64_t first_row, uint32_t max_div, smafa_hit *out, uint64_t cap, uint64_t *n_out) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL handle");
-    if (!n_out) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL count");
-    if (!out && cap) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: NULL row buffer with a capacity");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: a self-join needs a bound (max_div)");
-    *n_out = 0;
-    if (first_row > db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_hits_since: first_row %llu, the store has %llu subjects",
-                         (unsigned long long)first_row, (unsigned long long)db->n);
-    // pairs whose larger number is j: j of them, for every new row j
-    const uint64_t all_pairs = (db->n - first_row) * (db->n + first_row - (db->n > first_row ? 1 : 0)) / 2;
-    return pairs_to_host(db, all_pairs, out, cap, n_out, [&](smafa_hit *d_hits, uint64_t room, unsigned long long *d_count) {
-        return delta_pairs(db, (uint32_t)first_row, max_div, d_hits, room, d_count);
-    });
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_hits_since");
-}
-
-int smafa_db_self_components_update_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_labels, void *d_n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL handle");
-    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL labels");
-    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: NULL count");
-    if (max_div == SMAFA_NONE)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: components need a bound (max_div)");
-    if (first_row > db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update_launch: first_row %llu, the store has %llu subjects",
-                         (unsigned long long)first_row, (unsigned long long)db->n);
-    return delta_components(db, (uint32_t)first_row, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_components_update_launch");
-}
-
-int smafa_db_self_components_update(smafa_db *db, uint64_t first_row, uint32_t max_div, uint32_t *labels, uint64_t cap,
-                                    uint64_t *n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL handle");
-    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL labels");
-    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: NULL count");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: components need a bound (max_div)");
-    *n_components = 0;
-    if (first_row > db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: first_row %llu, the store has %llu subjects",
-                         (unsigned long long)first_row, (unsigned long long)db->n);
-    if (cap < db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_components_update: labels holds %llu entries, the store has %llu subjects",
-                         (unsigned long long)cap, (unsigned long long)db->n);
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    rc = J.out.ensure(std::max<uint64_t>(db->n, 1) * sizeof(uint32_t));  // the labels on their way in and out: 4 B per subject
-    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
-    if (rc) return rc;
-    if (first_row) HIP_TRY(hipMemcpyAsync(J.out.p, labels, first_row * sizeof(uint32_t), hipMemcpyHostToDevice, db->stream));
-    rc = delta_components(db, (uint32_t)first_row, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
-    if (rc) return rc;  // (labels[] is as it came)
-    unsigned long long count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    *n_components = count;
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_components_update");
-}
-
-int smafa_db_self_levels_launch(smafa_db *db, uint32_t max_div, void *d_labels, void *d_n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL handle");
-    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL labels");
-    if (!d_n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: NULL count");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels_launch: levels need a bound (max_div)");
-    return join_levels(db, max_div, (uint32_t *)d_labels, (unsigned long long *)d_n_components);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_levels_launch");
-}
-
-int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL handle");
-    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL labels");
-    if (!n_components) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: NULL count");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: levels need a bound (max_div)");
-    const uint64_t T = (uint64_t)max_div + 1u;
-    // (n_subjects < 2^32 and T <= 2^32 - 1: the product cannot wrap)
-    if (cap < T * db->n)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_levels: labels holds %llu entries, %llu levels of %llu subjects need %llu",
-                         (unsigned long long)cap, (unsigned long long)T, (unsigned long long)db->n, (unsigned long long)(T * db->n));
-    std::fill(n_components, n_components + T, (uint64_t)0);
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    rc = J.out.ensure(std::max<uint64_t>(T * db->n, 1) * sizeof(uint32_t));  // the labels on their way to the caller
-    if (!rc) rc = J.cnt.ensure(T * sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join_levels(db, max_div, J.out.as<uint32_t>(), J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
-    HIP_TRY(hipMemcpyAsync(n_components, J.cnt.p, T * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
-    if (db->n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, T * db->n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    if (J.out.cap > (512ull << 20)) J.out.release();
-    if (J.parent.cap > (512ull << 20)) J.parent.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_levels");
-}
-
-int smafa_db_self_forest_launch(smafa_db *db, uint32_t max_div, void *d_edges, void *d_level_ends) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL handle");
-    if (!d_edges) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL edges");
-    if (!d_level_ends) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: NULL level_ends");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest_launch: a forest needs a bound (max_div)");
-    return join_forest(db, max_div, (smafa_hit *)d_edges, (unsigned long long *)d_level_ends);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_forest_launch");
-}
-
-int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint64_t cap, uint64_t *level_ends) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL handle");
-    if (!edges) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL edges");
-    if (!level_ends) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: NULL level_ends");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: a forest needs a bound (max_div)");
-    const uint64_t T = (uint64_t)max_div + 1u, room = db->n ? db->n - 1 : 0;
-    if (cap < room)  // (nothing is written, level_ends included)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_forest: edges holds %llu rows, a forest of %llu subjects may need %llu",
-                         (unsigned long long)cap, (unsigned long long)db->n, (unsigned long long)room);
-    std::fill(level_ends, level_ends + T, (uint64_t)0);
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    rc = J.out.ensure(std::max<uint64_t>(room, 1) * sizeof(smafa_hit));  // the edges on their way to the caller
-    if (!rc) rc = J.cnt.ensure(T * sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join_forest(db, max_div, J.out.as<smafa_hit>(), J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
-    HIP_TRY(hipMemcpyAsync(level_ends, J.cnt.p, T * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    const uint64_t total = level_ends[T - 1];
-    if (total > room) return set_error(SMAFA_ERR_DEVICE, "smafa_db_self_forest: %llu edges among %llu subjects are no forest",
-                                       (unsigned long long)total, (unsigned long long)db->n);
-    if (total) HIP_TRY(hipMemcpyAsync(edges, J.out.p, total * sizeof(smafa_hit), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    // a level's edges arrive in any order: (query, subject) inside each level, so that a given forest prints one way
-    for (uint64_t t = 0, begin = 0; t < T && begin < total; begin = level_ends[t++])
-        std::sort(edges + begin, edges + level_ends[t], [](const smafa_hit &x, const smafa_hit &y) {
-            return x.query != y.query ? x.query < y.query : x.subject < y.subject;
-        });
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    if (J.kept.cap > (512ull << 20)) J.kept.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_forest");
-}
-
-int smafa_db_self_density_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_labels, void *d_degrees,
-                                 void *d_counts) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL handle");
-    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL labels");
-    if (!d_counts) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: NULL counts");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density_launch: density needs a bound (max_div)");
-    return join_density(db, max_div, std::max<uint32_t>(min_pts, 1u), (uint32_t *)d_degrees, (uint32_t *)d_labels, (unsigned long long *)d_counts);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_density_launch");
-}
-
-int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t *labels, uint32_t *degrees, uint64_t cap,
-                          uint64_t counts[3]) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL handle");
-    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL labels");
-    if (!counts) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: NULL counts");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: density needs a bound (max_div)");
-    if (cap < db->n)  // (nothing is written, the counts included)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_density: labels holds %llu entries, the store has %llu subjects",
-                         (unsigned long long)cap, (unsigned long long)db->n);
-    counts[0] = counts[1] = counts[2] = 0;
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    const uint64_t n = db->n;
-    // the labels, and the degrees behind them, on their way to the caller: 4 B (8 B) per subject
-    rc = J.out.ensure(std::max<uint64_t>(n, 1) * (degrees ? 2u : 1u) * sizeof(uint32_t));
-    if (!rc) rc = J.cnt.ensure(3 * sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join_density(db, max_div, std::max<uint32_t>(min_pts, 1u), degrees ? J.out.as<uint32_t>() + n : nullptr, J.out.as<uint32_t>(),
-                      J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters are copied as they lie");
-    HIP_TRY(hipMemcpyAsync(counts, J.cnt.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    if (n && degrees) HIP_TRY(hipMemcpyAsync(degrees, J.out.as<uint32_t>() + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    if (J.kept.cap > (512ull << 20)) J.kept.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_density");
-}
-
-int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, void *d_labels, void *d_parents, void *d_weights,
-                               void *d_n_peaks) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL handle");
-    if (!d_labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL labels");
-    if (!d_n_peaks) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: NULL n_peaks");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: peaks need a bound (max_div)");
-    if (radius != SMAFA_NONE && radius > max_div)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks_launch: radius %u is larger than max_div %u", radius, max_div);
-    return join_peaks(db, max_div, radius == SMAFA_NONE ? max_div : radius, (uint32_t *)d_labels, (uint32_t *)d_parents, (uint32_t *)d_weights,
-                      (unsigned long long *)d_n_peaks);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_peaks_launch");
-}
-
-int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *labels, uint32_t *parents, uint32_t *weights,
-                        uint64_t cap, uint64_t *n_peaks) try {
-    if (!db) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL handle");
-    if (!labels) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL labels");
-    if (!n_peaks) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: NULL n_peaks");
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: peaks need a bound (max_div)");
-    if (radius != SMAFA_NONE && radius > max_div)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: radius %u is larger than max_div %u", radius, max_div);
-    if (cap < db->n)  // (nothing is written, the count included)
-        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_peaks: labels holds %llu entries, the store has %llu subjects",
-                         (unsigned long long)cap, (unsigned long long)db->n);
-    *n_peaks = 0;
-    int rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    const uint64_t n = db->n;
-    // the labels, and the parents and weights behind them, on their way to the caller: 4 B x 3 per subject
-    rc = J.out.ensure(std::max<uint64_t>(n, 1) * 3u * sizeof(uint32_t));
-    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
-    if (rc) return rc;
-    rc = join_peaks(db, max_div, radius == SMAFA_NONE ? max_div : radius, J.out.as<uint32_t>(), parents ? J.out.as<uint32_t>() + n : nullptr,
-                    weights ? J.out.as<uint32_t>() + 2 * n : nullptr, J.cnt.as<unsigned long long>());
-    if (rc) return rc;
-    unsigned long long count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, J.cnt.p, sizeof count, hipMemcpyDeviceToHost, db->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(labels, J.out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    if (n && parents) HIP_TRY(hipMemcpyAsync(parents, J.out.as<uint32_t>() + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    if (n && weights) HIP_TRY(hipMemcpyAsync(weights, J.out.as<uint32_t>() + 2 * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    *n_peaks = count;
-    if (db->hits.cap > (512ull << 20)) db->hits.release();
-    if (J.kept.cap > (512ull << 20)) J.kept.release();
-    return SMAFA_OK;
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_peaks");
-}
-
-// the argument checks the two neighbours calls share (nothing is written before they pass)
-static int neighbours_args(const char *who, const smafa_db *db, uint32_t max_div, uint32_t max_num_hits, const void *offsets,
-                           const void *neighbours, uint64_t cap, const void *total, const char *total_name) {
-    if (!offsets) return set_error(SMAFA_ERR_INVALID, "%s: NULL offsets", who);
-    if (!total) return set_error(SMAFA_ERR_INVALID, "%s: NULL %s", who, total_name);
-    if (!neighbours && cap) return set_error(SMAFA_ERR_INVALID, "%s: NULL neighbours with a capacity", who);
-    if (max_div == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: neighbour lists need a bound (max_div)", who);
-    if (max_num_hits == 0) return set_error(SMAFA_ERR_INVALID, "%s: max_num_hits is 0 (SMAFA_NONE: no cut)", who);
-    if (!db) return set_error(SMAFA_ERR_INVALID, "%s: NULL handle", who);  // (last: the checks above need no handle, and no device)
-    return SMAFA_OK;
-}
-
-int smafa_db_self_neighbours_launch(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, void *d_offsets, void *d_neighbours,
-                                    void *d_dists, uint64_t cap, void *d_total) try {
-    int rc = neighbours_args("smafa_db_self_neighbours_launch", db, max_div, max_num_hits, d_offsets, d_neighbours, cap, d_total, "total");
-    if (rc) return rc;
-    return join_neighbours(db, max_div, max_num_hits, (unsigned long long *)d_offsets, (uint32_t *)d_neighbours, (uint32_t *)d_dists, cap,
-                           (unsigned long long *)d_total);
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_neighbours_launch");
-}
-
-int smafa_db_self_neighbours(smafa_db *db, uint32_t max_div, uint32_t max_num_hits, uint64_t *offsets, uint32_t *neighbours,
-                             uint32_t *dists, uint64_t cap, uint64_t *n_out) try {
-    int rc = neighbours_args("smafa_db_self_neighbours", db, max_div, max_num_hits, offsets, neighbours, cap, n_out, "n_out");
-    if (rc) return rc;
-    *n_out = 0;
-    rc = use_device(db);
-    if (rc) return rc;
-    auto &J = db->join;
-    const uint64_t n = db->n;
-    // no row lists more than the others, or than the cut: beyond that a larger capacity buys nothing
-    const uint64_t room = std::min<uint64_t>(cap, n < 2 ? 0 : n * std::min<uint64_t>(n - 1, max_num_hits));
-    // the offsets, the neighbours and the distances behind them, on their way to the caller
-    rc = J.out.ensure((n + 1) * sizeof(uint64_t) + room * (dists ? 2u : 1u) * sizeof(uint32_t));
-    if (!rc) rc = J.cnt.ensure(sizeof(unsigned long long));
-    if (rc) return rc;
-    unsigned long long *const d_offsets = J.out.as<unsigned long long>();
-    uint32_t *const d_neighbours = reinterpret_cast<uint32_t *>(d_offsets + n + 1), *const d_dists = dists ? d_neighbours + room : nullptr;
-    rc = join_neighbours(db, max_div, max_num_hits, d_offsets, d_neighbours, d_dists, room, J.cnt.as<unsigned long long>());
-    if (rc && rc != SMAFA_ERR_CAPACITY) return rc;
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the offsets are copied as they lie");
-    unsigned long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, J.cnt.p, sizeof total, hipMemcpyDeviceToHost, db->stream));
-    HIP_TRY(hipMemcpyAsync(offsets, d_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, db->stream));
-    if (!rc && total) {
-        HIP_TRY(hipMemcpyAsync(neighbours, d_neighbours, total * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-        if (dists) HIP_TRY(hipMemcpyAsync(dists, d_dists, total * sizeof(uint32_t), hipMemcpyDeviceToHost, db->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    *n_out = total;
-    if (rc)  // (join_neighbours saw `room`; the text names the capacity the caller gave)
-        set_error(SMAFA_ERR_CAPACITY, "neighbour lists too small: %llu entries needed, capacity %llu", total, (unsigned long long)cap);
-    for (DevBuf *b : {&J.out, &db->hits, &J.entries})
-        if (b->cap > (512ull << 20)) b->release();
-    if (db->keys_a.cap > (512ull << 20))
-        for (DevBuf *b : {&db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b, &db->sort_tmp}) b->release();
-    return rc;  // (SMAFA_ERR_CAPACITY: its text stands, the offsets and *n_out are written, the lists are not)
-} catch (...) {
-    return smafa::exception_code("smafa_db_self_neighbours");
-}
+#include "self_join_abi.hip.h"  // the smafa_db_self_* entry points: argument checks, the device-pointer forms, the host forms
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {
     if (!db || !query_codes || (!distances && db->n)) return set_error(SMAFA_ERR_INVALID, "smafa_distances: NULL argument");

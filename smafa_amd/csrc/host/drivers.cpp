@@ -160,6 +160,32 @@ struct FreeGuard {
     ~FreeGuard() { smafa_free(p); }
 };
 
+// ---- what the store verbs print with (smafa_pairs .. smafa_neighbours)
+// one row of text: the fields, tabs between them
+void append_row(std::string &text, std::initializer_list<uint32_t> fields) {
+    char sep = 0;
+    for (uint32_t f : fields) {
+        if (sep) text.push_back(sep);
+        append_u32(text, f);
+        sep = '\t';
+    }
+    text.push_back('\n');
+}
+
+// rows 0 .. count - 1 to fd, at most `block` of them per write: row(text, i) appends row i
+template <class Row>
+int write_rows(int fd, size_t count, size_t block, Row row) {
+    std::string text;
+    for (size_t b0 = 0; b0 < count; b0 += block) {
+        text.clear();
+        for (size_t i = b0, e = std::min(count, b0 + block); i < e; i++) row(text, i);
+        const int rc = write_all(fd, text.data(), text.size());
+        if (rc) return rc;
+    }
+    return SMAFA_OK;
+}
+constexpr size_t kRowsPerWrite = (size_t)1 << 18;
+
 // First occurrences of every distinct row, in input order — the HashSet<Vec<u64>> test of src/cluster.rs:24,46-48.
 // Rows are hashed by all threads, then thread t owns the rows whose hash falls in partition t and runs them, in input
 // order, through its own open-addressing table; "first" is decided inside one partition, so the result does not
@@ -621,45 +647,58 @@ static int load_db_store(const char *db_path, int device, DbGuard *store, bool *
     return rc;
 }
 
+// A store verb between its checks and its print: the clock, the store of the DB file, its subject count.
+struct StoreVerb {
+    double t_start = 0.0;
+    DbGuard store;
+    bool empty = false;  // the DB holds no row: store.db is NULL, n is 0
+    size_t n = 0;
+    unsigned long long seconds() const { return (unsigned long long)(now_seconds() - t_start); }
+};
+
+// What every store verb starts with, in this order: the path and the bound checked (who: the verb, for the texts), then the
+// verb's further checks, the clock started, the DB file loaded on `device` and its subjects counted (print_pairs has no use for
+// the count: its buffer grows by the call's own answer).
+static int begin_store_verb(const char *who, const char *db_path, uint32_t max_divergence, int device, StoreVerb &v,
+                            const std::function<int()> &more_checks = nullptr) {
+    if (!db_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL path", who);
+    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: a bound (max_divergence) is needed", who);
+    if (more_checks) {
+        const int rc = more_checks();
+        if (rc) return rc;
+    }
+    v.t_start = now_seconds();
+    int rc = load_db_store(db_path, device, &v.store, &v.empty);
+    if (rc || v.empty) return rc;
+    smafa_db_info_t info{};
+    rc = smafa_db_info(v.store.db, &info);
+    v.n = (size_t)info.n_subjects;
+    return rc;
+}
+
 // -------------------------------------------------------------------------------------- pairs
 // The self-join of a DB file's subjects (smafa_db_self_hits), printed "{i}\t{j}\t{distance}\n" per pair — or, since a row
 // (smafa_db_self_hits_since), the pairs whose larger number is at least that row.
 static int print_pairs(const char *who, const char *db_path, bool since, uint64_t first_row, uint32_t max_divergence, int out_fd, int device) {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL path", who);
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: a bound (max_divergence) is needed", who);
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
+    StoreVerb v;
+    int rc = begin_store_verb(who, db_path, max_divergence, device, v);
     if (rc) return rc;
-    if (empty)  // (an empty DB has no pairs)
+    if (v.empty)  // (an empty DB has no pairs)
         return since && first_row ? set_error(SMAFA_ERR_INVALID, "%s: first_row %llu, the store has 0 subjects", who, (unsigned long long)first_row)
                                   : SMAFA_OK;
     std::vector<smafa_hit> pairs((size_t)1 << 16);
     uint64_t count = 0;
     const auto join = [&] {
-        return since ? smafa_db_self_hits_since(store.db, first_row, max_divergence, pairs.data(), pairs.size(), &count)
-                     : smafa_db_self_hits(store.db, max_divergence, pairs.data(), pairs.size(), &count);
+        return since ? smafa_db_self_hits_since(v.store.db, first_row, max_divergence, pairs.data(), pairs.size(), &count)
+                     : smafa_db_self_hits(v.store.db, max_divergence, pairs.data(), pairs.size(), &count);
     };
     while ((rc = join()) == SMAFA_ERR_CAPACITY) pairs.resize(count);
     if (rc) return rc;
-    std::string text;
-    const size_t block = (size_t)1 << 18;  // rows per write
-    for (size_t b0 = 0; b0 < count; b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(count, b0 + block); i < e; i++) {
-            append_u32(text, pairs[i].query);
-            text.push_back('\t');
-            append_u32(text, pairs[i].subject);
-            text.push_back('\t');
-            append_u32(text, pairs[i].dist);
-            text.push_back('\n');
-        }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
-    log_line(1, "%llu pairs within %u, took %llu seconds", (unsigned long long)count, max_divergence,
-             (unsigned long long)(now_seconds() - t_start));
+    rc = write_rows(out_fd, count, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_row(text, {pairs[i].query, pairs[i].subject, pairs[i].dist});
+    });
+    if (rc) return rc;
+    log_line(1, "%llu pairs within %u, took %llu seconds", (unsigned long long)count, max_divergence, v.seconds());
     return SMAFA_OK;
 }
 
@@ -678,35 +717,16 @@ int smafa_pairs_since(const char *db_path, uint64_t first_row, uint32_t max_dive
 // --------------------------------------------------------------------------------- components
 // The label of every subject of a DB file (smafa_db_self_components), printed "{i}\t{label}\n" in subject order.
 int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_components: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_components: a bound (max_divergence) is needed");
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    std::vector<uint32_t> labels((size_t)info.n_subjects);
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_components", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    std::vector<uint32_t> labels(v.n);
     uint64_t count = 0;
-    rc = smafa_db_self_components(store.db, max_divergence, labels.data(), labels.size(), &count);
+    rc = smafa_db_self_components(v.store.db, max_divergence, labels.data(), labels.size(), &count);
+    if (!rc) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) { append_row(text, {(uint32_t)i, labels[i]}); });
     if (rc) return rc;
-    std::string text;
-    const size_t block = (size_t)1 << 18;  // rows per write
-    for (size_t b0 = 0; b0 < labels.size(); b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(labels.size(), b0 + block); i < e; i++) {
-            append_u32(text, (uint32_t)i);
-            text.push_back('\t');
-            append_u32(text, labels[i]);
-            text.push_back('\n');
-        }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
-    log_line(1, "%llu components of %llu sequences within %u, took %llu seconds", (unsigned long long)count,
-             (unsigned long long)labels.size(), max_divergence, (unsigned long long)(now_seconds() - t_start));
+    log_line(1, "%llu components of %llu sequences within %u, took %llu seconds", (unsigned long long)count, (unsigned long long)v.n,
+             max_divergence, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_components");
@@ -715,38 +735,24 @@ int smafa_components(const char *db_path, uint32_t max_divergence, int out_fd, i
 // The labels of every subject of a DB file at every bound 0 .. max_divergence (smafa_db_self_levels), printed
 // "{i}\t{label_0}\t...\t{label_N}\n" in subject order.
 int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_component_levels: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_component_levels: a bound (max_divergence) is needed");
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    const size_t n = (size_t)info.n_subjects, T = (size_t)max_divergence + 1;
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_component_levels", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    const size_t n = v.n, T = (size_t)max_divergence + 1;
     std::vector<uint32_t> labels(n * T);
     std::vector<uint64_t> counts(T);
-    rc = smafa_db_self_levels(store.db, max_divergence, labels.data(), labels.size(), counts.data());
-    if (rc) return rc;
-    std::string text;
-    const size_t block = std::max<size_t>(1, ((size_t)1 << 18) / T);  // rows per write
-    for (size_t b0 = 0; b0 < n; b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(n, b0 + block); i < e; i++) {
-            append_u32(text, (uint32_t)i);
-            for (size_t t = 0; t < T; t++) {
-                text.push_back('\t');
-                append_u32(text, labels[t * n + i]);
-            }
-            text.push_back('\n');
+    rc = smafa_db_self_levels(v.store.db, max_divergence, labels.data(), labels.size(), counts.data());
+    if (!rc) rc = write_rows(out_fd, n, std::max<size_t>(1, kRowsPerWrite / T), [&](std::string &text, size_t i) {
+        append_u32(text, (uint32_t)i);
+        for (size_t t = 0; t < T; t++) {
+            text.push_back('\t');
+            append_u32(text, labels[t * n + i]);
         }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
+        text.push_back('\n');
+    });
+    if (rc) return rc;
     log_line(1, "%llu components of %llu sequences within 0, %llu within %u, took %llu seconds", (unsigned long long)counts[0],
-             (unsigned long long)n, (unsigned long long)counts[T - 1], max_divergence, (unsigned long long)(now_seconds() - t_start));
+             (unsigned long long)n, (unsigned long long)counts[T - 1], max_divergence, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_component_levels");
@@ -756,39 +762,20 @@ int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out
 // The minimum spanning forest of a DB file's subjects up to max_divergence (smafa_db_self_forest), printed
 // "{a}\t{b}\t{distance}\n" per edge in the host form's order: by distance, then a, then b.
 int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_forest: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_forest: a bound (max_divergence) is needed");
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    const size_t n = (size_t)info.n_subjects, T = (size_t)max_divergence + 1;
-    std::vector<smafa_hit> edges(std::max<size_t>(n, 2) - 1);  // (one row at least: the call takes no NULL buffer)
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_forest", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    const size_t T = (size_t)max_divergence + 1;
+    std::vector<smafa_hit> edges(std::max<size_t>(v.n, 2) - 1);  // (one row at least: the call takes no NULL buffer)
     std::vector<uint64_t> level_ends(T);
-    rc = smafa_db_self_forest(store.db, max_divergence, edges.data(), edges.size(), level_ends.data());
-    if (rc) return rc;
+    rc = smafa_db_self_forest(v.store.db, max_divergence, edges.data(), edges.size(), level_ends.data());
     const size_t count = (size_t)level_ends[T - 1];
-    std::string text;
-    const size_t block = (size_t)1 << 18;  // rows per write
-    for (size_t b0 = 0; b0 < count; b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(count, b0 + block); i < e; i++) {
-            append_u32(text, edges[i].query);
-            text.push_back('\t');
-            append_u32(text, edges[i].subject);
-            text.push_back('\t');
-            append_u32(text, edges[i].dist);
-            text.push_back('\n');
-        }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
-    log_line(1, "%llu edges among %llu sequences within %u, took %llu seconds", (unsigned long long)count, (unsigned long long)n,
-             max_divergence, (unsigned long long)(now_seconds() - t_start));
+    if (!rc) rc = write_rows(out_fd, count, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_row(text, {edges[i].query, edges[i].subject, edges[i].dist});
+    });
+    if (rc) return rc;
+    log_line(1, "%llu edges among %llu sequences within %u, took %llu seconds", (unsigned long long)count, (unsigned long long)v.n,
+             max_divergence, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_forest");
@@ -798,39 +785,25 @@ int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int d
 // The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
 // "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.
 int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_density: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_density: a bound (max_divergence) is needed");
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    std::vector<uint32_t> labels((size_t)info.n_subjects), degrees((size_t)info.n_subjects);
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_density", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    std::vector<uint32_t> labels(v.n), degrees(v.n);
     uint64_t counts[3] = {0, 0, 0};
-    rc = smafa_db_self_density(store.db, max_divergence, min_pts, labels.data(), degrees.data(), labels.size(), counts);
+    rc = smafa_db_self_density(v.store.db, max_divergence, min_pts, labels.data(), degrees.data(), labels.size(), counts);
+    if (!rc) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_u32(text, (uint32_t)i);
+        text.push_back('\t');
+        if (labels[i] == SMAFA_NONE) text += "-1";
+        else append_u32(text, labels[i]);
+        text.push_back('\t');
+        append_u32(text, degrees[i]);
+        text.push_back('\n');
+    });
     if (rc) return rc;
-    std::string text;
-    const size_t block = (size_t)1 << 18;  // rows per write
-    for (size_t b0 = 0; b0 < labels.size(); b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(labels.size(), b0 + block); i < e; i++) {
-            append_u32(text, (uint32_t)i);
-            text.push_back('\t');
-            if (labels[i] == SMAFA_NONE) text += "-1";
-            else append_u32(text, labels[i]);
-            text.push_back('\t');
-            append_u32(text, degrees[i]);
-            text.push_back('\n');
-        }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
     log_line(1, "%llu clusters, %llu core and %llu noise among %llu sequences within %u at min_pts %u, took %llu seconds",
-             (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)labels.size(),
-             max_divergence, min_pts, (unsigned long long)(now_seconds() - t_start));
+             (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)v.n,
+             max_divergence, min_pts, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_density");
@@ -840,43 +813,22 @@ int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts
 // The abundance-peak label, the parent and the weight of every subject of a DB file (smafa_db_self_peaks), printed
 // "{i}\t{label}\t{parent}\t{weight}\n" in subject order.
 int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_peaks: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_peaks: a bound (max_divergence) is needed");
-    if (radius != SMAFA_NONE && radius > max_divergence)
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_peaks", db_path, max_divergence, device, v, [&] {
+        if (radius == SMAFA_NONE || radius <= max_divergence) return (int)SMAFA_OK;
         return set_error(SMAFA_ERR_INVALID, "smafa_peaks: radius %u is larger than max_divergence %u", radius, max_divergence);
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    const size_t n = (size_t)info.n_subjects;
+    });
+    if (rc || v.empty) return rc;
+    const size_t n = v.n;
     std::vector<uint32_t> labels(n), parents(n), weights(n);
     uint64_t n_peaks = 0;
-    rc = smafa_db_self_peaks(store.db, max_divergence, radius, labels.data(), parents.data(), weights.data(), n, &n_peaks);
+    rc = smafa_db_self_peaks(v.store.db, max_divergence, radius, labels.data(), parents.data(), weights.data(), n, &n_peaks);
+    if (!rc) rc = write_rows(out_fd, n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_row(text, {(uint32_t)i, labels[i], parents[i], weights[i]});
+    });
     if (rc) return rc;
-    std::string text;
-    const size_t block = (size_t)1 << 18;  // rows per write
-    for (size_t b0 = 0; b0 < n; b0 += block) {
-        text.clear();
-        for (size_t i = b0, e = std::min<size_t>(n, b0 + block); i < e; i++) {
-            append_u32(text, (uint32_t)i);
-            text.push_back('\t');
-            append_u32(text, labels[i]);
-            text.push_back('\t');
-            append_u32(text, parents[i]);
-            text.push_back('\t');
-            append_u32(text, weights[i]);
-            text.push_back('\n');
-        }
-        rc = write_all(out_fd, text.data(), text.size());
-        if (rc) return rc;
-    }
     log_line(1, "%llu peaks among %llu sequences within %u, weighed within %u, took %llu seconds", (unsigned long long)n_peaks,
-             (unsigned long long)n, max_divergence, radius == SMAFA_NONE ? max_divergence : radius,
-             (unsigned long long)(now_seconds() - t_start));
+             (unsigned long long)n, max_divergence, radius == SMAFA_NONE ? max_divergence : radius, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_peaks");
@@ -886,48 +838,35 @@ int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, i
 // The neighbours of every subject of a DB file within the bound, nearest first, at most max_num_hits of them
 // (smafa_db_self_neighbours), printed "{i}\t{j}\t{dist}\n" ordered by (i, dist, j): both directions of every pair.
 int smafa_neighbours(const char *db_path, uint32_t max_divergence, uint32_t max_num_hits, int out_fd, int device) try {
-    if (!db_path) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: NULL path");
-    if (max_divergence == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: a bound (max_divergence) is needed");
-    if (max_num_hits == 0) return set_error(SMAFA_ERR_INVALID, "smafa_neighbours: max_num_hits is 0");
-    const double t_start = now_seconds();
-    DbGuard store;
-    bool empty = false;
-    int rc = load_db_store(db_path, device, &store, &empty);
-    if (rc || empty) return rc;
-    smafa_db_info_t info;
-    rc = smafa_db_info(store.db, &info);
-    if (rc) return rc;
-    const size_t n = (size_t)info.n_subjects;
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_neighbours", db_path, max_divergence, device, v, [&] {
+        return max_num_hits ? (int)SMAFA_OK : set_error(SMAFA_ERR_INVALID, "smafa_neighbours: max_num_hits is 0");
+    });
+    if (rc || v.empty) return rc;
+    const size_t n = v.n;
     std::vector<uint64_t> offsets(n + 1);
     std::vector<uint32_t> neighbours, dists;
     uint64_t total = 0;
     // the capacity protocol: the degrees alone first, then the call sized by them
-    rc = smafa_db_self_neighbours(store.db, max_divergence, max_num_hits, offsets.data(), nullptr, nullptr, 0, &total);
+    rc = smafa_db_self_neighbours(v.store.db, max_divergence, max_num_hits, offsets.data(), nullptr, nullptr, 0, &total);
     if (rc == SMAFA_ERR_CAPACITY) {
         neighbours.resize((size_t)total);
         dists.resize((size_t)total);
-        rc = smafa_db_self_neighbours(store.db, max_divergence, max_num_hits, offsets.data(), neighbours.data(), dists.data(), total, &total);
+        rc = smafa_db_self_neighbours(v.store.db, max_divergence, max_num_hits, offsets.data(), neighbours.data(), dists.data(), total, &total);
     }
     if (rc) return rc;
+    // (not write_rows: a write ends with the row whose list crosses a multiple of kRowsPerWrite entries, never inside a list)
     std::string text;
-    const size_t block = (size_t)1 << 18;  // entries per write, about
     for (size_t i = 0; i < n; i++) {
-        for (uint64_t e = offsets[i]; e < offsets[i + 1]; e++) {
-            append_u32(text, (uint32_t)i);
-            text.push_back('\t');
-            append_u32(text, neighbours[e]);
-            text.push_back('\t');
-            append_u32(text, dists[e]);
-            text.push_back('\n');
-        }
-        if (i + 1 == n || offsets[i + 1] / block != offsets[i] / block) {
+        for (uint64_t e = offsets[i]; e < offsets[i + 1]; e++) append_row(text, {(uint32_t)i, neighbours[e], dists[e]});
+        if (i + 1 == n || offsets[i + 1] / kRowsPerWrite != offsets[i] / kRowsPerWrite) {
             rc = write_all(out_fd, text.data(), text.size());
             if (rc) return rc;
             text.clear();
         }
     }
     log_line(1, "%llu neighbours of %llu sequences within %u, took %llu seconds", (unsigned long long)total, (unsigned long long)n,
-             max_divergence, (unsigned long long)(now_seconds() - t_start));
+             max_divergence, v.seconds());
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_neighbours");

@@ -552,12 +552,7 @@ int scan_to_host(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, u
     }
     out.swap(l.done);
     if (max_num_hits != SMAFA_NONE && max_num_hits >= 1) cut_at_kth(out, max_num_hits);
-    // scratch of an unusually large answer is not worth keeping (the buffers regrow on demand)
-    if (db->scratch.cap > (512ull << 20)) db->scratch.release();
-    if (db->keys_a.cap > (512ull << 20)) {
-        db->keys_a.release();
-        db->keys_b.release();
-        db->sort_tmp.release();
-    }
+    trim({&db->scratch});
+    trim_together(db->keys_a, {&db->keys_b, &db->sort_tmp});
     return SMAFA_OK;
 }

@@ -1,7 +1,10 @@
-// self_join.hip.h — host code of the self-join of a resident store: one driver that walks the store and knows no consumer
-// (join_pass), and the seven calls that consume its pieces (join_pairs, join_components, join_levels, join_density, join_peaks,
-// join_neighbours, join_forest); and the driver of the delta join (delta_pass: the rows appended since a mark against the whole store), with
-// its two calls (delta_pairs, delta_components).  Both drivers scan their pieces through one loop, join_pieces.
+// self_join.hip.h — host code of the self-join of a resident store.  Two drivers walk the store and know no consumer: join_pass (every
+// row against the rows behind it) and delta_pass (the rows appended since a mark against the whole store).  Each cuts its spans
+// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Nine calls
+// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours and join_forest over
+// join_pass, delta_pairs and delta_components over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
+// or more JoinConsumers: timed_consumer (a kernel per piece), watching (that, gated on a device counter read at every wait),
+// keeping_consumer (that, with J.kept grown by the gate).  Their C ABI is self_join_abi.hip.h.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
 #pragma once
 
@@ -14,8 +17,9 @@ struct JoinCall {
     bool delta = false;     // a delta call: its records come from smafa_dl::gather_records_kernel
     double *slot = nullptr;      // the timed pass whose events are not read yet: the J.*_ms it is booked to ...
     const char *what = nullptr;  // ... and its level-3 trace text (nullptr: none)
-    unsigned long long kept_seen = 0;  // density, peaks: the kept total as of the pieces before the one just scanned; neighbours: the
-                                       // entry total likewise
+    unsigned long long ctl_seen = 0;  // J.ctl[0] as a watching consumer last read it, in front of a piece's wait: what the call's kernels
+                                      // counted there over the pieces before the one just scanned — pairs kept (density, peaks, forest),
+                                      // entries appended (neighbours), labels that are none (components update)
 };
 
 // a piece's finished list: rows (record of the piece, subject, distance) of block records p0 + b + S * k, k < R
@@ -173,6 +177,46 @@ static int join_pieces(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer, u
     return SMAFA_OK;
 }
 
+// How a driver cut one span: nq records in `padded` zeroed record slots (padded as qset_fill pads: whole 64-record chunks plus
+// one), scanned as S blocks from wave tile tile_begin on, every piece shaped `shape`; block b is traced as "<what> <at>, block b of S".
+struct JoinSpan {
+    uint64_t nq, padded;
+    uint32_t S;
+    JoinPiece shape;
+    uint32_t tile_begin;
+    const char *what;
+    uint64_t at;
+};
+
+// One span of either driver: the set in db->join_q gets the span's records — records(qrec) launches the one kernel that writes
+// them, timed ev[0]..ev[1] —, then block b = 0 .. S - 1 is scanned over its records range(b) = {q0, q_end} through join_pieces, and
+// a wait ends the span.  `piece` is the caller's: the reduced piece size outlives the span.
+template <class Records, class Range>
+static int join_span(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer, uint64_t &piece, const JoinSpan &span, Records records,
+                     Range range) {
+    smafa_db *db = c.db;
+    auto &J = db->join;
+    smafa_qset *qs = &db->join_q;
+    qs->nq = span.nq;
+    qs->serial = g_qset_serial.fetch_add(1);
+    RC_TRY(qs->qrec.ensure(span.padded * db->QS * sizeof(uint32_t)));
+    RC_TRY(qs->thr.ensure(span.padded * sizeof(uint32_t)));
+    HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+    HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, span.padded * db->QS * sizeof(uint32_t), db->stream));
+    records(qs->qrec.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+    db->call_launches++;
+    bool rec_timed = false;
+    for (uint32_t b = 0; b < span.S; b++) {
+        const std::pair<uint64_t, uint64_t> q = range(b);
+        char where[64];
+        snprintf(where, sizeof where, "%s %llu, block %u of %u", span.what, (unsigned long long)span.at, b, span.S);
+        RC_TRY(join_pieces(c, scan_div, consumer, q.first, q.second, piece, span.shape, span.tile_begin, rec_timed, where));
+    }
+    return timed_sync(c);  // the span's records are overwritten next
+}
+
 // The driver: every pair of the store's rows within scan_div of each other, once or twice, as the lists of PIECES to `consumer`.
 // The store is walked in SPANS of join_stride x join_block consecutive positions.  A span's rows become query records on
 // the device (store_records_kernel), dealt round-robin into join_stride BLOCKS: block b holds the span's positions b,
@@ -183,40 +227,28 @@ static int join_pieces(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer, u
 // sits in a few workgroups (profiles/r07_self_join.txt, stride 1 against 16).
 static int join_pass(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer) {
     smafa_db *db = c.db;
-    auto &J = db->join;
-    smafa_qset *qs = &db->join_q;
-    qs->db = db;
+    db->join_q.db = db;
     const uint64_t span_rows = db->join_block * db->join_stride;
     uint64_t piece = db->join_block;  // rows per scan
-    J.joins++;
+    db->join.joins++;
     for (uint64_t p0 = 0; p0 < db->n; p0 += span_rows) {
         const uint64_t p1 = std::min<uint64_t>(db->n, p0 + span_rows), m = p1 - p0;
         const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
         const uint32_t R = (uint32_t)((m + S - 1) / S);                            // rows of its fullest block
-        // padded as qset_fill pads: whole 64-record chunks plus one, zeros (a short block's last record slot stays zero too)
+        // (a short block's last record slot stays zero too)
         const uint64_t padded = std::max<uint64_t>(((uint64_t)S * R + 63) / 64 * 64, 64) + 64;
-        qs->nq = (uint64_t)S * R;
-        qs->serial = g_qset_serial.fetch_add(1);
-        RC_TRY(qs->qrec.ensure(padded * db->QS * sizeof(uint32_t)));
-        RC_TRY(qs->thr.ensure(padded * sizeof(uint32_t)));
-        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
-        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
         const uint32_t t0 = (uint32_t)(p0 / kWaveTile), t1 = (uint32_t)((p1 - 1) / kWaveTile) + 1u;
-        hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0,
-                           db->stream, reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0,
-                           (uint32_t)p1, S, R, qs->qrec.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
-        db->call_launches++;
-        bool rec_timed = false;
-        for (uint32_t b = 0; b < S; b++) {
-            const uint64_t rows_b = (m - b + S - 1) / S;  // positions b, b + S, ... of the span
-            char where[64];
-            snprintf(where, sizeof where, "span at %llu, block %u of %u", (unsigned long long)p0, b, S);
-            RC_TRY(join_pieces(c, scan_div, consumer, (uint64_t)b * R, (uint64_t)b * R + rows_b, piece,
-                               {nullptr, 0, (uint32_t)p0, S, R, db->d_order}, t0, rec_timed, where));
-        }
-        RC_TRY(timed_sync(c));  // the span's records are overwritten next
+        const JoinPiece shape{nullptr, 0, (uint32_t)p0, S, R, db->d_order};
+        const JoinSpan span{/* nq */ (uint64_t)S * R, padded, S, shape, /* tile_begin */ t0, "span at", /* at */ p0};
+        RC_TRY(join_span(c, scan_div, consumer, piece, span,
+                         [&](uint32_t *qrec) {
+                             hipLaunchKernelGGL(smafa_join::store_records_kernel, dim3(t1 - t0), dim3(256), 0, db->stream,
+                                                reinterpret_cast<const uint4 *>(db->d_planes), db->P, db->PQ, db->W, db->QS, (uint32_t)p0,
+                                                (uint32_t)p1, S, R, qrec);
+                         },
+                         [&](uint32_t b) {  // positions b, b + S, ... of the span
+                             return std::pair<uint64_t, uint64_t>((uint64_t)b * R, (uint64_t)b * R + (m - b + S - 1) / S);
+                         }));
     }
     return SMAFA_OK;
 }
@@ -233,8 +265,7 @@ static int join_pass(JoinCall &c, uint32_t scan_div, JoinConsumer &consumer) {
 static int delta_pass(JoinCall &c, uint32_t first_row, uint32_t scan_div, JoinConsumer &consumer) {
     smafa_db *db = c.db;
     auto &J = db->join;
-    smafa_qset *qs = &db->join_q;
-    qs->db = db;
+    db->join_q.db = db;
     const uint64_t new_rows = db->n - first_row, span_rows = db->join_block * db->join_stride;
     uint64_t piece = db->join_block;  // rows per scan
     RC_TRY(J.rows.ensure(new_rows * sizeof(uint32_t)));
@@ -242,29 +273,19 @@ static int delta_pass(JoinCall &c, uint32_t first_row, uint32_t scan_div, JoinCo
     for (uint64_t a0 = 0; a0 < new_rows; a0 += span_rows) {
         const uint64_t m = std::min<uint64_t>(span_rows, new_rows - a0);
         const uint32_t S = (uint32_t)((m + db->join_block - 1) / db->join_block);  // blocks of this span
-        // padded as join_pass pads: whole 64-record chunks plus one, zeros
         const uint64_t padded = std::max<uint64_t>((m + 63) / 64 * 64, 64) + 64;
-        qs->nq = m;
-        qs->serial = g_qset_serial.fetch_add(1);
-        RC_TRY(qs->qrec.ensure(padded * db->QS * sizeof(uint32_t)));
-        RC_TRY(qs->thr.ensure(padded * sizeof(uint32_t)));
-        HIP_TRY(hipEventRecord(J.ev[0], db->stream));
-        HIP_TRY(hipMemsetAsync(qs->qrec.p, 0, padded * db->QS * sizeof(uint32_t), db->stream));
-        hipLaunchKernelGGL(smafa_dl::gather_records_kernel, list_grid(m * db->P * db->W), dim3(256), 0, db->stream, db->d_planes,
-                           J.pos_of.as<uint32_t>(), db->P, db->PQ, db->W, db->QS, (uint32_t)(first_row + a0), (uint32_t)m,
-                           qs->qrec.as<uint32_t>(), J.rows.as<uint32_t>() + a0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(J.ev[1], db->stream));
-        db->call_launches++;
-        bool rec_timed = false;
-        for (uint32_t b = 0; b < S; b++) {
-            const uint64_t q0 = (uint64_t)b * db->join_block;
-            char where[64];
-            snprintf(where, sizeof where, "new rows from %llu, block %u of %u", (unsigned long long)(first_row + a0), b, S);
-            RC_TRY(join_pieces(c, scan_div, consumer, q0, std::min<uint64_t>(m, q0 + db->join_block), piece,
-                               {nullptr, 0, (uint32_t)a0, 1u, 0xffffffffu, J.rows.as<uint32_t>()}, 0u, rec_timed, where));
-        }
-        RC_TRY(timed_sync(c));  // the span's records are overwritten next
+        const JoinPiece shape{nullptr, 0, (uint32_t)a0, 1u, 0xffffffffu, J.rows.as<uint32_t>()};
+        const JoinSpan span{/* nq */ m, padded, S, shape, /* tile_begin */ 0u, "new rows from", /* at */ first_row + a0};
+        RC_TRY(join_span(c, scan_div, consumer, piece, span,
+                         [&](uint32_t *qrec) {
+                             hipLaunchKernelGGL(smafa_dl::gather_records_kernel, list_grid(m * db->P * db->W), dim3(256), 0, db->stream,
+                                                db->d_planes, J.pos_of.as<uint32_t>(), db->P, db->PQ, db->W, db->QS,
+                                                (uint32_t)(first_row + a0), (uint32_t)m, qrec, J.rows.as<uint32_t>() + a0);
+                         },
+                         [&](uint32_t b) {  // join_block consecutive rows
+                             const uint64_t q0 = (uint64_t)b * db->join_block;
+                             return std::pair<uint64_t, uint64_t>(q0, std::min<uint64_t>(m, q0 + db->join_block));
+                         }));
     }
     return SMAFA_OK;
 }
@@ -310,24 +331,31 @@ static int grow_kept(smafa_db *db, uint64_t rows, uint64_t live) {
     return SMAFA_OK;
 }
 
-// A consumer whose kernel also moves pairs to J.kept.  In front of every piece's wait the kept total so far is read back (every
-// count/keep pass in front of the piece's scan has ended with it), and in front of its pass (count <= the scratch capacity: a
-// truncated list was scanned again) the list gets room for whatever the piece keeps on top of that, while the knob allows it.
-template <class Launch>
-static JoinConsumer keeping_consumer(JoinCall &c, double *slot, const char *what, Launch launch) {
-    JoinConsumer k = timed_consumer(c, slot, what, launch);
-    k.before_wait = [&c] {
-        smafa_db *db = c.db;
-        auto &J = db->join;
-        unsigned long long &kept_seen = c.kept_seen;
-        HIP_TRY(hipMemcpyAsync(&kept_seen, J.ctl.p, sizeof kept_seen, hipMemcpyDeviceToHost, db->stream));
-        return SMAFA_OK;
-    };
-    k.take = [&c, timed = k.take](const JoinPiece &p) {
-        if (!c.db->join.kept_stuck) RC_TRY(grow_kept(c.db, c.kept_seen + p.count, std::min<uint64_t>(c.kept_seen, kept_room(c.db))));
+// ---- a consumer that watches J.ctl[0], a total its own kernel raises
+static int read_watched(JoinCall &c) {
+    HIP_TRY(hipMemcpyAsync(&c.ctl_seen, c.db->join.ctl.p, sizeof c.ctl_seen, hipMemcpyDeviceToHost, c.db->stream));
+    return SMAFA_OK;
+}
+// `k` with the total read back into c.ctl_seen in front of every piece's wait (every pass in front of the piece's scan has ended
+// with it: exact as of the pieces before), and gate(that total, the piece) in front of every take — it makes room for what the
+// piece may add, or fails the call (count <= the scratch capacity: a truncated list was scanned again).
+template <class Gate>
+static JoinConsumer watching(JoinCall &c, JoinConsumer k, Gate gate) {
+    k.before_wait = [&c] { return read_watched(c); };
+    k.take = [&c, gate, timed = k.take](const JoinPiece &p) {
+        RC_TRY(gate(c.ctl_seen, p));
         return timed(p);
     };
     return k;
+}
+
+// A consumer whose kernel also moves pairs to J.kept: watching the kept total, the list given room for whatever the piece keeps
+// on top of that, while the knob allows it.
+template <class Launch>
+static JoinConsumer keeping_consumer(JoinCall &c, double *slot, const char *what, Launch launch) {
+    return watching(c, timed_consumer(c, slot, what, launch), [&c](unsigned long long kept, const JoinPiece &p) {
+        return c.db->join.kept_stuck ? SMAFA_OK : grow_kept(c.db, kept + p.count, std::min<uint64_t>(kept, kept_room(c.db)));
+    });
 }
 
 // Every count is final and `total` pairs were kept or counted over.  None: there is nothing to link.  All of them in J.kept: ONE
@@ -452,11 +480,7 @@ static int delta_components(smafa_db *db, uint32_t first_row, uint32_t max_div, 
         hipLaunchKernelGGL(smafa_dl::seed_parents_kernel, row_grid(n), dim3(256), 0, db->stream, d_labels, first_row, n,
                            J.parent.as<uint32_t>(), J.ctl.as<unsigned long long>());
     RC_TRY(timed_end(c, all_near ? 0u : 1u));
-    unsigned long long &bad = c.kept_seen;
-    const auto read_bad = [&c] {
-        HIP_TRY(hipMemcpyAsync(&c.kept_seen, c.db->join.ctl.p, sizeof c.kept_seen, hipMemcpyDeviceToHost, c.db->stream));
-        return SMAFA_OK;
-    };
+    const unsigned long long &bad = c.ctl_seen;
     const auto bad_labels = [&] {
         return set_error(SMAFA_ERR_INVALID, "components update: %llu of the first %u labels are no labels of a store of %u rows (a label is "
                          "at most its row's number, and its own label)", bad, first_row, first_row);
@@ -465,13 +489,12 @@ static int delta_components(smafa_db *db, uint32_t first_row, uint32_t max_div, 
         hipLaunchKernelGGL(smafa_cc::link_rows_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
                            J.parent.as<uint32_t>());
     });
-    link.before_wait = read_bad;
-    link.take = [&, timed = link.take](const JoinPiece &p) { return bad ? bad_labels() : timed(p); };
+    link = watching(c, link, [&](unsigned long long, const JoinPiece &) { return bad ? bad_labels() : SMAFA_OK; });
     if (!c.no_scans) {
         RC_TRY(join_positions(c));
         RC_TRY(delta_pass(c, first_row, max_div, link));
     }
-    RC_TRY(read_bad());
+    RC_TRY(read_watched(c));
     RC_TRY(timed_sync(c));
     if (bad) return bad_labels();
     RC_TRY(timed_pass(c, &J.flatten_ms, nullptr, [&] {
@@ -753,20 +776,13 @@ static int join_neighbours(smafa_db *db, uint32_t max_div, uint32_t k, unsigned 
                            p.order, J.pos_of.as<uint32_t>(), shift, J.entries.as<unsigned long long>(), apart ? entry_rows(db) : (uint32_t *)nullptr,
                            (unsigned long long)J.entries_cap, J.ctl.as<unsigned long long>());
     });
-    pack.before_wait = [&c] {
-        smafa_db *db = c.db;
-        unsigned long long &seen = c.kept_seen;
-        HIP_TRY(hipMemcpyAsync(&seen, db->join.ctl.p, sizeof seen, hipMemcpyDeviceToHost, db->stream));
-        return SMAFA_OK;
-    };
     const auto too_many = [](unsigned long long entries) {
         return set_error(SMAFA_ERR_NOMEM, "neighbours: %llu entries before the cut, the device sort orders at most %llu", entries, kSortItemsMax);
     };
-    pack.take = [&, timed = pack.take](const JoinPiece &p) {
-        if (c.kept_seen > kSortItemsMax) return too_many(c.kept_seen);  // (exact so far, and it only grows)
-        RC_TRY(grow_entries(db, c.kept_seen + 2 * p.count, c.kept_seen, apart));
-        return timed(p);
-    };
+    pack = watching(c, pack, [&](unsigned long long seen, const JoinPiece &p) {
+        if (seen > kSortItemsMax) return too_many(seen);  // (exact so far, and it only grows)
+        return grow_entries(db, seen + 2 * p.count, seen, apart);
+    });
     RC_TRY(join_pass(c, scan_div, pack));
     unsigned long long entries = 0, total = 0;
     HIP_TRY(hipMemcpyAsync(&entries, J.ctl.p, sizeof entries, hipMemcpyDeviceToHost, db->stream));
@@ -929,4 +945,3 @@ static int join_forest(smafa_db *db, uint32_t max_div, smafa_hit *d_edges, unsig
              J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, kept_total);
     return SMAFA_OK;
 }
-#undef RC_TRY

@@ -1,4 +1,4 @@
-"""Launch census of the five self-join calls: launches, scans and the kernel list of smafa_last_call_stats /
+"""Launch census of the nine self-join calls: launches, scans and the kernel list of smafa_last_call_stats /
 smafa_last_call_kernels, per call and case — tests/join_launch_census.json, which tests/test_gpu_join_launch_census.py holds
 this tree against.
 
@@ -6,6 +6,11 @@ The table is recorded from a build of the PARENT commit: one library (SMAFA_AMD_
 alone, so that the parent's build runs the very same cases:
 
     SMAFA_AMD_LIB=$PARENT python tools/join_census.py --repeat 3 --out tests/join_launch_census.json
+
+With --calls only the named calls are recorded and merged into the file that is there: the other calls' entries stay as they
+are, from the parent they were recorded from, and "builds" names the build of every call recorded this way:
+
+    SMAFA_AMD_LIB=$PARENT python tools/join_census.py --repeat 3 --calls neighbours,forest --out tests/join_launch_census.json
 
 A peaks call that climbed ends in jump rounds, whose number may differ from run to run (pointer doubling in place): where
 `launches` differed between the repeats it is recorded as null and only scans and kernels are pinned."""
@@ -22,8 +27,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-CALLS = ["pairs", "components", "levels", "density", "peaks"]
-KNOBS = ["SMAFA_JOIN_BLOCK", "SMAFA_JOIN_STRIDE", "SMAFA_JOIN_SCRATCH_MAX", "SMAFA_DENSITY_KEEP_MAX"]
+CALLS = ["pairs", "components", "levels", "density", "peaks"]  # recorded from the commit before the driver/consumer split
+NEWER_CALLS = ["neighbours", "forest", "pairs_since", "components_update"]  # recorded later (--calls), each from its own parent
+ALL_CALLS = CALLS + NEWER_CALLS
+KNOBS = ["SMAFA_JOIN_BLOCK", "SMAFA_JOIN_STRIDE", "SMAFA_JOIN_SCRATCH_MAX", "SMAFA_DENSITY_KEEP_MAX", "SMAFA_NEIGHBOUR_SORT"]
 NONE = 0xFFFFFFFF  # SMAFA_NONE
 
 
@@ -40,8 +47,11 @@ def stores():
             len(brute_pairs(nt60, 5)))
 
 
-def cases():
-    """-> [(id, store, max_div, radius of the peaks call, knobs)]"""
+def cases(call=None):
+    """-> [(id, store, max_div, radius of the peaks call, knobs)]; neighbours: every case at both cuts, and one in two sorts"""
+    if call == "neighbours":
+        both = cases() + [("nt60 two sorts", "nt60", 5, NONE, {"SMAFA_NEIGHBOUR_SORT": "2"})]
+        return [(cid + ", k %s" % ("none" if k == NONE else k), name, D, k, knobs) for cid, name, D, _, knobs in both for k in (NONE, 3)]
     pairs = stores()[1]
     out = []
     for D in (0, 3):  # the dense store at its bounds: the rescan at the default ceiling, the halving at 1 000 000 rows
@@ -74,6 +84,10 @@ def load(path):
     lib.smafa_db_self_levels.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
     lib.smafa_db_self_density.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, u64p]
     lib.smafa_db_self_peaks.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_neighbours.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_forest.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_hits_since.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_components_update.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
     lib.smafa_last_call_stats.argtypes = [vp, C.POINTER(C.c_float), u32p, u32p]
     lib.smafa_last_call_kernels.argtypes = [vp, C.c_char_p, C.c_uint64]
     return lib
@@ -88,7 +102,7 @@ def census(lib, call):
         if rc and rc not in allowed:
             raise RuntimeError("join_census: %s" % lib.smafa_last_error().decode())
 
-    for cid, name, D, radius, knobs in cases():
+    for cid, name, D, radius, knobs in cases(call):  # (neighbours: the cut in the radius' place)
         codes, alphabet = stores()[0][name]
         n = len(codes)
         saved = {k: os.environ.pop(k, None) for k in KNOBS}
@@ -102,8 +116,9 @@ def census(lib, call):
                 if saved[k] is not None:
                     os.environ[k] = saved[k]
         try:
-            if n:
-                ok(lib.smafa_db_append(h, codes.ctypes.data, n))
+            first = n // 2 if call == "components_update" else n  # the update: the labels of the first half, then the rest appended
+            if first:
+                ok(lib.smafa_db_append(h, codes.ctypes.data, first))
             labels = np.zeros(max((D + 1) * n if call == "levels" else n, 1), dtype=np.uint32)
             extra = np.zeros((2, max(n, 1)), dtype=np.uint32)
             counts = (C.c_uint64 * (D + 3))()
@@ -115,8 +130,25 @@ def census(lib, call):
                 ok(lib.smafa_db_self_levels(h, D, labels.ctypes.data, (D + 1) * n, counts))
             elif call == "density":
                 ok(lib.smafa_db_self_density(h, D, 3, labels.ctypes.data, extra[0].ctypes.data, n, counts))
-            else:
+            elif call == "peaks":
                 ok(lib.smafa_db_self_peaks(h, D, radius, labels.ctypes.data, extra[0].ctypes.data, extra[1].ctypes.data, n, counts))
+            elif call == "neighbours":  # the capacity protocol: the degrees alone, then the call sized by them — the census is the last call's
+                offsets = np.zeros(n + 1, dtype=np.uint64)
+                rc = lib.smafa_db_self_neighbours(h, D, radius, offsets.ctypes.data, None, None, 0, counts)
+                if rc == -3:
+                    lists = np.zeros((2, counts[0]), dtype=np.uint32)
+                    rc = lib.smafa_db_self_neighbours(h, D, radius, offsets.ctypes.data, lists[0].ctypes.data, lists[1].ctypes.data, counts[0], counts)
+                ok(rc)
+            elif call == "forest":
+                edges = np.zeros((max(n, 2) - 1, 3), dtype=np.uint32)
+                ok(lib.smafa_db_self_forest(h, D, edges.ctypes.data, len(edges), counts))
+            elif call == "pairs_since":  # no room for rows, as pairs
+                ok(lib.smafa_db_self_hits_since(h, n // 2, D, None, 0, counts), allowed=(-3,))
+            else:
+                ok(lib.smafa_db_self_components(h, D, labels.ctypes.data, first, counts))
+                if n - first:
+                    ok(lib.smafa_db_append(h, codes[first:].ctypes.data, n - first))
+                ok(lib.smafa_db_self_components_update(h, first, D, labels.ctypes.data, n, counts))
             ms, launches, scans = C.c_float(), C.c_uint32(), C.c_uint32()
             ok(lib.smafa_last_call_stats(h, C.byref(ms), C.byref(launches), C.byref(scans)))
             names = C.create_string_buffer(1 << 16)
@@ -131,11 +163,30 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--out", required=True)
+    ap.add_argument("--calls", help="comma-separated: record only these and merge them into the file at --out")
     args = ap.parse_args()
     path = os.environ.get("SMAFA_AMD_LIB") or os.path.join(ROOT, "smafa_amd", "lib", "libsmafa_amd.so")
     lib = load(path)
-    table = {"build": lib.smafa_build_id().decode(), "repeats": args.repeat, "calls": {}}
-    for call in CALLS:
+    build = lib.smafa_build_id().decode()
+    named = args.calls.split(",") if args.calls else CALLS
+    unknown = sorted(set(named) - set(ALL_CALLS))
+    if unknown:
+        raise SystemExit("join_census: no such call: %s (there are: %s)" % (", ".join(unknown), ", ".join(ALL_CALLS)))
+    if args.calls:
+        if not os.path.exists(args.out):
+            raise SystemExit("join_census: --calls merges into %s, which is not there; record the whole table first" % args.out)
+        with open(args.out) as f:
+            table = json.load(f)
+        if table["repeats"] != args.repeat:
+            raise SystemExit("join_census: %s was recorded with %d repeats, not %d" % (args.out, table["repeats"], args.repeat))
+        # "build" is the build of the calls recorded with the whole table; "builds" names every call's own
+        builds = table.setdefault("builds", {})
+        for call in table["calls"]:
+            builds.setdefault(call, table["build"])
+        builds.update({call: build for call in named})
+    else:
+        table = {"build": build, "repeats": args.repeat, "calls": {}}
+    for call in named:
         runs = [census(lib, call) for _ in range(args.repeat)]
         merged = runs[0]
         for cid, rec in merged.items():
@@ -149,7 +200,7 @@ def main():
     with open(args.out, "w") as f:
         json.dump(table, f, indent=1)
         f.write("\n")
-    print("join_census: build %s, %d cases x %d calls -> %s" % (table["build"], len(cases()), len(CALLS), args.out))
+    print("join_census: build %s, %d cases of %s -> %s" % (build, sum(len(table["calls"][c]) for c in named), ", ".join(named), args.out))
 
 
 if __name__ == "__main__":

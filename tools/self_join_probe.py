@@ -139,17 +139,17 @@ def probe(label, alphabet, n, D, lines, batch=65536):
     lines += [
         "%s: n = %d, L = 60, bound %d, blocks of %s rows, %s interleaved per span: %d pairs" % (
             label, n, D, os.environ.get("SMAFA_JOIN_BLOCK", "65536"), os.environ.get("SMAFA_JOIN_STRIDE", "16"), total),
-        "  (a) self_launch, scan kernels     : median %.1f ms (runs %s), device time of its kernels %.1f ms" % (
-            med(a), ", ".join("%.1f" % x[0] for x in a), statistics.median(x[2] for x in a)),
+        "  (a) self_launch, scan kernels     : median %.3f ms (runs %s), device time of its kernels %.1f ms" % (
+            med(a), ", ".join("%.3f" % x[0] for x in a), statistics.median(x[2] for x in a)),
         "      kernels: %s" % "; ".join(kernels_a),
         "      stages : %s" % (stages[-1] if stages else "not captured"),
         "      blocks : %s" % blocks_a,
-        "  (a1) the same, consecutive blocks : median %.1f ms (runs %s)" % (med(a1), ", ".join("%.1f" % x[0] for x in a1)),
+        "  (a1) the same, consecutive blocks : median %.3f ms (runs %s)" % (med(a1), ", ".join("%.3f" % x[0] for x in a1)),
         "      blocks : %s" % blocks_a1,
-        "  (b) self_launch, block index      : median %.1f ms (runs %s); index max_div_served %s, probes used: %s" % (
-            med(b), ", ".join("%.1f" % x[0] for x in b), info["max_div_served"], used),
-        "  (c) %d x scan_launch of 65 536 rows : median %.1f ms (runs %s); %d rows before de-duplication" % (
-            len(qsets), med(c), ", ".join("%.1f" % x[0] for x in c), c[0][1]),
+        "  (b) self_launch, block index      : median %.3f ms (runs %s); index max_div_served %s, probes used: %s" % (
+            med(b), ", ".join("%.3f" % x[0] for x in b), info["max_div_served"], used),
+        "  (c) %d x scan_launch of 65 536 rows : median %.3f ms (runs %s); %d rows before de-duplication" % (
+            len(qsets), med(c), ", ".join("%.3f" % x[0] for x in c), c[0][1]),
         "  (a) / (c) = %.3f" % (med(a) / med(c)),
         "",
     ]
