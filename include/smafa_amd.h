@@ -368,6 +368,58 @@ int smafa_db_self_levels(smafa_db *db, uint32_t max_div, uint32_t *labels, uint6
 int smafa_db_self_forest_launch(smafa_db *db, uint32_t max_div, void *d_edges /* n_subjects - 1 smafa_hit */, void *d_level_ends /* max_div + 1 uint64 */);
 int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint64_t cap, uint64_t *level_ends);
 
+/* ------------------------------------------------- mutual-reachability forest: the merge tree of the density clusters */
+/*
+ * "The density clusters at EVERY bound, for one min_pts": smafa_db_self_density cures single linkage's chaining at one bound
+ * per call, smafa_db_self_forest gives every bound from one join but chains.  This call gives the hierarchy HDBSCAN starts
+ * from: a minimum spanning forest under the mutual-reachability distance.  Subjects are numbered in append order;
+ * D = max_div, M = min_pts (0 is taken as 1, as in the density call), L = seq_len, n = n_subjects.
+ *   ball(i, t)  = 1 + the number of OTHER subjects j != i with distance(i, j) <= t.  The row counts itself, and equal rows at
+ *                 different numbers count, exactly as smafa_db_self_density counts (degree[i] + 1 at bound t).
+ *   core[i]     = the smallest t in 0 .. D with ball(i, t) >= M; SMAFA_NONE if there is none: the row is SPARSE at D.  M <= 1
+ *                 gives core 0 everywhere, M = 2 the nearest-neighbour distance; in general it is the distance to the
+ *                 (M - 1)-th nearest other row, entry M - 2 of the row's list from smafa_db_self_neighbours(max_num_hits =
+ *                 M - 1) where that list has M - 1 entries.
+ *   the graph     vertices the subjects, edges the pairs (a, b) with distance <= D whose ends are both not sparse, an edge's
+ *                 weight w = max(distance(a, b), core[a], core[b]), so 0 <= w <= D.
+ *   edges       smafa_hit{query = a, subject = b, dist = w}, a < b, ordered by w ascending;
+ *   level_ends  max_div + 1 uint64: level_ends[t] = the number of edges with w <= t;
+ *   cores       n_subjects uint32, optional: core[i].
+ * For every t the edges [0, level_ends[t]) are acyclic and their connected components are exactly the components of the
+ * graph cut at weight t.  A pair has w <= t iff it is within t and both ends are core at t, so restricted to the rows with
+ * core <= t these components are byte for byte the core-row labels of smafa_db_self_density(db, t, M); rows with core > t are
+ * singletons; level_ends[t] = n_subjects minus the number of sets.  WHICH of several pairs of equal weight is chosen is free
+ * and may differ from run to run; cores, the counts per level and the partitions are functions of the store, D and M alone,
+ * the same under smafa_set_prefilter / smafa_set_zone_level / smafa_set_index, every SMAFA_JOIN_* setting and
+ * SMAFA_DENSITY_KEEP_MAX.  M <= 1: the result satisfies the contract of smafa_db_self_forest as it stands (w is the distance).
+ * Not in the reference.
+ * The store is joined ONCE, at bound min(D, L - 1); the join moves its pairs, each once, to the kept list of
+ * smafa_db_self_forest and tallies every pair at both ends, per distance (4 B x (min(D, L - 1) + 1) per subject, handle-owned,
+ * exact at any capacity of the list).  The cores come from the tallies, and Kruskal's algorithm then runs by weight class as
+ * for the plain forest, a pair weighed by its ends' cores.  Where the pairs exceed the list, the store is joined once more
+ * per class t at bound t: every pair of weight t is within t.
+ * Bounds no two rows can exceed (D >= L): nothing is scanned above L - 1.  If n >= M, every row still sparse after class
+ * L - 1 has core exactly L (every other row is within L), every surviving root r != 0 gets the edge (0, r, L) — two rows in
+ * different sets after class L - 1 are either L apart or have an end of core L — and level_ends[t] = n - 1 for t >= L.  If
+ * n < M every row is sparse, there is no edge and level_ends is all 0.
+ * n = 0 or 1: no scan and no edge, level_ends all 0, cores 0 where M <= 1, else SMAFA_NONE.  max_div = SMAFA_NONE, a NULL
+ * handle, NULL edges or NULL level_ends is SMAFA_ERR_INVALID, smafa_last_error() names the argument, and nothing is written.
+ * The self-join's SMAFA_ERR_NOMEM is inherited unchanged; a partial list is never spanned.
+ *
+ * smafa_db_self_reach_forest_launch: device-resident form.  d_edges = device buffer of n_subjects - 1 smafa_hit (the edges
+ * inside a level are in no particular order), d_level_ends = device buffer of max_div + 1 uint64, d_cores = device buffer of
+ * n_subjects uint32, or NULL.  Synchronisation as for smafa_db_self_components_launch.  smafa_last_call_kernels lists the
+ * scan-family instantiations first, then smafa_join::store_records_kernel, smafa_join::inverse_order_kernel where it ran,
+ * smafa_sf::init_forest_kernel, smafa_mr::tally_keep_kernel, smafa_mr::core_dist_kernel, smafa_mr::span_reach_kernel where it
+ * ran and smafa_sf::star_roots_kernel where it ran.
+ *
+ * smafa_db_self_reach_forest: host form.  cap = capacity of `edges` in rows; cap < n_subjects - 1 is SMAFA_ERR_INVALID and
+ * nothing is written.  The edges of one level are additionally ordered by (query, subject); level_ends holds max_div + 1
+ * entries, cores n_subjects entries or is NULL.
+ */
+int smafa_db_self_reach_forest_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_edges /* n_subjects - 1 smafa_hit */, void *d_level_ends /* max_div + 1 uint64 */, void *d_cores /* n_subjects uint32, may be NULL */);
+int smafa_db_self_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *edges, uint64_t cap, uint64_t *level_ends, uint32_t *cores /* n_subjects entries, may be NULL */);
+
 /* ------------------------------------------------- density clusters of the store (DBSCAN over the self-join) */
 /*
  * "Which of the store's rows belong together at bound max_div, where enough rows agree": single linkage chains — one sparse
@@ -714,6 +766,11 @@ int smafa_component_levels(const char *db_path, uint32_t max_divergence, int out
  * distance <= t are the merge tree of `smafa components --max-divergence t`; which of several pairs of equal distance joins
  * two components may differ from run to run.  An empty DB prints nothing. */
 int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int device);
+/* `smafa forest --min-pts M` (not in the reference): the same DB, and the mutual-reachability forest of its subjects up to
+ * max_divergence at min_pts (smafa_db_self_reach_forest), "{a}\t{b}\t{weight}\n" per edge, a < b, ordered by weight, then a,
+ * then b; with cores != 0 (`--cores`) the core distance of every subject instead, "{i}\t{core}\n" in subject order, -1 for a
+ * row that is sparse at the bound: the k-distance plot.  An empty DB prints nothing. */
+int smafa_reach_forest(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int cores, int out_fd, int device);
 /* `smafa density` (not in the reference): the same DB, and per subject its density-cluster label and its degree
  * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
  * is printed as -1.  An empty DB prints nothing. */

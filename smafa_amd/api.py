@@ -401,6 +401,32 @@ class SubjectStore:
         check(lib().smafa_db_self_forest_launch(self._h, _opt(max_divergence), C.c_void_p(d_edges) if d_edges else None,
                                                 C.c_void_p(d_level_ends) if d_level_ends else None))
 
+    # ---- mutual-reachability forest ----------------------------------------------------------
+    def self_reach_forest(self, max_divergence: int, min_pts: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(edges, level_ends, cores) — smafa_db_self_reach_forest: a minimum spanning forest under the mutual-reachability
+        distance w = max(distance(a, b), core[a], core[b]), the tree HDBSCAN starts from.  cores (uint32, n_subjects) is the
+        distance of every row to its (min_pts - 1)-th nearest other row, NONE where fewer are within max_divergence (the row
+        is sparse and in no edge).  edges are rows as self_forest gives them with dist = w, ordered by (w, query, subject);
+        level_ends (uint64, max_divergence + 1) counts the edges with w <= t.  The edges [0, level_ends[t]) are acyclic and
+        connect, among the rows with core <= t, exactly the core rows' clusters of self_density(t, min_pts).  min_pts <= 1 is
+        self_forest's contract.  forest_linkage takes the edges as they are."""
+        n = self.info().n_subjects
+        levels = int(max_divergence) + 1 if max_divergence is not None and 0 <= int(max_divergence) < _lib.NONE else 1
+        edges = np.zeros(max(n - 1, 1), dtype=HIT_DTYPE)
+        level_ends = np.zeros(levels, dtype=np.uint64)
+        cores = np.zeros(n, dtype=np.uint32)
+        check(lib().smafa_db_self_reach_forest(self._h, _opt(max_divergence), int(min_pts), edges.ctypes.data, max(n - 1, 0),
+                                               level_ends.ctypes.data_as(C.POINTER(C.c_uint64)), cores.ctypes.data if n else None))
+        return edges[: int(level_ends[-1])], level_ends, cores
+
+    def self_reach_forest_launch(self, max_divergence: int, min_pts: int, d_edges: int, d_level_ends: int, d_cores: int = 0) -> None:
+        """device-resident form (smafa_db_self_reach_forest_launch): up to n_subjects - 1 rows of three uint32 in d_edges, ordered
+        by weight, max_divergence + 1 level ends in d_level_ends (device uint64 each), and n_subjects uint32 core distances in
+        d_cores (0: not wanted)"""
+        check(lib().smafa_db_self_reach_forest_launch(self._h, _opt(max_divergence), int(min_pts), C.c_void_p(d_edges) if d_edges else None,
+                                                      C.c_void_p(d_level_ends) if d_level_ends else None,
+                                                      C.c_void_p(d_cores) if d_cores else None))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -708,6 +734,13 @@ def forest(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) 
     """`smafa forest`: "a\\tb\\tdist" per edge of a minimum spanning forest of the DB file's subjects up to max_divergence
     (smafa_db_self_forest), ordered by (dist, a, b), to out_fd."""
     check(lib().smafa_forest(os.fsencode(db_path), _opt(max_divergence), out_fd, device))
+
+
+def reach_forest(db_path: str, max_divergence: int, min_pts: int, cores: bool = False, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa forest --min-pts M`: "a\\tb\\tw" per edge of the mutual-reachability forest of the DB file's subjects up to
+    max_divergence at min_pts (smafa_db_self_reach_forest), ordered by (w, a, b), to out_fd — or, with cores, "i\\tcore" per
+    subject, -1 for a sparse row."""
+    check(lib().smafa_reach_forest(os.fsencode(db_path), _opt(max_divergence), int(min_pts), 1 if cores else 0, out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

@@ -28,6 +28,7 @@
 #include "neighbours.hip.h"
 #include "delta.hip.h"
 #include "forest.hip.h"
+#include "reach.hip.h"
 
 namespace smafa {
 
@@ -238,6 +239,11 @@ struct smafa_db {
         // forest (forest.hip.h): parent holds one union-find, 4 B per subject, live for one call; kept as for density; ctl[0] is the
         // kept total, ctl[1] the running edge total; count_ms (keep passes), link_ms (init + span launches), flatten_ms (the star
         // launch) and joins (1, or 1 + the scanned classes on the slow path)
+        // reach forest (reach.hip.h): parent holds the union-find and core[] behind it, 4 B x 2 per subject, live for one call; hist
+        // the tallies, 4 B x E per subject, zeroed at the start of every call; kept as for density; ctl[0] is the kept total,
+        // ctl[1] the rows that are not sparse, ctl[2] the running edge total; count_ms (tally/keep passes), filter_ms (the cores
+        // launch), link_ms (init + span launches), flatten_ms (the star launch) and joins as for the forest
+        DevBuf hist;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1195,7 +1201,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
-                      &db->join.kept, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
+                      &db->join.kept, &db->join.hist, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
         if (e) (void)hipEventDestroy(e);

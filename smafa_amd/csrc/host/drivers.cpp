@@ -781,6 +781,38 @@ int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int d
     return smafa::exception_code("smafa_forest");
 }
 
+// ------------------------------------------------------------------------------------ reach forest
+// The mutual-reachability forest of a DB file's subjects up to max_divergence at min_pts (smafa_db_self_reach_forest), printed
+// "{a}\t{b}\t{weight}\n" per edge in the host form's order: by weight, then a, then b — or, with `cores`, the core distance of
+// every subject instead, "{i}\t{core}\n" in subject order, -1 for a row that is sparse at the bound.
+int smafa_reach_forest(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int cores, int out_fd, int device) try {
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_reach_forest", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    const size_t T = (size_t)max_divergence + 1;
+    std::vector<smafa_hit> edges(std::max<size_t>(v.n, 2) - 1);  // (one row at least: the call takes no NULL buffer)
+    std::vector<uint64_t> level_ends(T);
+    std::vector<uint32_t> core(v.n);
+    rc = smafa_db_self_reach_forest(v.store.db, max_divergence, min_pts, edges.data(), edges.size(), level_ends.data(), core.data());
+    const size_t count = (size_t)level_ends[T - 1];
+    if (!rc && cores) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_u32(text, (uint32_t)i);
+        text.push_back('\t');
+        if (core[i] == SMAFA_NONE) text += "-1";
+        else append_u32(text, core[i]);
+        text.push_back('\n');
+    });
+    else if (!rc) rc = write_rows(out_fd, count, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_row(text, {edges[i].query, edges[i].subject, edges[i].dist});
+    });
+    if (rc) return rc;
+    log_line(1, "%llu edges among %llu sequences within %u at min_pts %u, took %llu seconds", (unsigned long long)count,
+             (unsigned long long)v.n, max_divergence, min_pts, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_reach_forest");
+}
+
 // ------------------------------------------------------------------------------------ density
 // The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
 // "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.

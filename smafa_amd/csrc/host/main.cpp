@@ -9,8 +9,9 @@
 //           within the bound; --since: those whose larger sequence number is at least ROW)
 //   components -d/--database FILE  --max-divergence INT  [--levels]   (this build only: the single-linkage component of
 //           every subject; --levels: at every bound 0 .. INT)
-//   forest  -d/--database FILE  --max-divergence INT   (this build only: the minimum spanning forest of the subjects up to
-//           the bound, the merge tree of the components at every bound 0 .. INT)
+//   forest  -d/--database FILE  --max-divergence INT  [--min-pts INT [--cores]]   (this build only: the minimum spanning forest
+//           of the subjects up to the bound, the merge tree of the components at every bound 0 .. INT; --min-pts: the forest
+//           under the mutual-reachability distance, the merge tree of the density clusters; --cores: the core distances instead)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
@@ -59,10 +60,14 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        components of the database's own sequences at the bound, one \"i<TAB>label\" line per sequence, label = the\n"
             "        smallest sequence number of its component; --levels: one label column per bound 0 .. <INT>,\n"
             "        \"i<TAB>label_0<TAB>...<TAB>label_INT\", from one join)\n"
-            "forest  -d, --database <FILE>  --max-divergence <INT>  [--device <N>]  (not in the reference: a minimum spanning forest of\n"
+            "forest  -d, --database <FILE>  --max-divergence <INT>  [--min-pts <INT> [--cores]]  [--device <N>]  (not in the reference: a minimum spanning forest of\n"
             "        the database's own sequences under the pairs within the bound, one \"a<TAB>b<TAB>divergence\" line per edge, a < b,\n"
             "        ordered by divergence, then a, then b; the lines up to divergence t are the merge tree of `components` at t;\n"
             "        which of several pairs of equal divergence joins two components may differ from run to run)\n"
+            "        [--min-pts <INT>]: the forest under the mutual-reachability distance max(divergence, core(a), core(b)) in the\n"
+            "        third column, core(i) = the divergence of sequence i's (min-pts - 1)-th nearest other sequence; the lines up to\n"
+            "        weight t are the merge tree of the core sequences of `density` at bound t; sequences with fewer than min-pts - 1\n"
+            "        others within the bound are in no line; --cores: one \"i<TAB>core\" line per sequence instead, -1 for those)\n"
             "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
@@ -118,7 +123,7 @@ int main(int argc, char **argv) {
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0;
     bool have_min_pts = false, have_since = false;
     unsigned long long since = 0;
-    bool have_max_div = false, packed = false, no_gpu = false, levels = false;
+    bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
     int verbosity = 1;  // the reference logs at info level unless told otherwise (bird_tool_utils set_log_level)
@@ -151,7 +156,7 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &device)) return usage("--device needs an unsigned integer");
         } else if (a == "--packed") {
             packed = true;
-        } else if (a == "--min-pts" && cmd == "density") {
+        } else if (a == "--min-pts" && (cmd == "density" || cmd == "forest")) {
             if (!parse_u32(value(), &min_pts)) return usage("--min-pts needs an unsigned integer");
             have_min_pts = true;
         } else if (a == "--radius" && cmd == "peaks") {
@@ -166,6 +171,8 @@ int main(int argc, char **argv) {
             have_since = true;
         } else if (a == "--levels" && cmd == "components") {
             levels = true;
+        } else if (a == "--cores" && cmd == "forest") {
+            cores = true;
         } else if (a == "--no-gpu") {
             no_gpu = true;
         } else if (a == "--gpus") {
@@ -233,7 +240,9 @@ int main(int argc, char **argv) {
     } else if (cmd == "forest") {
         if (!database) return usage("forest needs --database");
         if (!have_max_div) return usage("forest needs --max-divergence");
-        rc = smafa_forest(database, max_div, 1, (int)device);
+        if (cores && !have_min_pts) return usage("--cores needs --min-pts");
+        rc = have_min_pts ? smafa_reach_forest(database, max_div, min_pts, cores ? 1 : 0, 1, (int)device)
+                          : smafa_forest(database, max_div, 1, (int)device);
     } else if (cmd == "density") {
         if (!database) return usage("density needs --database");
         if (!have_max_div) return usage("density needs --max-divergence");

@@ -1,8 +1,8 @@
 // self_join.hip.h — host code of the self-join of a resident store.  Two drivers walk the store and know no consumer: join_pass (every
 // row against the rows behind it) and delta_pass (the rows appended since a mark against the whole store).  Each cuts its spans
-// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Nine calls
-// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours and join_forest over
-// join_pass, delta_pairs and delta_components over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
+// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Ten calls
+// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours, join_forest and
+// join_reach_forest over join_pass, delta_pairs and delta_components over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
 // or more JoinConsumers: timed_consumer (a kernel per piece), watching (that, gated on a device counter read at every wait),
 // keeping_consumer (that, with J.kept grown by the gate).  Their C ABI is self_join_abi.hip.h.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
@@ -18,7 +18,7 @@ struct JoinCall {
     double *slot = nullptr;      // the timed pass whose events are not read yet: the J.*_ms it is booked to ...
     const char *what = nullptr;  // ... and its level-3 trace text (nullptr: none)
     unsigned long long ctl_seen = 0;  // J.ctl[0] as a watching consumer last read it, in front of a piece's wait: what the call's kernels
-                                      // counted there over the pieces before the one just scanned — pairs kept (density, peaks, forest),
+                                      // counted there over the pieces before the one just scanned — pairs kept (density, peaks, forests),
                                       // entries appended (neighbours), labels that are none (components update)
 };
 
@@ -943,5 +943,101 @@ static int join_forest(smafa_db *db, uint32_t max_div, smafa_hit *d_edges, unsig
     log_line(2, "forest of %u rows up to bound %u, joined at bound %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, "
              "scans %.3f ms, keep %.3f ms, span %.3f ms, star %.3f ms, %llu pairs kept", n, max_div, scan_div, J.blocks + J.rescans, J.rescans,
              J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, kept_total);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_reach_forest_launch (reach.hip.h): join_forest with an edge's weight max(dist, core[a], core[b]).  d_edges is n - 1
+// rows, d_level_ends max_div + 1 counters, d_cores n entries or nullptr; J.parent one union-find and core[] behind it, J.hist the
+// tallies (E per subject, zeroed here), J.ctl the kept total, the rows that are not sparse and the running edge total.  The join
+// runs ONCE at bound E - 1 with tally_keep_kernel per piece (the exactly-once rule, so pos_of[]): the kept pairs move to J.kept
+// and are tallied per end and distance.  core_dist_kernel then makes core[] of the tallies; fewer than two rows that are not
+// sparse: no edge.  Else the kept total decides (kept_plan) how span_reach_kernel gets the pairs: E launches over the kept list,
+// one per weight class, or the store joined once more per class at bound t with the raw piece lists spanned at only_dist = t (every
+// pair of weight t is within t).  max_div >= L and n >= min_pts: a row still sparse behind class L - 1 has core exactly L, and
+// star_roots_kernel hangs every surviving root under row 0 at weight L.  One path for every min_pts >= 1.
+static int join_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *d_edges, unsigned long long *d_level_ends,
+                             uint32_t *d_cores) {
+    auto &J = db->join;
+    const uint32_t n_levels = max_div + 1u, E = std::min(n_levels, std::max<uint32_t>(db->L, 1u)), scan_div = E - 1u;
+    const bool all_near = max_div >= db->L && db->n >= min_pts;
+    JoinCall c{db};
+    RC_TRY(join_begin(c, d_level_ends, n_levels, 2));
+    if (c.nothing) {  // no row, or one: no edge, every level ends at 0; the one row is core at 0 where it alone is enough
+        if (d_cores && db->n) HIP_TRY(hipMemsetAsync(d_cores, min_pts <= 1u ? 0 : 0xff, db->n * sizeof(uint32_t), db->stream));
+        return SMAFA_OK;
+    }
+    const uint32_t n = (uint32_t)db->n;
+    const unsigned long long room = n - 1u;
+    RC_TRY(J.parent.ensure((size_t)n * 2u * sizeof(uint32_t)));
+    RC_TRY(J.hist.ensure((size_t)n * E * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(3 * sizeof(unsigned long long)));
+    uint32_t *const parent = J.parent.as<uint32_t>(), *const core = parent + n, *const hist = J.hist.as<uint32_t>();
+    unsigned long long *const n_dense = J.ctl.as<unsigned long long>() + 1, *const n_edges = n_dense + 1;
+    RC_TRY(timed_begin(c, &J.link_ms, "reach: parent[] initialised, the tallies zeroed"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 3 * sizeof(unsigned long long), db->stream));
+    HIP_TRY(hipMemsetAsync(hist, 0, (size_t)n * E * sizeof(uint32_t), db->stream));
+    hipLaunchKernelGGL(smafa_sf::init_forest_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n);
+    RC_TRY(timed_end(c));
+    RC_TRY(join_positions(c));
+    JoinConsumer tally = keeping_consumer(c, &J.count_ms, "reach: parent[] untouched, a piece's rows tallied and kept", [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_mr::tally_keep_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, J.pos_of.as<uint32_t>(), J.kept.as<smafa_hit>(), (unsigned long long)kept_room(db),
+                           J.ctl.as<unsigned long long>(), hist, E);
+    });
+    uint32_t only_dist = 0;  // the class the span launches handle
+    const auto launch_span = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_mr::span_reach_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
+                           p.order, core, parent, only_dist, d_edges, room, n_edges);
+    };
+    const auto end_class = [&] {  // (stream-ordered: behind the class's last launch, in front of the next class's first)
+        HIP_TRY(hipMemcpyAsync(d_level_ends + only_dist, n_edges, sizeof(unsigned long long), hipMemcpyDeviceToDevice, db->stream));
+        return SMAFA_OK;
+    };
+    JoinConsumer span = timed_consumer(c, &J.link_ms, "reach: a class of a piece's rows spanned", launch_span);
+    RC_TRY(join_pass(c, scan_div, tally));
+    RC_TRY(timed_pass(c, &J.filter_ms, "reach: the core distances", [&] {
+        hipLaunchKernelGGL(smafa_mr::core_dist_kernel, row_grid(n), dim3(256), 0, db->stream, hist, n, E, min_pts,
+                           all_near ? db->L : SMAFA_NONE, core, d_cores, n_dense);
+    }));
+    unsigned long long totals[2] = {0, 0};  // every tally is final: the kept total; the rows that are not sparse
+    HIP_TRY(hipMemcpyAsync(totals, J.ctl.p, sizeof totals, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    const unsigned long long kept_total = totals[0];
+    // (fewer than two rows that are not sparse: no pair has a weight)
+    const KeptPlan plan = totals[1] < 2 ? kKeptNothing : kept_plan(db, kept_total, "reach", "span");
+    if (plan == kKeptOnce) {
+        RC_TRY(timed_begin(c, &J.link_ms, "reach: the kept list spanned, class by class"));
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            launch_span(kept_piece(db, kept_total));
+            RC_TRY(end_class());
+        }
+        RC_TRY(timed_end(c, E));
+        span.used = true;
+    } else if (plan == kKeptJoinAgain) {
+        log_line(2, "reach: %llu pairs, the kept list holds %llu: the store is joined once more per class, at the bounds 0 .. %u",
+                 kept_total, (unsigned long long)kept_room(db), scan_div);
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            RC_TRY(join_pass(c, only_dist, span));
+            RC_TRY(end_class());
+        }
+    }
+    RC_TRY(timed_sync(c));
+    if (all_near) {
+        RC_TRY(timed_pass(c, &J.flatten_ms, "reach: the surviving roots hung under row 0", [&] {
+            hipLaunchKernelGGL(smafa_sf::star_roots_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n, db->L, d_edges, room, n_edges,
+                               d_level_ends, n_levels);
+        }));
+        RC_TRY(timed_sync(c));
+    }
+    join_finish(c);
+    note_call_kernel(db, "smafa_sf::init_forest_kernel");
+    if (tally.used) note_call_kernel(db, "smafa_mr::tally_keep_kernel");
+    note_call_kernel(db, "smafa_mr::core_dist_kernel");
+    if (span.used) note_call_kernel(db, "smafa_mr::span_reach_kernel");
+    if (all_near) note_call_kernel(db, "smafa_sf::star_roots_kernel");
+    log_line(2, "reach forest of %u rows up to bound %u at min_pts %u, joined at bound %u: %u scans (%u of them repeats) in %u join%s, "
+             "records %.3f ms, scans %.3f ms, tally %.3f ms, cores %.3f ms, span %.3f ms, star %.3f ms, %llu pairs kept, %llu rows not sparse",
+             n, max_div, min_pts, scan_div, J.blocks + J.rescans, J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms,
+             J.filter_ms, J.link_ms, J.flatten_ms, kept_total, totals[1]);
     return SMAFA_OK;
 }

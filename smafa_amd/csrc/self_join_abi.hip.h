@@ -1,7 +1,7 @@
-// self_join_abi.hip.h — the C ABI of the self-join: the eighteen smafa_db_self_* entry points, nine calls in two forms each.  The
+// self_join_abi.hip.h — the C ABI of the self-join: the twenty smafa_db_self_* entry points, ten calls in two forms each.  The
 // *_launch form checks its arguments and hands the caller's device pointers to the call of self_join.hip.h.  The host form checks
 // the same, then runs the same call on the handle's own buffers and copies the results out: pairs_to_host for the two pair
-// lists, HostForm for the seven calls that return arrays and counters.
+// lists, HostForm for the eight calls that return arrays and counters.
 // A new call: its two entry points here, built from self_args / HostForm / trim; what it checks beyond self_args, and where it zeroes
 // its outputs among its checks, is its own (the order is part of the contract: tests hold what a failing check leaves untouched).
 // Included once by engine.hip, inside extern "C", behind self_join.hip.h.
@@ -12,7 +12,7 @@ static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counters and offs
 // ---- argument checks: `who` is the entry point, the name is the argument's
 static int missing(const char *who, const char *name) { return set_error(SMAFA_ERR_INVALID, "%s: NULL %s", who, name); }
 
-// what sixteen of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
+// what eighteen of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
 static int self_args(const char *who, const smafa_db *db, bool has_a, const char *a, bool has_b, const char *b, uint32_t max_div,
                      const char *needs) {
     if (!db) return missing(who, "handle");
@@ -262,6 +262,51 @@ int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint6
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_forest");
+}
+
+// ---- mutual-reachability forest
+int smafa_db_self_reach_forest_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_edges, void *d_level_ends,
+                                      void *d_cores) try {
+    RC_TRY(self_args("smafa_db_self_reach_forest_launch", db, d_edges, "edges", d_level_ends, "level_ends", max_div,
+                     "a reach forest needs a bound"));
+    return join_reach_forest(db, max_div, std::max<uint32_t>(min_pts, 1u), (smafa_hit *)d_edges, (unsigned long long *)d_level_ends,
+                             (uint32_t *)d_cores);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_reach_forest_launch");
+}
+
+int smafa_db_self_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *edges, uint64_t cap, uint64_t *level_ends,
+                               uint32_t *cores) try {
+    RC_TRY(self_args("smafa_db_self_reach_forest", db, edges, "edges", level_ends, "level_ends", max_div, "a reach forest needs a bound"));
+    const uint64_t T = (uint64_t)max_div + 1u, n = db->n, room = n ? n - 1 : 0;
+    if (cap < room)  // (nothing is written, level_ends and cores included)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_reach_forest: edges holds %llu rows, a forest of %llu subjects may need %llu",
+                         (unsigned long long)cap, (unsigned long long)n, (unsigned long long)room);
+    std::fill(level_ends, level_ends + T, (uint64_t)0);
+    const HostForm h{db};
+    auto &J = db->join;
+    // the edges, and the cores behind them, on their way to the caller: 12 B per edge, 4 B per subject
+    const uint64_t edge_bytes = std::max<uint64_t>(room, 1) * sizeof(smafa_hit);
+    RC_TRY(h.stage(edge_bytes + (cores ? n * sizeof(uint32_t) : 0), T));
+    uint32_t *const d_cores = cores ? reinterpret_cast<uint32_t *>(J.out.as<char>() + edge_bytes) : nullptr;
+    RC_TRY(join_reach_forest(db, max_div, std::max<uint32_t>(min_pts, 1u), J.out.as<smafa_hit>(), h.cnt(), d_cores));
+    RC_TRY(h.fetch(level_ends, h.cnt(), T * sizeof(uint64_t)));
+    RC_TRY(h.fetch(cores, d_cores, n * sizeof(uint32_t)));
+    RC_TRY(h.wait());  // (a wait of its own: the edge total decides the next copy)
+    const uint64_t total = level_ends[T - 1];
+    if (total > room) return set_error(SMAFA_ERR_DEVICE, "smafa_db_self_reach_forest: %llu edges among %llu subjects are no forest",
+                                       (unsigned long long)total, (unsigned long long)n);
+    RC_TRY(h.fetch(edges, J.out.p, total * sizeof(smafa_hit)));
+    RC_TRY(h.wait());
+    // a level's edges arrive in any order: (query, subject) inside each level, so that a given forest prints one way
+    for (uint64_t t = 0, begin = 0; t < T && begin < total; begin = level_ends[t++])
+        std::sort(edges + begin, edges + level_ends[t], [](const smafa_hit &x, const smafa_hit &y) {
+            return x.query != y.query ? x.query < y.query : x.subject < y.subject;
+        });
+    trim({&db->hits, &J.kept, &J.hist});
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_reach_forest");
 }
 
 // ---- density
