@@ -420,6 +420,58 @@ int smafa_db_self_forest(smafa_db *db, uint32_t max_div, smafa_hit *edges, uint6
 int smafa_db_self_reach_forest_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, void *d_edges /* n_subjects - 1 smafa_hit */, void *d_level_ends /* max_div + 1 uint64 */, void *d_cores /* n_subjects uint32, may be NULL */);
 int smafa_db_self_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *edges, uint64_t cap, uint64_t *level_ends, uint32_t *cores /* n_subjects entries, may be NULL */);
 
+/* ------------------------------------------------- stable clusters: HDBSCAN's selection over the mutual-reachability forest */
+/*
+ * "One label per subject, chosen per region of the data at the level where that region's cluster is most persistent": the
+ * step behind smafa_db_self_reach_forest.  Distances here are integers 0 .. D, ties are the rule, so the textbook's binary
+ * merges and lambda = 1 / distance are ill-defined; this is the LEVEL-WISE definition, an exact integer function of the store
+ * and of D = max_div, M = min_pts (0 is taken as 1) and S = min_cluster_size (0 is taken as max(M, 1)) alone.
+ *   levels      core[] is the reach forest's.  For t in 0 .. D, lab_t[i] = the smallest subject number of subject i's set in
+ *               that call's graph cut at weight t (the partitions its level_ends delimit, with its rules for D >= L and n < M).
+ *               Subject i is IN at t iff core[i] <= t.  size_t(r) = the number of subjects in at t with lab_t[i] == r; a subject
+ *               that is not in is a singleton of size 0.  A component (t, r) is BIG iff size_t(r) >= S.  kids(t, r) = the
+ *               number of big components (t - 1, r') with lab_t[r'] == r; kids(0, .) = 0.
+ *   clusters    A big component STARTS a cluster iff kids != 1; otherwise it CONTINUES the cluster of its one big child.  A
+ *               cluster C is therefore a chain of components (t_lo, r_lo) .. (t_hi, r_hi).  Its parent is the cluster started
+ *               at (t_hi + 1, lab_{t_hi + 1}[r_hi]) when t_hi < D (that component has kids >= 2); when t_hi == D it is a root.
+ *               stability(C) = the sum over t = t_lo .. t_hi of size_t(r_t), as uint64.  This is HDBSCAN's
+ *               sum over points (lambda_p - lambda_birth) with lambda measured in LEVELS instead of 1 / distance; the
+ *               result depends on D through the roots' lifetime: a larger D lengthens every root and nothing else.
+ *   selection   (excess of mass)  best(C) = max(stability(C), the sum of best(child) over C's children).  C is CHOSEN iff
+ *               stability(C) >= that sum (a leaf's sum is 0; a tie goes to the parent) and no ancestor of C is chosen.
+ *   labels      n_subjects uint32: labels[i] = r_hi of the chosen cluster C with core[i] <= t_hi and lab_{t_hi}[i] == r_hi —
+ *               there is at most one —, SMAFA_NONE where there is none: noise.  A label is the smallest subject number of its
+ *               cluster.
+ *   joined      n_subjects uint32, optional: the smallest t in [t_lo, t_hi] at which subject i is in and in C's component;
+ *               the subjects of C's descendant clusters get t_lo; noise gets SMAFA_NONE.
+ *   n_clusters  one uint64 ON THE HOST in both forms: the number of chosen clusters.
+ *   cores       n_subjects uint32, optional: core[i], as smafa_db_self_reach_forest gives it.
+ * Every output is the same from run to run and under smafa_set_prefilter / smafa_set_zone_level / smafa_set_index, every
+ * SMAFA_JOIN_* setting and SMAFA_DENSITY_KEEP_MAX.  Not in the reference.
+ * The call runs smafa_db_self_reach_forest_launch's passes into handle-owned buffers and then works from the at most n - 1
+ * edges and the cores alone: the edges are united class by class over a fresh union-find, and behind every class the root,
+ * the size and the big children of every component are recorded; the selection runs once up and once down the levels.  Levels
+ * above L are never scanned, allocated or launched: they are all alike, and their share of a stability, size x (D - L + 1), is
+ * added arithmetically.  The number of launches behind the forest is 5 x (min(D, L) + 1) + 2 whatever the store holds.  HBM
+ * on top of the reach forest's: 4 B x 2 x (min(D, L) + 1) per subject for the root and flag planes, 44 B per subject of
+ * per-level state, 12 B per subject for the edges and 8 B x (D + 1).
+ * n = 0: nothing is written but *n_clusters = 0.  n = 1: no scan; with M <= 1 and S <= 1 the subject is one cluster, label 0,
+ * joined 0; otherwise noise; cores as the reach forest's.
+ * Argument checks, in this order, each SMAFA_ERR_INVALID with smafa_last_error() naming the argument and NOTHING written: a
+ * NULL handle; NULL labels; NULL n_clusters; max_div == SMAFA_NONE; host form only: cap < n_subjects.  The self-join's
+ * SMAFA_ERR_NOMEM is inherited unchanged.
+ *
+ * smafa_db_self_stable_launch: device-resident form.  d_labels, d_joined (or NULL), d_cores (or NULL) = device buffers of
+ * n_subjects uint32.  The call waits for its own work — *n_clusters is valid on return, and so are the buffers.
+ * smafa_last_call_kernels lists the reach forest's kernels as that call lists them, then smafa_st::unite_class_kernel,
+ * smafa_st::snapshot_kernel, smafa_st::census_kernel (more than one level), smafa_st::adopt_kernel, smafa_st::excess_kernel,
+ * smafa_st::choose_kernel and smafa_st::assign_kernel.
+ *
+ * smafa_db_self_stable: host form.  cap = capacity of `labels` — and of `joined` and `cores` where given — in entries.
+ */
+int smafa_db_self_stable_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t min_cluster_size, void *d_labels /* n_subjects uint32 */, void *d_joined /* n_subjects uint32, may be NULL */, void *d_cores /* n_subjects uint32, may be NULL */, uint64_t *n_clusters /* host */);
+int smafa_db_self_stable(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t min_cluster_size, uint32_t *labels, uint32_t *joined /* may be NULL */, uint32_t *cores /* may be NULL */, uint64_t cap, uint64_t *n_clusters);
+
 /* ------------------------------------------------- density clusters of the store (DBSCAN over the self-join) */
 /*
  * "Which of the store's rows belong together at bound max_div, where enough rows agree": single linkage chains — one sparse
@@ -771,6 +823,10 @@ int smafa_forest(const char *db_path, uint32_t max_divergence, int out_fd, int d
  * then b; with cores != 0 (`--cores`) the core distance of every subject instead, "{i}\t{core}\n" in subject order, -1 for a
  * row that is sparse at the bound: the k-distance plot.  An empty DB prints nothing. */
 int smafa_reach_forest(const char *db_path, uint32_t max_divergence, uint32_t min_pts, int cores, int out_fd, int device);
+/* `smafa stable` (not in the reference): the same DB, and per subject the label of its stable cluster (smafa_db_self_stable at
+ * max_divergence, min_pts and min_cluster_size), "{i}\t{label}\n" in subject order, -1 for noise; with joined != 0
+ * (`--joined`) a third column, the level at which the subject joined its cluster, -1 for noise.  An empty DB prints nothing. */
+int smafa_stable(const char *db_path, uint32_t max_divergence, uint32_t min_pts, uint32_t min_cluster_size, int joined, int out_fd, int device);
 /* `smafa density` (not in the reference): the same DB, and per subject its density-cluster label and its degree
  * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
  * is printed as -1.  An empty DB prints nothing. */

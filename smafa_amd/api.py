@@ -427,6 +427,37 @@ class SubjectStore:
                                                       C.c_void_p(d_level_ends) if d_level_ends else None,
                                                       C.c_void_p(d_cores) if d_cores else None))
 
+    # ---- stable clusters ----------------------------------------------------------------------
+    def self_stable_clusters(self, max_divergence: int, min_pts: int, min_cluster_size: int = 0, joined: bool = False, cores: bool = False):
+        """(labels, n_clusters[, joined][, cores]) — smafa_db_self_stable: HDBSCAN's selection over the hierarchy of
+        self_reach_forest(max_divergence, min_pts), counted in levels.  labels (uint32, n_subjects) is the smallest subject number
+        of the row's chosen cluster, NONE for noise; a cluster holds at least min_cluster_size rows (0: min_pts) and is kept
+        where its stability — its size summed over the levels it lives through — is at least what its children's best add up
+        to.  joined (uint32) is the level at which the row joined its cluster, cores the reach forest's core distances.  Every
+        output is a function of the store and the three parameters alone."""
+        n = self.info().n_subjects
+        labels = np.zeros(n, dtype=np.uint32)
+        since = np.zeros(n, dtype=np.uint32) if joined else None
+        core = np.zeros(n, dtype=np.uint32) if cores else None
+        count = C.c_uint64(0)
+        # (an empty store: a pointer all the same, the call takes no NULL labels)
+        check(lib().smafa_db_self_stable(self._h, _opt(max_divergence), int(min_pts), int(min_cluster_size),
+                                         labels.ctypes.data if n else C.cast(C.pointer(C.c_uint32(0)), C.c_void_p),
+                                         since.ctypes.data if joined and n else None, core.ctypes.data if cores and n else None, n,
+                                         C.byref(count)))
+        return (labels, int(count.value)) + ((since,) if joined else ()) + ((core,) if cores else ())
+
+    def self_stable_clusters_launch(self, max_divergence: int, min_pts: int, min_cluster_size: int, d_labels: int, d_joined: int = 0,
+                                    d_cores: int = 0) -> int:
+        """device-resident form (smafa_db_self_stable_launch): n_subjects uint32 labels in d_labels, and where given (0: not
+        wanted) as many joined levels in d_joined and core distances in d_cores; -> n_clusters, the one value that crosses to the
+        host (the call has waited for its work when it returns)"""
+        count = C.c_uint64(0)
+        check(lib().smafa_db_self_stable_launch(self._h, _opt(max_divergence), int(min_pts), int(min_cluster_size),
+                                                C.c_void_p(d_labels) if d_labels else None, C.c_void_p(d_joined) if d_joined else None,
+                                                C.c_void_p(d_cores) if d_cores else None, C.byref(count)))
+        return int(count.value)
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -741,6 +772,13 @@ def reach_forest(db_path: str, max_divergence: int, min_pts: int, cores: bool = 
     max_divergence at min_pts (smafa_db_self_reach_forest), ordered by (w, a, b), to out_fd — or, with cores, "i\\tcore" per
     subject, -1 for a sparse row."""
     check(lib().smafa_reach_forest(os.fsencode(db_path), _opt(max_divergence), int(min_pts), 1 if cores else 0, out_fd, device))
+
+
+def stable_clusters(db_path: str, max_divergence: int, min_pts: int, min_cluster_size: int = 0, joined: bool = False, out_fd: int = 1,
+                    device: int = 0) -> None:
+    """`smafa stable`: "i\\tlabel" per subject of the DB file (smafa_db_self_stable), -1 for noise, to out_fd — with joined a third
+    column, the level at which the subject joined its cluster."""
+    check(lib().smafa_stable(os.fsencode(db_path), _opt(max_divergence), int(min_pts), int(min_cluster_size), 1 if joined else 0, out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

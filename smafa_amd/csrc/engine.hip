@@ -29,6 +29,7 @@
 #include "delta.hip.h"
 #include "forest.hip.h"
 #include "reach.hip.h"
+#include "stable.hip.h"
 
 namespace smafa {
 
@@ -244,6 +245,11 @@ struct smafa_db {
         // ctl[1] the rows that are not sparse, ctl[2] the running edge total; count_ms (tally/keep passes), filter_ms (the cores
         // launch), link_ms (init + span launches), flatten_ms (the star launch) and joins as for the forest
         DevBuf hist;
+        // stable clusters (stable.hip.h): the reach forest's state as above, and `stable`, live for one call: the forest's edges
+        // and level ends, the root and flag planes (4 B x 2 per subject and plane), kids[], two halves of size[], run[] and sum[]
+        // and the chosen total (stable_layout, self_join.hip.h); select_ms: everything behind the reach forest's last pass
+        DevBuf stable;
+        double select_ms = 0;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1201,7 +1207,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
-                      &db->join.kept, &db->join.hist, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
+                      &db->join.kept, &db->join.hist, &db->join.stable, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
         if (e) (void)hipEventDestroy(e);

@@ -813,6 +813,40 @@ int smafa_reach_forest(const char *db_path, uint32_t max_divergence, uint32_t mi
     return smafa::exception_code("smafa_reach_forest");
 }
 
+// ------------------------------------------------------------------------------------ stable clusters
+// The stable-cluster label of every subject of a DB file (smafa_db_self_stable), printed "{i}\t{label}\n" in subject order — with
+// `joined` "{i}\t{label}\t{level}\n", the level at which the subject joined its cluster; noise rows have -1 in both columns.
+int smafa_stable(const char *db_path, uint32_t max_divergence, uint32_t min_pts, uint32_t min_cluster_size, int joined, int out_fd,
+                 int device) try {
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_stable", db_path, max_divergence, device, v);
+    if (rc || v.empty) return rc;
+    std::vector<uint32_t> labels(v.n), since(joined ? v.n : 0);
+    uint64_t count = 0;
+    rc = smafa_db_self_stable(v.store.db, max_divergence, min_pts, min_cluster_size, labels.data(), joined ? since.data() : nullptr, nullptr,
+                              labels.size(), &count);
+    const auto append_or_none = [](std::string &text, uint32_t value) {
+        if (value == SMAFA_NONE) text += "-1";
+        else append_u32(text, value);
+    };
+    if (!rc) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_u32(text, (uint32_t)i);
+        text.push_back('\t');
+        append_or_none(text, labels[i]);
+        if (joined) {
+            text.push_back('\t');
+            append_or_none(text, since[i]);
+        }
+        text.push_back('\n');
+    });
+    if (rc) return rc;
+    log_line(1, "%llu stable clusters among %llu sequences up to %u at min_pts %u, min_cluster_size %u, took %llu seconds",
+             (unsigned long long)count, (unsigned long long)v.n, max_divergence, min_pts, min_cluster_size, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_stable");
+}
+
 // ------------------------------------------------------------------------------------ density
 // The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
 // "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.

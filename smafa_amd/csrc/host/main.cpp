@@ -12,6 +12,8 @@
 //   forest  -d/--database FILE  --max-divergence INT  [--min-pts INT [--cores]]   (this build only: the minimum spanning forest
 //           of the subjects up to the bound, the merge tree of the components at every bound 0 .. INT; --min-pts: the forest
 //           under the mutual-reachability distance, the merge tree of the density clusters; --cores: the core distances instead)
+//   stable  -d/--database FILE  --max-divergence INT  --min-pts INT  [--min-cluster-size INT] [--joined]   (this build only: the
+//           stable cluster of every subject, HDBSCAN's selection over the forest under the mutual-reachability distance)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
@@ -68,6 +70,11 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        third column, core(i) = the divergence of sequence i's (min-pts - 1)-th nearest other sequence; the lines up to\n"
             "        weight t are the merge tree of the core sequences of `density` at bound t; sequences with fewer than min-pts - 1\n"
             "        others within the bound are in no line; --cores: one \"i<TAB>core\" line per sequence instead, -1 for those)\n"
+            "stable  -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--min-cluster-size <INT>] [--joined]  [--device <N>]\n"
+            "        (not in the reference: stable clusters of the database's own sequences, one \"i<TAB>label\" line per sequence: the\n"
+            "        clusters of `forest --min-pts` at every weight 0 .. <INT>, each kept at the levels where it persists longest (HDBSCAN's\n"
+            "        excess of mass, counted in levels); label = the smallest sequence number of the cluster, -1 for noise; a cluster holds at\n"
+            "        least min-cluster-size sequences (default: min-pts); --joined: a third column, the level at which the sequence joined)\n"
             "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
@@ -120,10 +127,10 @@ int main(int argc, char **argv) {
     const bool is_cluster = cmd == "cluster";
     const char *input = nullptr, *database = nullptr, *query = nullptr;
     std::vector<const char *> count_paths;
-    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0;
+    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0;
     bool have_min_pts = false, have_since = false;
     unsigned long long since = 0;
-    bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false;
+    bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false, joined = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
     int verbosity = 1;  // the reference logs at info level unless told otherwise (bird_tool_utils set_log_level)
@@ -156,9 +163,13 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &device)) return usage("--device needs an unsigned integer");
         } else if (a == "--packed") {
             packed = true;
-        } else if (a == "--min-pts" && (cmd == "density" || cmd == "forest")) {
+        } else if (a == "--min-pts" && (cmd == "density" || cmd == "forest" || cmd == "stable")) {
             if (!parse_u32(value(), &min_pts)) return usage("--min-pts needs an unsigned integer");
             have_min_pts = true;
+        } else if (a == "--min-cluster-size" && cmd == "stable") {
+            if (!parse_u32(value(), &min_cluster_size)) return usage("--min-cluster-size needs an unsigned integer");
+        } else if (a == "--joined" && cmd == "stable") {
+            joined = true;
         } else if (a == "--radius" && cmd == "peaks") {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
         } else if (a == "--since" && cmd == "pairs") {
@@ -243,6 +254,11 @@ int main(int argc, char **argv) {
         if (cores && !have_min_pts) return usage("--cores needs --min-pts");
         rc = have_min_pts ? smafa_reach_forest(database, max_div, min_pts, cores ? 1 : 0, 1, (int)device)
                           : smafa_forest(database, max_div, 1, (int)device);
+    } else if (cmd == "stable") {
+        if (!database) return usage("stable needs --database");
+        if (!have_max_div) return usage("stable needs --max-divergence");
+        if (!have_min_pts) return usage("stable needs --min-pts");
+        rc = smafa_stable(database, max_div, min_pts, min_cluster_size, joined ? 1 : 0, 1, (int)device);
     } else if (cmd == "density") {
         if (!database) return usage("density needs --database");
         if (!have_max_div) return usage("density needs --max-divergence");

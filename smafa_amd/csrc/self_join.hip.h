@@ -1,8 +1,9 @@
 // self_join.hip.h — host code of the self-join of a resident store.  Two drivers walk the store and know no consumer: join_pass (every
 // row against the rows behind it) and delta_pass (the rows appended since a mark against the whole store).  Each cuts its spans
-// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Ten calls
-// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours, join_forest and
-// join_reach_forest over join_pass, delta_pairs and delta_components over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
+// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Eleven calls
+// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours, join_forest,
+// join_reach_forest and join_stable (the reach forest's passes, then its own) over join_pass, delta_pairs and delta_components
+// over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
 // or more JoinConsumers: timed_consumer (a kernel per piece), watching (that, gated on a device counter read at every wait),
 // keeping_consumer (that, with J.kept grown by the gate).  Their C ABI is self_join_abi.hip.h.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
@@ -99,7 +100,7 @@ static int join_begin(JoinCall &c, unsigned long long *d_count, size_t counters,
     db->call_ms = 0.f;
     db->call_launches = db->call_scans = db->last_launches = 0;
     db->timed = false;
-    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = 0.0;
+    J.rec_ms = J.scan_ms = J.filter_ms = J.link_ms = J.flatten_ms = J.count_ms = J.select_ms = 0.0;
     J.blocks = J.rescans = J.joins = J.jump_rounds = 0;
     J.kept_stuck = false;
     RC_TRY(use_device(db));
@@ -294,7 +295,7 @@ static int delta_pass(JoinCall &c, uint32_t first_row, uint32_t scan_div, JoinCo
 static void join_finish(JoinCall &c) {
     smafa_db *db = c.db;
     const auto &J = db->join;
-    db->call_ms += (float)(J.rec_ms + J.filter_ms + J.count_ms + J.link_ms + J.flatten_ms);
+    db->call_ms += (float)(J.rec_ms + J.filter_ms + J.count_ms + J.link_ms + J.flatten_ms + J.select_ms);
     db->call_timed = true;  // (scan_range cleared it)
     if (!c.no_scans) note_call_kernel(db, c.delta ? "smafa_dl::gather_records_kernel" : "smafa_join::store_records_kernel");
     if (c.inverted) note_call_kernel(db, "smafa_join::inverse_order_kernel");
@@ -955,17 +956,20 @@ static int join_forest(smafa_db *db, uint32_t max_div, smafa_hit *d_edges, unsig
 // one per weight class, or the store joined once more per class at bound t with the raw piece lists spanned at only_dist = t (every
 // pair of weight t is within t).  max_div >= L and n >= min_pts: a row still sparse behind class L - 1 has core exactly L, and
 // star_roots_kernel hangs every surviving root under row 0 at weight L.  One path for every min_pts >= 1.
-static int join_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *d_edges, unsigned long long *d_level_ends,
-                             uint32_t *d_cores) {
+// The call is reach_passes between join_begin and join_finish, and reach_notes: join_stable runs the same passes in front of its own.
+struct ReachRun {
+    uint32_t scan_div = 0;
+    bool all_near = false, tallied = false, spanned = false;
+    unsigned long long kept_total = 0, dense = 0;
+};
+
+// n >= 2, behind join_begin
+static int reach_passes(JoinCall &c, uint32_t max_div, uint32_t min_pts, smafa_hit *d_edges, unsigned long long *d_level_ends,
+                        uint32_t *d_cores, ReachRun &run) {
+    smafa_db *db = c.db;
     auto &J = db->join;
     const uint32_t n_levels = max_div + 1u, E = std::min(n_levels, std::max<uint32_t>(db->L, 1u)), scan_div = E - 1u;
     const bool all_near = max_div >= db->L && db->n >= min_pts;
-    JoinCall c{db};
-    RC_TRY(join_begin(c, d_level_ends, n_levels, 2));
-    if (c.nothing) {  // no row, or one: no edge, every level ends at 0; the one row is core at 0 where it alone is enough
-        if (d_cores && db->n) HIP_TRY(hipMemsetAsync(d_cores, min_pts <= 1u ? 0 : 0xff, db->n * sizeof(uint32_t), db->stream));
-        return SMAFA_OK;
-    }
     const uint32_t n = (uint32_t)db->n;
     const unsigned long long room = n - 1u;
     RC_TRY(J.parent.ensure((size_t)n * 2u * sizeof(uint32_t)));
@@ -1029,15 +1033,120 @@ static int join_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, s
         }));
         RC_TRY(timed_sync(c));
     }
-    join_finish(c);
+    run = {scan_div, all_near, tally.used, span.used, kept_total, totals[1]};
+    return SMAFA_OK;
+}
+
+// behind join_finish: the kernels of the reach forest's passes, in launch order
+static void reach_notes(const smafa_db *db, const ReachRun &run) {
     note_call_kernel(db, "smafa_sf::init_forest_kernel");
-    if (tally.used) note_call_kernel(db, "smafa_mr::tally_keep_kernel");
+    if (run.tallied) note_call_kernel(db, "smafa_mr::tally_keep_kernel");
     note_call_kernel(db, "smafa_mr::core_dist_kernel");
-    if (span.used) note_call_kernel(db, "smafa_mr::span_reach_kernel");
-    if (all_near) note_call_kernel(db, "smafa_sf::star_roots_kernel");
+    if (run.spanned) note_call_kernel(db, "smafa_mr::span_reach_kernel");
+    if (run.all_near) note_call_kernel(db, "smafa_sf::star_roots_kernel");
+}
+
+static int join_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts, smafa_hit *d_edges, unsigned long long *d_level_ends,
+                             uint32_t *d_cores) {
+    auto &J = db->join;
+    JoinCall c{db};
+    RC_TRY(join_begin(c, d_level_ends, (size_t)max_div + 1u, 2));
+    if (c.nothing) {  // no row, or one: no edge, every level ends at 0; the one row is core at 0 where it alone is enough
+        if (d_cores && db->n) HIP_TRY(hipMemsetAsync(d_cores, min_pts <= 1u ? 0 : 0xff, db->n * sizeof(uint32_t), db->stream));
+        return SMAFA_OK;
+    }
+    ReachRun run;
+    RC_TRY(reach_passes(c, max_div, min_pts, d_edges, d_level_ends, d_cores, run));
+    join_finish(c);
+    reach_notes(db, run);
     log_line(2, "reach forest of %u rows up to bound %u at min_pts %u, joined at bound %u: %u scans (%u of them repeats) in %u join%s, "
              "records %.3f ms, scans %.3f ms, tally %.3f ms, cores %.3f ms, span %.3f ms, star %.3f ms, %llu pairs kept, %llu rows not sparse",
-             n, max_div, min_pts, scan_div, J.blocks + J.rescans, J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms,
-             J.filter_ms, J.link_ms, J.flatten_ms, kept_total, totals[1]);
+             (uint32_t)db->n, max_div, min_pts, run.scan_div, J.blocks + J.rescans, J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms,
+             J.scan_ms, J.count_ms, J.filter_ms, J.link_ms, J.flatten_ms, run.kept_total, run.dense);
+    return SMAFA_OK;
+}
+
+// smafa_db_self_stable_launch (stable.hip.h): the reach forest's passes into the handle's own buffers, then HDBSCAN's selection over
+// its edges and cores, plane by plane.  J.stable holds, in this order: the forest's level ends (max_div + 1 counters) and the
+// chosen total; two halves {run[], sum[] (8 B per subject each), size[] (4 B)} for the plane in hand and the one below; kids[];
+// the root planes and the flag planes (4 B per subject and plane each); the forest's edges (n - 1 rows).  The planes are
+// min(max_div, L) + 1: the scanned classes and, where max_div >= L, the class L that star_roots_kernel fills, which counts
+// max_div - L + 1 times in a stability — nothing is allocated or launched per level above L.  parent[] is made fresh once and the
+// classes are united one after another, four launches a plane (three for plane 0: nothing lies below it), then excess_kernel, one
+// choose_kernel per plane from the last one down and assign_kernel: 5 x planes + 2 launches whatever the store holds, no host
+// loop over rows, edges or clusters, and one wait at the end, for the chosen total — the only value of this stage that crosses to the host.
+// min_pts >= 1, min_size >= 1; d_joined, d_cores: n entries each, or nullptr; n_clusters: the caller's, on the host
+static int join_stable(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t min_size, uint32_t *d_labels, uint32_t *d_joined,
+                       uint32_t *d_cores, uint64_t *n_clusters) {
+    auto &J = db->join;
+    const uint32_t n = (uint32_t)db->n, L = std::max<uint32_t>(db->L, 1u), planes = std::min(max_div, L) + 1u;
+    const unsigned long long mult = max_div >= L ? (unsigned long long)(max_div - L) + 1ull : 1ull;  // of the last plane
+    const size_t n_levels = (size_t)max_div + 1u, room = n ? n - 1u : 0u;
+    const size_t half = (size_t)n * 16u + ((size_t)n * 4u + 7u) / 8u * 8u, plane = (size_t)n * sizeof(uint32_t);
+    RC_TRY(use_device(db));
+    RC_TRY(J.stable.ensure((n_levels + 1u) * 8u + 2u * half + plane + 2u * planes * plane + room * sizeof(smafa_hit)));
+    unsigned long long *const level_ends = J.stable.as<unsigned long long>(), *const chosen = level_ends + n_levels;
+    char *const halves = reinterpret_cast<char *>(chosen + 1);
+    uint32_t *const kids = reinterpret_cast<uint32_t *>(halves + 2u * half), *const root = kids + n, *const flag = root + (size_t)planes * n;
+    smafa_hit *const edges = reinterpret_cast<smafa_hit *>(flag + (size_t)planes * n);
+    const auto run_of = [&](uint32_t t) { return reinterpret_cast<unsigned long long *>(halves + (t & 1u) * half); };
+    const auto size_of = [&](uint32_t t) { return reinterpret_cast<uint32_t *>(run_of(t) + 2u * (size_t)n); };
+    JoinCall c{db};
+    RC_TRY(join_begin(c, level_ends, n_levels, 2));
+    if (c.nothing) {  // no row: nothing; one row: a cluster of its own where it alone is enough, noise elsewhere; cores as the reach forest's
+        const bool one = n == 1u && min_pts <= 1u && min_size <= 1u;
+        if (n) HIP_TRY(hipMemsetAsync(d_labels, one ? 0 : 0xff, sizeof(uint32_t), db->stream));
+        if (n && d_joined) HIP_TRY(hipMemsetAsync(d_joined, one ? 0 : 0xff, sizeof(uint32_t), db->stream));
+        if (n && d_cores) HIP_TRY(hipMemsetAsync(d_cores, min_pts <= 1u ? 0 : 0xff, sizeof(uint32_t), db->stream));
+        *n_clusters = one ? 1u : 0u;
+        return SMAFA_OK;
+    }
+    ReachRun run;
+    RC_TRY(reach_passes(c, max_div, min_pts, edges, level_ends, d_cores, run));
+    // (as reach_passes left them: the union-find, to be made fresh; core[] behind it; the running edge total, final)
+    uint32_t *const parent = J.parent.as<uint32_t>(), *const core = parent + n;
+    const unsigned long long *const n_edges = J.ctl.as<unsigned long long>() + 2;
+    const dim3 rows = row_grid(n), block(256);
+    RC_TRY(timed_begin(c, &J.select_ms, "stable: the forest's classes united, counted and chosen from"));
+    HIP_TRY(hipMemsetAsync(chosen, 0, sizeof(unsigned long long), db->stream));
+    hipLaunchKernelGGL(smafa_sf::init_forest_kernel, rows, block, 0, db->stream, parent, n);
+    for (uint32_t t = 0; t < planes; t++) {
+        unsigned long long *const run_t = run_of(t), *const sum_t = run_t + n, *const run_b = run_of(t + 1u), *const sum_b = run_b + n;
+        uint32_t *const size_t_ = size_of(t), *const size_b = size_of(t + 1u), *const root_t = root + (size_t)t * n;
+        uint32_t *const flag_t = flag + (size_t)t * n;
+        HIP_TRY(hipMemsetAsync(sum_t, 0, half - (size_t)n * 8u, db->stream));  // sum[] and size[] of this half
+        hipLaunchKernelGGL(smafa_st::unite_class_kernel, rows, block, 0, db->stream, edges, n_edges, (unsigned long long)room, n, t, parent);
+        hipLaunchKernelGGL(smafa_st::snapshot_kernel, rows, block, 0, db->stream, parent, core, n, t, root_t, size_t_, kids);
+        if (t) hipLaunchKernelGGL(smafa_st::census_kernel, rows, block, 0, db->stream, size_b, root_t, n, min_size, kids);
+        hipLaunchKernelGGL(smafa_st::adopt_kernel, rows, block, 0, db->stream, root_t, size_t_, size_b, kids, n, min_size,
+                           t + 1u == planes ? mult : 1ull, t ? 1u : 0u, run_b, sum_b, run_t, sum_t, t ? flag_t - n : flag_t, flag_t);
+    }
+    hipLaunchKernelGGL(smafa_st::excess_kernel, rows, block, 0, db->stream, run_of(planes - 1u), run_of(planes - 1u) + n, n,
+                       flag + (size_t)(planes - 1u) * n);
+    for (uint32_t t = planes; t-- > 0;) {
+        const bool last = t + 1u == planes;
+        hipLaunchKernelGGL(smafa_st::choose_kernel, rows, block, 0, db->stream, last ? (const uint32_t *)nullptr : root + (size_t)(t + 1u) * n,
+                           last ? (const uint32_t *)nullptr : flag + (size_t)(t + 1u) * n, n, flag + (size_t)t * n, chosen);
+    }
+    hipLaunchKernelGGL(smafa_st::assign_kernel, rows, block, 0, db->stream, root, flag, core, n, planes, d_labels, d_joined);
+    RC_TRY(timed_end(c, 5u * planes + 2u));
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, chosen, sizeof total, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    *n_clusters = total;
+    join_finish(c);
+    reach_notes(db, run);
+    note_call_kernel(db, "smafa_st::unite_class_kernel");
+    note_call_kernel(db, "smafa_st::snapshot_kernel");
+    if (planes > 1u) note_call_kernel(db, "smafa_st::census_kernel");
+    note_call_kernel(db, "smafa_st::adopt_kernel");
+    note_call_kernel(db, "smafa_st::excess_kernel");
+    note_call_kernel(db, "smafa_st::choose_kernel");
+    note_call_kernel(db, "smafa_st::assign_kernel");
+    log_line(2, "stable clusters of %u rows up to bound %u at min_pts %u, min_cluster_size %u, joined at bound %u: %u scans (%u of them "
+             "repeats) in %u join%s, records %.3f ms, scans %.3f ms, tally %.3f ms, cores %.3f ms, span %.3f ms, star %.3f ms, select %.3f ms "
+             "over %u planes, %llu pairs kept, %llu rows not sparse, %llu clusters", n, max_div, min_pts, min_size, run.scan_div,
+             J.blocks + J.rescans, J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.filter_ms, J.link_ms,
+             J.flatten_ms, J.select_ms, planes, run.kept_total, run.dense, total);
     return SMAFA_OK;
 }

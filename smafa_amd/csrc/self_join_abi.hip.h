@@ -1,7 +1,7 @@
-// self_join_abi.hip.h — the C ABI of the self-join: the twenty smafa_db_self_* entry points, ten calls in two forms each.  The
+// self_join_abi.hip.h — the C ABI of the self-join: the twenty-two smafa_db_self_* entry points, eleven calls in two forms each.  The
 // *_launch form checks its arguments and hands the caller's device pointers to the call of self_join.hip.h.  The host form checks
 // the same, then runs the same call on the handle's own buffers and copies the results out: pairs_to_host for the two pair
-// lists, HostForm for the eight calls that return arrays and counters.
+// lists, HostForm for the nine calls that return arrays and counters.
 // A new call: its two entry points here, built from self_args / HostForm / trim; what it checks beyond self_args, and where it zeroes
 // its outputs among its checks, is its own (the order is part of the contract: tests hold what a failing check leaves untouched).
 // Included once by engine.hip, inside extern "C", behind self_join.hip.h.
@@ -12,7 +12,7 @@ static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counters and offs
 // ---- argument checks: `who` is the entry point, the name is the argument's
 static int missing(const char *who, const char *name) { return set_error(SMAFA_ERR_INVALID, "%s: NULL %s", who, name); }
 
-// what eighteen of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
+// what twenty of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
 static int self_args(const char *who, const smafa_db *db, bool has_a, const char *a, bool has_b, const char *b, uint32_t max_div,
                      const char *needs) {
     if (!db) return missing(who, "handle");
@@ -307,6 +307,44 @@ int smafa_db_self_reach_forest(smafa_db *db, uint32_t max_div, uint32_t min_pts,
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_reach_forest");
+}
+
+// ---- stable clusters
+// min_cluster_size 0: min_pts, as min_pts 0 is 1
+static uint32_t stable_min_size(uint32_t min_pts, uint32_t min_cluster_size) { return min_cluster_size ? min_cluster_size : std::max<uint32_t>(min_pts, 1u); }
+
+int smafa_db_self_stable_launch(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t min_cluster_size, void *d_labels, void *d_joined,
+                                void *d_cores, uint64_t *n_clusters) try {
+    RC_TRY(self_args("smafa_db_self_stable_launch", db, d_labels, "labels", n_clusters, "n_clusters", max_div, "stable clusters need a bound"));
+    return join_stable(db, max_div, std::max<uint32_t>(min_pts, 1u), stable_min_size(min_pts, min_cluster_size), (uint32_t *)d_labels,
+                       (uint32_t *)d_joined, (uint32_t *)d_cores, n_clusters);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_stable_launch");
+}
+
+int smafa_db_self_stable(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_t min_cluster_size, uint32_t *labels, uint32_t *joined,
+                         uint32_t *cores, uint64_t cap, uint64_t *n_clusters) try {
+    RC_TRY(self_args("smafa_db_self_stable", db, labels, "labels", n_clusters, "n_clusters", max_div, "stable clusters need a bound"));
+    RC_TRY(labels_cap_arg("smafa_db_self_stable", db, cap));  // (nothing is written, the count included)
+    *n_clusters = 0;
+    const HostForm h{db};
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // the labels, and the joined levels and the cores behind them, on their way to the caller: 4 B x 3 per subject
+    RC_TRY(h.stage(std::max<uint64_t>(n, 1) * 3u * sizeof(uint32_t), 1));
+    uint32_t *const d_labels = J.out.as<uint32_t>();
+    uint64_t count = 0;
+    RC_TRY(join_stable(db, max_div, std::max<uint32_t>(min_pts, 1u), stable_min_size(min_pts, min_cluster_size), d_labels,
+                       joined ? d_labels + n : nullptr, cores ? d_labels + 2 * n : nullptr, &count));
+    RC_TRY(h.fetch(labels, d_labels, n * sizeof(uint32_t)));
+    RC_TRY(h.fetch(joined, d_labels + n, n * sizeof(uint32_t)));
+    RC_TRY(h.fetch(cores, d_labels + 2 * n, n * sizeof(uint32_t)));
+    RC_TRY(h.wait());
+    *n_clusters = count;
+    trim({&db->hits, &J.kept, &J.hist, &J.stable});
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_stable");
 }
 
 // ---- density
