@@ -666,6 +666,52 @@ int smafa_db_self_hits_since(smafa_db *db, uint64_t first_row, uint32_t max_div,
 int smafa_db_self_components_update_launch(smafa_db *db, uint64_t first_row, uint32_t max_div, void *d_labels, void *d_n_components);
 int smafa_db_self_components_update(smafa_db *db, uint64_t first_row, uint32_t max_div, uint32_t *labels, uint64_t cap, uint64_t *n_components);
 
+/* ------------------------------------------------- consensus: one sequence per labelled cluster, and the member nearest to it */
+/*
+ * What each cluster of a label call looks like.  `labels` holds one uint32 per subject, as smafa_db_self_components,
+ * _density, _peaks, _stable and the others write them: SMAFA_NONE (the row belongs to no cluster and is left out) or a value
+ * below n_subjects.  A value need not be a member's own number.  The call is an exact integer function of the store and the
+ * labels and gives the same bytes from run to run.
+ *
+ * Let r_0 < r_1 < ... < r_{K-1} be the distinct values other than SMAFA_NONE.
+ *   ids[k]    = r_k.
+ *   sizes[k]  = the number of rows with that label.
+ *   codes[k * seq_len + c], for source column c in 0 .. seq_len - 1: the code that the most members of cluster k hold at
+ *               column c; a tie goes to the smallest code.  Codes are those of smafa_encode, columns are in the caller's
+ *               order, not the store's.  The nucleotide N class (code 4) is a code like any other: it wins a column only with
+ *               a strict plurality over every smaller code.
+ *   div[i]    (optional, n_subjects uint32) = the scan's distance between row i and codes[k(i)]: the number of columns where
+ *               they differ.  SMAFA_NONE for unlabelled rows.
+ *   nearest[k] (optional) = the member of cluster k with the smallest (div, subject number).
+ *   *n_clusters (host uint64 in both forms) = K.
+ *
+ * Checks, in this order, each SMAFA_ERR_INVALID with the argument named in smafa_last_error() and nothing written: a NULL
+ * handle; NULL labels; NULL n_clusters; NULL ids, sizes or codes while cap_clusters > 0.  Then, from the device: a label that is
+ * neither SMAFA_NONE nor below n_subjects gives SMAFA_ERR_INVALID — the text names `labels` and the smallest offending subject
+ * number, found with an atomic minimum, so it is the same every run — and nothing is written.  cap_clusters < K gives
+ * SMAFA_ERR_CAPACITY with *n_clusters = K and no output array touched: cap_clusters = 0 with NULL arrays is the way to ask for K.
+ * An empty store gives *n_clusters = 0 and writes nothing else; all labels SMAFA_NONE gives K = 0 and div all SMAFA_NONE.
+ *
+ * On the device (consensus.hip.h): the values that occur are marked and numbered by an exclusive sum; the store's positions are
+ * sorted by their group's number with one stable radix sort over the bits of K; one wave64 per SMAFA_CONSENSUS_CHUNK sorted
+ * entries (read when the handle is made; default 4096, at least 64) reads each plane word of its members once, lanes as
+ * columns, counts codes in LDS and votes; a group that crosses such a window adds its counters to one table per window edge,
+ * voted by a second small kernel; a last pass measures every row against its group's consensus in bit-plane form and takes the
+ * nearest by atomic minimum.  Handle-owned scratch: 16 B per position for the sort, 8 B per subject, 12 + 4 x planes x words B
+ * per cluster, 4 KB x words per window — never clusters x columns x alphabet counters.  No other call's state (the inverse order,
+ * the kept list, the index) is touched.
+ *
+ * smafa_db_consensus_launch: device-resident form.  d_labels = n_subjects uint32; d_ids, d_sizes, d_nearest (or NULL) =
+ * cap_clusters uint32; d_codes = cap_clusters x seq_len bytes; d_div (or NULL) = n_subjects uint32.  The call waits for its own
+ * work, as smafa_db_self_stable_launch does: *n_clusters and the buffers are valid on return.
+ * smafa_db_consensus: host form.
+ * smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of the call; smafa_last_call_kernels lists
+ * consensus::mark_groups_kernel, group_ids_kernel, group_keys_kernel, segment_bounds_kernel, tally_vote_kernel<planes>,
+ * vote_tables_kernel<planes> (more than one window), measure_kernel (an optional output asked for) and finish_groups_kernel.
+ */
+int smafa_db_consensus_launch(smafa_db *db, const void *d_labels, void *d_ids, void *d_sizes, void *d_codes, void *d_nearest /* may be NULL */, void *d_div /* may be NULL */, uint64_t cap_clusters, uint64_t *n_clusters /* host */);
+int smafa_db_consensus(smafa_db *db, const uint32_t *labels, uint32_t *ids, uint32_t *sizes, uint8_t *codes, uint32_t *nearest, uint32_t *div, uint64_t cap_clusters, uint64_t *n_clusters);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -827,6 +873,13 @@ int smafa_reach_forest(const char *db_path, uint32_t max_divergence, uint32_t mi
  * max_divergence, min_pts and min_cluster_size), "{i}\t{label}\n" in subject order, -1 for noise; with joined != 0
  * (`--joined`) a third column, the level at which the subject joined its cluster, -1 for noise.  An empty DB prints nothing. */
 int smafa_stable(const char *db_path, uint32_t max_divergence, uint32_t min_pts, uint32_t min_cluster_size, int joined, int out_fd, int device);
+/* `smafa consensus` (not in the reference): the same DB and a labels file — "{i}\t{label}[\t...]\n" per subject exactly as
+ * `components`, `density`, `peaks` and `stable` print them, further columns ignored, -1 for SMAFA_NONE; labels_path "-" is
+ * stdin.  Line j must carry i = j and there must be n_subjects lines: anything else — a label that is neither
+ * -1 nor below n_subjects included — is SMAFA_ERR_INVALID with a text that names the line (exit status 1).  Per cluster, in ascending label order (smafa_db_consensus),
+ * "{label}\t{size}\t{nearest}\t{max_div}\t{SEQUENCE}\n": max_div the greatest div among the cluster's members, SEQUENCE
+ * smafa_decode of the consensus.  An empty DB prints nothing. */
+int smafa_consensus(const char *db_path, const char *labels_path, int out_fd, int device);
 /* `smafa density` (not in the reference): the same DB, and per subject its density-cluster label and its degree
  * (smafa_db_self_density at max_divergence and min_pts), "{i}\t{label}\t{degree}\n" in subject order; the label of a noise row
  * is printed as -1.  An empty DB prints nothing. */

@@ -43,6 +43,7 @@ EXPORTS = [
     "smafa_db_self_forest_launch", "smafa_db_self_forest", "smafa_forest",
     "smafa_db_self_reach_forest_launch", "smafa_db_self_reach_forest", "smafa_reach_forest",
     "smafa_db_self_stable_launch", "smafa_db_self_stable", "smafa_stable",
+    "smafa_db_consensus_launch", "smafa_db_consensus", "smafa_consensus",
     "smafa_makedb", "smafa_makedb_packed", "smafa_query", "smafa_query_multi", "smafa_cluster", "smafa_cluster_multi", "smafa_cluster_sharded", "smafa_count",
 ]
 
@@ -200,6 +201,9 @@ def lib() -> C.CDLL:
     l.smafa_db_self_stable_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, u64p]
     l.smafa_db_self_stable.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
     l.smafa_stable.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]
+    l.smafa_db_consensus_launch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
+    l.smafa_db_consensus.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
+    l.smafa_consensus.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]
     l.smafa_count.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_int]
     _lib = l
     return l

@@ -458,6 +458,51 @@ class SubjectStore:
                                                 C.c_void_p(d_cores) if d_cores else None, C.byref(count)))
         return int(count.value)
 
+    # ---- consensus ----------------------------------------------------------------------------
+    def cluster_consensus(self, labels, nearest: bool = True, div: bool = True):
+        """(ids, sizes, codes[K, L] uint8, nearest, div) — smafa_db_consensus: what each cluster of `labels` looks like.  labels
+        (uint32, n_subjects) is what self_components, self_density, self_peaks, self_stable_clusters and the others return: NONE
+        or a value below n_subjects per row.  ids (uint32, K) are the distinct labels in ascending order, sizes their member
+        counts, codes[k, c] the code most members of cluster k hold at column c (a tie to the smallest code), div[i] the number
+        of columns where row i differs from its cluster's consensus (NONE for an unlabelled row), nearest[k] the member with the
+        smallest (div, number).  nearest / div not wanted: None in their place.  Asks for K first, then allocates."""
+        n, L = self.info().n_subjects, self.info().seq_len
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        if labels.shape != (n,):
+            raise ValueError(f"labels has shape {labels.shape}, the store has {n} subjects")
+        # (an empty store: a pointer all the same, the call takes no NULL labels)
+        p_labels = labels.ctypes.data if n else C.cast(C.pointer(C.c_uint32(0)), C.c_void_p)
+        count = C.c_uint64(0)
+        rc = lib().smafa_db_consensus(self._h, p_labels, None, None, None, None, None, 0, C.byref(count))
+        if rc != _lib.ERR_CAPACITY:
+            check(rc)
+        K = int(count.value)
+        ids, sizes = np.zeros(K, dtype=np.uint32), np.zeros(K, dtype=np.uint32)
+        codes = np.zeros((K, L), dtype=np.uint8)
+        near = np.zeros(K, dtype=np.uint32) if nearest else None
+        dist = np.full(n, NONE, dtype=np.uint32) if div else None
+        if K:  # (K = 0: every row is unlabelled, div is NONE throughout)
+            check(lib().smafa_db_consensus(self._h, p_labels, ids.ctypes.data, sizes.ctypes.data, codes.ctypes.data,
+                                           near.ctypes.data if nearest else None, dist.ctypes.data if div else None, K, C.byref(count)))
+        return ids, sizes, codes, near, dist
+
+    def cluster_consensus_launch(self, d_labels: int, d_ids: int, d_sizes: int, d_codes: int, d_nearest: int = 0, d_div: int = 0,
+                                 cap_clusters: int = 0) -> int:
+        """device-resident form (smafa_db_consensus_launch): n_subjects uint32 labels in d_labels; cap_clusters uint32 each in
+        d_ids, d_sizes and (0: not wanted) d_nearest, cap_clusters x seq_len bytes in d_codes, n_subjects uint32 in d_div (0:
+        not wanted); -> K.  SmafaError with code ERR_CAPACITY where cap_clusters < K (its .count holds K): nothing is written.
+        The call has waited for its work when it returns."""
+        count = C.c_uint64(0)
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        rc = lib().smafa_db_consensus_launch(self._h, ptr(d_labels), ptr(d_ids), ptr(d_sizes), ptr(d_codes), ptr(d_nearest), ptr(d_div),
+                                             int(cap_clusters), C.byref(count))
+        if rc == _lib.ERR_CAPACITY:
+            e = _lib.SmafaError(rc, lib().smafa_last_error().decode(errors="replace"))
+            e.count = int(count.value)
+            raise e
+        check(rc)
+        return int(count.value)
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -779,6 +824,12 @@ def stable_clusters(db_path: str, max_divergence: int, min_pts: int, min_cluster
     """`smafa stable`: "i\\tlabel" per subject of the DB file (smafa_db_self_stable), -1 for noise, to out_fd — with joined a third
     column, the level at which the subject joined its cluster."""
     check(lib().smafa_stable(os.fsencode(db_path), _opt(max_divergence), int(min_pts), int(min_cluster_size), 1 if joined else 0, out_fd, device))
+
+
+def consensus(db_path: str, labels_path: str, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa consensus`: "label\\tsize\\tnearest\\tmax_div\\tSEQUENCE" per cluster of the labels file ("i\\tlabel" per subject of the
+    DB file, as the label verbs print it; "-": stdin) in ascending label order (smafa_db_consensus), to out_fd."""
+    check(lib().smafa_consensus(os.fsencode(db_path), os.fsencode(labels_path), out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

@@ -30,6 +30,7 @@
 #include "forest.hip.h"
 #include "reach.hip.h"
 #include "stable.hip.h"
+#include "consensus.hip.h"
 
 namespace smafa {
 
@@ -250,12 +251,18 @@ struct smafa_db {
         // and the chosen total (stable_layout, self_join.hip.h); select_ms: everything behind the reach forest's last pass
         DevBuf stable;
         double select_ms = 0;
+        // consensus (consensus.hip.h): `cons`, live for one call: the bad-row word, mark[] and dense[] (4 B x 2 per subject),
+        // seg_begin[] and the slots (12 B per group), the records (4 x P x W B per group) and one table of 32 x 32W counters per
+        // window of consensus_chunk sorted entries; the sort's double buffers are keys_a / keys_b / idx_a / idx_b (16 B per position).
+        // count_ms (groups), filter_ms (keys, sort and bounds), link_ms (tally and vote), flatten_ms (measure and finish)
+        DevBuf cons;
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
     uint64_t join_scratch_max = 1ull << 27;  // rows the block's scratch list may grow to (1.5 GB) before the block is halved (SMAFA_JOIN_SCRATCH_MAX)
     uint64_t density_keep_max = 1ull << 27;  // rows the kept pair list (density and peaks calls) may grow to; 0: never kept, the store is joined
                                              // twice (SMAFA_DENSITY_KEEP_MAX; default: the value of join_scratch_max)
+    uint64_t consensus_chunk = 4096;  // sorted entries per wave of consensus::tally_vote_kernel (SMAFA_CONSENSUS_CHUNK)
     bool neighbour_two_sorts = false;  // neighbours: the two-sort order also where one key would hold an entry (SMAFA_NEIGHBOUR_SORT=2, tests)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
@@ -1068,6 +1075,8 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *jv = getenv("SMAFA_JOIN_BLOCK")) db->join_block = std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64);
     if (const char *jv = getenv("SMAFA_JOIN_STRIDE")) db->join_stride = std::min<uint64_t>(4096, std::max<uint64_t>(1, strtoull(jv, nullptr, 10)));
     if (const char *jv = getenv("SMAFA_JOIN_SCRATCH_MAX")) db->join_scratch_max = std::max<uint64_t>(4096, strtoull(jv, nullptr, 10));
+    if (const char *jv = getenv("SMAFA_CONSENSUS_CHUNK"))
+        db->consensus_chunk = std::min<uint64_t>(1u << 20, std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64));
     if (const char *jv = getenv("SMAFA_NEIGHBOUR_SORT")) db->neighbour_two_sorts = atoi(jv) == 2;
     db->density_keep_max = db->join_scratch_max;
     if (const char *jv = getenv("SMAFA_DENSITY_KEEP_MAX")) {  // any number of rows, 0 included (two joins); not a number: ignored, aloud
@@ -1207,7 +1216,7 @@ void smafa_db_destroy(smafa_db *db) {
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
-                      &db->join.kept, &db->join.hist, &db->join.stable, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
+                      &db->join.kept, &db->join.hist, &db->join.stable, &db->join.cons, &db->join.ctl, &db->join.entries, &db->join_q.qrec, &db->join_q.thr, &db->join_q.cnt})
         b->release();
     for (hipEvent_t e : db->join.ev)
         if (e) (void)hipEventDestroy(e);

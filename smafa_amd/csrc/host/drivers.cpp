@@ -7,6 +7,7 @@
 // (src/lib.rs:292,310), `cluster` prints "{raw record}\t{centroid string}\n" (src/cluster.rs:79-84).
 // Inputs the reference panics on fail with SMAFA_ERR_PANIC and the same message, after the rows the
 // reference would already have printed.
+#include <fcntl.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -845,6 +846,107 @@ int smafa_stable(const char *db_path, uint32_t max_divergence, uint32_t min_pts,
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_stable");
+}
+
+// ------------------------------------------------------------------------------------ consensus
+// A labels file as the label verbs print it: line j is "{j}\t{label}" and whatever columns follow, label -1 for SMAFA_NONE.  `text`
+// is the whole file; -> labels[n], or SMAFA_ERR_INVALID naming the first line that is not what it should be.
+static int parse_labels(const std::string &text, size_t n, std::vector<uint32_t> &labels) {
+    labels.assign(n, SMAFA_NONE);
+    size_t at = 0, line = 0;
+    const auto bad = [&](const char *what) {
+        return set_error(SMAFA_ERR_INVALID, "smafa_consensus: labels line %llu: %s", (unsigned long long)line + 1, what);
+    };
+    // an unsigned decimal number of at most ten digits at text[at ..), -> false where there is none
+    const auto number = [&](uint64_t *out) {
+        size_t digits = 0;
+        uint64_t v = 0;
+        while (at < text.size() && text[at] >= '0' && text[at] <= '9' && digits < 11) v = v * 10 + (uint64_t)(text[at++] - '0'), digits++;
+        *out = v;
+        return digits > 0 && digits < 11;
+    };
+    for (; at < text.size(); line++) {
+        if (line >= n) return bad("more lines than the database has sequences");
+        uint64_t i = 0, label = SMAFA_NONE;
+        if (!number(&i)) return bad("no sequence number");
+        if (i != line) return bad("the sequence number is not the line's own (line j carries sequence j)");
+        if (at >= text.size() || text[at] != '\t') return bad("no tab behind the sequence number");
+        at++;
+        if (text.compare(at, 2, "-1") == 0) at += 2;
+        else if (!number(&label)) return bad("no label");
+        else if (label >= n) return bad("the label is neither -1 nor the number of a sequence of the database");
+        if (at < text.size() && text[at] != '\t' && text[at] != '\n' && text[at] != '\r') return bad("the label is not a number");
+        labels[line] = (uint32_t)label;
+        while (at < text.size() && text[at] != '\n') at++;  // further columns
+        if (at < text.size()) at++;
+    }
+    if (line < n) return bad("the file ends here, the database has more sequences");
+    return SMAFA_OK;
+}
+
+static int read_whole(const char *path, std::string &text) {
+    const bool std_in = !strcmp(path, "-");
+    const int fd = std_in ? 0 : open(path, O_RDONLY);
+    if (fd < 0) return set_error(SMAFA_ERR_IO, "smafa_consensus: cannot open labels file \"%s\": %s", path, strerror(errno));
+    char buf[1 << 16];
+    ssize_t got = 0;
+    while ((got = read(fd, buf, sizeof buf)) > 0 || (got < 0 && errno == EINTR))
+        if (got > 0) text.append(buf, (size_t)got);
+    const int err = errno;
+    if (!std_in) close(fd);
+    return got < 0 ? set_error(SMAFA_ERR_IO, "smafa_consensus: reading labels file \"%s\": %s", path, strerror(err)) : SMAFA_OK;
+}
+
+// The consensus of every labelled cluster of a DB file (smafa_db_consensus), printed
+// "{label}\t{size}\t{nearest}\t{max_div}\t{SEQUENCE}\n" per cluster in ascending label order.
+int smafa_consensus(const char *db_path, const char *labels_path, int out_fd, int device) try {
+    if (!labels_path) return set_error(SMAFA_ERR_INVALID, "smafa_consensus: NULL labels path");
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_consensus", db_path, 0 /* no bound to check */, device, v);
+    if (rc) return rc;
+    std::string text;
+    rc = read_whole(labels_path, text);
+    std::vector<uint32_t> labels;
+    if (!rc) rc = parse_labels(text, v.n, labels);
+    if (rc || v.empty) return rc;
+    std::string().swap(text);
+    smafa_db_info_t info{};
+    rc = smafa_db_info(v.store.db, &info);
+    if (rc) return rc;
+    const size_t L = info.seq_len;
+    uint64_t K = 0;
+    rc = smafa_db_consensus(v.store.db, labels.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0, &K);
+    if (rc && rc != SMAFA_ERR_CAPACITY) return rc;
+    std::vector<uint32_t> ids(K), sizes(K), nearest(K), div(v.n), worst(K, 0);
+    std::vector<uint8_t> codes(K * L);
+    if (K) rc = smafa_db_consensus(v.store.db, labels.data(), ids.data(), sizes.data(), codes.data(), nearest.data(), div.data(), K, &K);
+    if (rc) return rc;
+    // max_div per cluster: ids[] ascends, so a label's cluster is found by bisection
+    for (size_t i = 0; i < v.n; i++) {
+        if (labels[i] == SMAFA_NONE) continue;
+        const size_t k = (size_t)(std::lower_bound(ids.begin(), ids.end(), labels[i]) - ids.begin());
+        worst[k] = std::max(worst[k], div[i]);
+    }
+    std::vector<char> letters(L);
+    int decode_rc = SMAFA_OK;
+    rc = write_rows(out_fd, K, std::max<size_t>(1, kRowsPerWrite / (L / 8 + 1)), [&](std::string &out, size_t k) {
+        append_u32(out, ids[k]);
+        for (uint32_t field : {sizes[k], nearest[k], worst[k]}) {
+            out.push_back('\t');
+            append_u32(out, field);
+        }
+        out.push_back('\t');
+        const int drc = smafa_decode(info.alphabet, codes.data() + k * L, L, letters.data());
+        if (drc) decode_rc = drc;
+        out.append(letters.data(), L);
+        out.push_back('\n');
+    });
+    if (!rc) rc = decode_rc;
+    if (rc) return rc;
+    log_line(1, "%llu consensus sequences of %llu sequences, took %llu seconds", (unsigned long long)K, (unsigned long long)v.n, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_consensus");
 }
 
 // ------------------------------------------------------------------------------------ density

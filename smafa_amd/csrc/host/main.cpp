@@ -14,6 +14,8 @@
 //           under the mutual-reachability distance, the merge tree of the density clusters; --cores: the core distances instead)
 //   stable  -d/--database FILE  --max-divergence INT  --min-pts INT  [--min-cluster-size INT] [--joined]   (this build only: the
 //           stable cluster of every subject, HDBSCAN's selection over the forest under the mutual-reachability distance)
+//   consensus -d/--database FILE  --labels FILE|-   (this build only: per cluster of a labels file, as components, density, peaks
+//           and stable print them, its size, the member nearest to its consensus, the greatest divergence from it, and the consensus)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
@@ -75,6 +77,12 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        clusters of `forest --min-pts` at every weight 0 .. <INT>, each kept at the levels where it persists longest (HDBSCAN's\n"
             "        excess of mass, counted in levels); label = the smallest sequence number of the cluster, -1 for noise; a cluster holds at\n"
             "        least min-cluster-size sequences (default: min-pts); --joined: a third column, the level at which the sequence joined)\n"
+            "consensus -d, --database <FILE>  --labels <FILE|->  [--device <N>]  (not in the reference: one line per cluster of a labels\n"
+            "        file, \"label<TAB>size<TAB>nearest<TAB>max_div<TAB>SEQUENCE\" in ascending label order; the file holds one\n"
+            "        \"i<TAB>label\" line per sequence as `components`, `density`, `peaks` and `stable` print them (further columns are\n"
+            "        ignored, -1: in no cluster, -: stdin); SEQUENCE = per column the letter most members hold, ties to the first of\n"
+            "        A C G T N (amino acids: in code order); nearest = the member with the fewest differences from it, ties to the\n"
+            "        smaller number; max_div = the most differences of any member:  smafa stable ... | smafa consensus -d DB --labels -)\n"
             "density -d, --database <FILE>  --max-divergence <INT>  --min-pts <INT>  [--device <N>]  (not in the reference: density\n"
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
@@ -125,7 +133,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0;
     bool have_min_pts = false, have_since = false;
@@ -170,6 +178,8 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &min_cluster_size)) return usage("--min-cluster-size needs an unsigned integer");
         } else if (a == "--joined" && cmd == "stable") {
             joined = true;
+        } else if (a == "--labels" && cmd == "consensus") {
+            if (!(labels = value())) return usage("--labels needs a file, or - for stdin");
         } else if (a == "--radius" && cmd == "peaks") {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
         } else if (a == "--since" && cmd == "pairs") {
@@ -259,6 +269,10 @@ int main(int argc, char **argv) {
         if (!have_max_div) return usage("stable needs --max-divergence");
         if (!have_min_pts) return usage("stable needs --min-pts");
         rc = smafa_stable(database, max_div, min_pts, min_cluster_size, joined ? 1 : 0, 1, (int)device);
+    } else if (cmd == "consensus") {
+        if (!database) return usage("consensus needs --database");
+        if (!labels) return usage("consensus needs --labels");
+        rc = smafa_consensus(database, labels, 1, (int)device);
     } else if (cmd == "density") {
         if (!database) return usage("density needs --database");
         if (!have_max_div) return usage("density needs --max-divergence");

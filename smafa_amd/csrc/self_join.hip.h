@@ -1150,3 +1150,137 @@ static int join_stable(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32_
              J.flatten_ms, J.select_ms, planes, run.kept_total, run.dense, total);
     return SMAFA_OK;
 }
+
+// ---- consensus (consensus.hip.h).  Not a consumer of the join: the call reads labels the caller holds and the store's own planes.
+// It shares the join's call frame (join_begin / timed passes / join_finish, so that smafa_last_call_* and smafa_last_scan_ms report
+// it) and scans nothing.  Two phases with ONE host read between them: the bad-row word and K gate everything that writes to the
+// caller's arrays.  J.parent holds the bad-row word, mark[] and dense[] (8 B per subject); the sort's double buffers are the handle's
+// keys_a / keys_b / idx_a / idx_b (16 B per position) and the shared sort_tmp; J.cons holds seg_begin[] and the slots (12 B per
+// group), the records (4 x P x W B per group) and one table per window of consensus_chunk sorted entries — never K x L x alphabet
+// counters.  pos_of[], the kept list and the index are not touched.
+// who: the entry point, for the texts; d_nearest, d_div: or nullptr; n_clusters: the caller's, on the host
+static int join_consensus(smafa_db *db, const char *who, const uint32_t *d_labels, uint32_t *d_ids, uint32_t *d_sizes, uint8_t *d_codes,
+                          uint32_t *d_nearest, uint32_t *d_div, uint64_t cap, uint64_t *n_clusters) {
+    auto &J = db->join;
+    const uint64_t n_pos64 = (db->n + kWaveTile - 1) / kWaveTile * kWaveTile;
+    if (n_pos64 >= (1ull << 31))  // (the device radix sort counts its items in an int)
+        return set_error(SMAFA_ERR_INVALID, "%s: the consensus takes stores of fewer than 2^31 positions (this one: %llu)", who,
+                         (unsigned long long)n_pos64);
+    const uint32_t n = (uint32_t)db->n, n_pos = (uint32_t)n_pos64, P = db->P, W = db->W, L = db->L;
+    RC_TRY(use_device(db));
+    RC_TRY(J.parent.ensure(8u + 2u * ((size_t)n + 1u) * sizeof(uint32_t)));
+    uint32_t *const bad = J.parent.as<uint32_t>(), *const mark = bad + 2, *const dense = mark + n + 1u;
+    JoinCall c{db, true};
+    RC_TRY(join_begin(c, J.parent.as<unsigned long long>(), 1, 1));
+    if (c.nothing) {  // an empty store: no cluster, nothing else written
+        *n_clusters = 0;
+        return SMAFA_OK;
+    }
+    const dim3 rows = row_grid(n), block(256);
+    // ---- groups: which values occur, their dense numbers, K — and the smallest row with an illegal label
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, mark, dense, n + 1u, db->stream));
+    RC_TRY(db->sort_tmp.ensure(tmp_bytes));
+    RC_TRY(timed_begin(c, &J.count_ms, "consensus: groups marked and numbered"));
+    HIP_TRY(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), db->stream));
+    HIP_TRY(hipMemsetAsync(mark, 0, ((size_t)n + 1u) * sizeof(uint32_t), db->stream));
+    hipLaunchKernelGGL(consensus::mark_groups_kernel, rows, block, 0, db->stream, d_labels, n, mark, bad);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(db->sort_tmp.p, tmp_bytes, mark, dense, n + 1u, db->stream));
+    RC_TRY(timed_end(c, 2));
+    uint32_t bad_row = SMAFA_NONE, K = 0;
+    HIP_TRY(hipMemcpyAsync(&bad_row, bad, sizeof bad_row, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(hipMemcpyAsync(&K, dense + n, sizeof K, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    join_finish(c);
+    note_call_kernel(db, "consensus::mark_groups_kernel");
+    if (bad_row != SMAFA_NONE) {
+        uint32_t value = 0;
+        HIP_TRY(hipMemcpyAsync(&value, d_labels + bad_row, sizeof value, hipMemcpyDeviceToHost, db->stream));
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        return set_error(SMAFA_ERR_INVALID, "%s: labels[%u] is %u, neither SMAFA_NONE nor the number of one of the store's %u subjects", who,
+                         bad_row, value, n);
+    }
+    *n_clusters = K;
+    if (K > cap)
+        return set_error(SMAFA_ERR_CAPACITY, "%s: cluster arrays too small: %u clusters, capacity %llu", who, K, (unsigned long long)cap);
+    if (K == 0) {  // every row unlabelled
+        if (d_div) HIP_TRY(hipMemsetAsync(d_div, 0xff, (size_t)n * sizeof(uint32_t), db->stream));
+        HIP_TRY(hipStreamSynchronize(db->stream));
+        return SMAFA_OK;
+    }
+    // ---- the rest, enqueued at once and waited for once
+    const uint32_t chunk = (uint32_t)db->consensus_chunk, n_windows = (uint32_t)(((uint64_t)n + chunk - 1u) / chunk);
+    const size_t table_words = (size_t)consensus::kCodes * 32u * W, rec_words = (size_t)P * W;
+    const size_t slots_at = 0, seg_at = slots_at + (size_t)K * 8u, recs_at = (seg_at + ((size_t)K + 1u) * 4u + 7u) / 8u * 8u;
+    const size_t tables_at = recs_at + (size_t)K * rec_words * 4u, tables_bytes = (size_t)n_windows * table_words * 4u;
+    RC_TRY(J.cons.ensure(tables_at + tables_bytes));
+    for (DevBuf *b : {&db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b}) RC_TRY(b->ensure((size_t)n_pos * sizeof(uint32_t)));
+    unsigned long long *const slots = reinterpret_cast<unsigned long long *>(J.cons.as<char>() + slots_at);
+    uint32_t *const seg_begin = reinterpret_cast<uint32_t *>(J.cons.as<char>() + seg_at);
+    uint32_t *const recs = reinterpret_cast<uint32_t *>(J.cons.as<char>() + recs_at);
+    uint32_t *const tables = reinterpret_cast<uint32_t *>(J.cons.as<char>() + tables_at);
+    uint32_t *const ka = db->keys_a.as<uint32_t>(), *const kb = db->keys_b.as<uint32_t>();
+    uint32_t *const ia = db->idx_a.as<uint32_t>(), *const ib = db->idx_b.as<uint32_t>();
+    int key_bits = 1;
+    while (key_bits < 32 && (1ull << key_bits) <= K) key_bits++;  // the keys are 0 .. K
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, ka, kb, ia, ib, (int)n_pos, 0, key_bits, db->stream));
+    RC_TRY(db->sort_tmp.ensure(tmp_bytes));
+    const uint32_t *const perm = db->d_perm.as<uint32_t>();
+    const uint8_t *const tab = db->d_tab.as<uint8_t>();
+    const bool measured = d_nearest || d_div;
+    HIP_TRY(hipEventRecord(J.ev[0], db->stream));
+    hipLaunchKernelGGL(consensus::group_ids_kernel, rows, block, 0, db->stream, mark, dense, n, d_ids);
+    hipLaunchKernelGGL(consensus::group_keys_kernel, row_grid(n_pos), block, 0, db->stream, d_labels, db->d_order, dense, n, n_pos, K, ka, ia);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(db->sort_tmp.p, tmp_bytes, ka, kb, ia, ib, (int)n_pos, 0, key_bits, db->stream));
+    hipLaunchKernelGGL(consensus::segment_bounds_kernel, row_grid(n_pos), block, 0, db->stream, kb, n_pos, K, seg_begin);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(J.ev[1], db->stream));
+    HIP_TRY(hipMemsetAsync(tables, 0, tables_bytes, db->stream));
+    const dim3 tally_grid((n_windows + consensus::kWavesPerBlock - 1u) / consensus::kWavesPerBlock);
+    const auto by_planes = [&](auto planes_c) {
+        constexpr int PS = decltype(planes_c)::value;
+        hipLaunchKernelGGL(consensus::tally_vote_kernel<PS>, tally_grid, block, 0, db->stream, db->d_planes, kb, ib, seg_begin, K, chunk, n_windows,
+                           L, W, perm, tab, tables, recs, d_codes);
+        if (n_windows > 1u)
+            hipLaunchKernelGGL(consensus::vote_tables_kernel<PS>, dim3(n_windows - 1u), dim3(64), 0, db->stream, kb, seg_begin, K, chunk, L, W, perm,
+                               tab, tables, recs, d_codes);
+    };
+    if (P == 5) by_planes(ic<5>{});
+    else if (P == 3) by_planes(ic<3>{});
+    else by_planes(ic<2>{});
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(J.ev[2], db->stream));
+    if (d_div) HIP_TRY(hipMemsetAsync(d_div, 0xff, (size_t)n * sizeof(uint32_t), db->stream));
+    if (d_nearest) HIP_TRY(hipMemsetAsync(slots, 0xff, (size_t)K * 8u, db->stream));
+    if (measured)
+        hipLaunchKernelGGL(consensus::measure_kernel, rows, block, 0, db->stream, db->d_planes, kb, ib, seg_begin, K, P, W, recs, db->d_order, d_div,
+                           d_nearest ? slots : (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(consensus::finish_groups_kernel, row_grid(K), block, 0, db->stream, seg_begin, slots, K, d_sizes, d_nearest);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(J.ev[3], db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    float sort_ms = 0.f, vote_ms = 0.f, measure_ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&sort_ms, J.ev[0], J.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&vote_ms, J.ev[1], J.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&measure_ms, J.ev[2], J.ev[3]));
+    J.filter_ms = sort_ms, J.link_ms = vote_ms, J.flatten_ms = measure_ms;
+    db->call_ms += sort_ms + vote_ms + measure_ms;
+    db->call_launches += 6u + (n_windows > 1u ? 1u : 0u) + (measured ? 1u : 0u);  // (the scan's and the sort's launches count as one each)
+    char name[64];
+    note_call_kernel(db, "consensus::group_ids_kernel");
+    note_call_kernel(db, "consensus::group_keys_kernel");
+    note_call_kernel(db, "consensus::segment_bounds_kernel");
+    snprintf(name, sizeof name, "consensus::tally_vote_kernel<%u>", P);
+    note_call_kernel(db, name);
+    snprintf(name, sizeof name, "consensus::vote_tables_kernel<%u>", P);
+    if (n_windows > 1u) note_call_kernel(db, name);
+    if (measured) note_call_kernel(db, "consensus::measure_kernel");
+    note_call_kernel(db, "consensus::finish_groups_kernel");
+    size_t scratch = J.parent.cap + J.cons.cap + db->sort_tmp.cap;
+    for (const DevBuf *b : {&db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b}) scratch += b->cap;
+    log_line(2, "consensus of %u groups among %u rows, windows of %u: groups %.3f ms, sort %.3f ms, tally and vote %.3f ms, measure %.3f ms, "
+             "scratch %zu B", K, n, chunk, J.count_ms, J.filter_ms, J.link_ms, J.flatten_ms, scratch);
+    trim({&J.cons, &J.parent});
+    trim_together(db->keys_a, {&db->keys_b, &db->idx_a, &db->idx_b, &db->sort_tmp});
+    return SMAFA_OK;
+}

@@ -1,4 +1,5 @@
-// self_join_abi.hip.h — the C ABI of the self-join: the twenty-two smafa_db_self_* entry points, eleven calls in two forms each.  The
+// self_join_abi.hip.h — the C ABI of the self-join: the twenty-two smafa_db_self_* entry points, eleven calls in two forms each — and,
+// last, the two forms of smafa_db_consensus, which takes labels such as theirs and shares their host form.  The
 // *_launch form checks its arguments and hands the caller's device pointers to the call of self_join.hip.h.  The host form checks
 // the same, then runs the same call on the handle's own buffers and copies the results out: pairs_to_host for the two pair
 // lists, HostForm for the nine calls that return arrays and counters.
@@ -457,5 +458,57 @@ int smafa_db_self_neighbours(smafa_db *db, uint32_t max_div, uint32_t max_num_hi
     return rc;  // (SMAFA_ERR_CAPACITY: its text stands, the offsets and *n_out are written, the lists are not)
 } catch (...) {
     return smafa::exception_code("smafa_db_self_neighbours");
+}
+
+// ---- consensus (no bound, no join: the caller's labels and the store's planes)
+// handle, labels, n_clusters, then the three arrays a capacity asks for; nothing is written before they pass
+static int consensus_args(const char *who, const smafa_db *db, const void *labels, const void *n_clusters, const void *ids, const void *sizes,
+                          const void *codes, uint64_t cap) {
+    if (!db) return missing(who, "handle");
+    if (!labels) return missing(who, "labels");
+    if (!n_clusters) return missing(who, "n_clusters");
+    if (cap && !ids) return missing(who, "ids with a capacity");
+    if (cap && !sizes) return missing(who, "sizes with a capacity");
+    if (cap && !codes) return missing(who, "codes with a capacity");
+    return SMAFA_OK;
+}
+
+int smafa_db_consensus_launch(smafa_db *db, const void *d_labels, void *d_ids, void *d_sizes, void *d_codes, void *d_nearest, void *d_div,
+                              uint64_t cap_clusters, uint64_t *n_clusters) try {
+    RC_TRY(consensus_args("smafa_db_consensus_launch", db, d_labels, n_clusters, d_ids, d_sizes, d_codes, cap_clusters));
+    return join_consensus(db, "smafa_db_consensus_launch", (const uint32_t *)d_labels, (uint32_t *)d_ids, (uint32_t *)d_sizes, (uint8_t *)d_codes,
+                          (uint32_t *)d_nearest, (uint32_t *)d_div, cap_clusters, n_clusters);
+} catch (...) {
+    return smafa::exception_code("smafa_db_consensus_launch");
+}
+
+int smafa_db_consensus(smafa_db *db, const uint32_t *labels, uint32_t *ids, uint32_t *sizes, uint8_t *codes, uint32_t *nearest, uint32_t *div,
+                       uint64_t cap_clusters, uint64_t *n_clusters) try {
+    RC_TRY(consensus_args("smafa_db_consensus", db, labels, n_clusters, ids, sizes, codes, cap_clusters));
+    const HostForm h{db};
+    auto &J = db->join;
+    const uint64_t n = db->n, L = db->L, room = std::min<uint64_t>(cap_clusters, n);  // no more clusters than rows
+    // the labels on their way in, and behind them div, ids, sizes, nearest (4 B each) and the codes (L bytes per cluster) on their way out
+    RC_TRY(h.stage(std::max<uint64_t>((2u * n + 3u * room) * sizeof(uint32_t) + room * L, 1), 0));
+    uint32_t *const d_labels = J.out.as<uint32_t>(), *const d_div = d_labels + n, *const d_ids = d_div + n, *const d_sizes = d_ids + room;
+    uint32_t *const d_nearest = d_sizes + room;
+    uint8_t *const d_codes = reinterpret_cast<uint8_t *>(d_nearest + room);
+    if (n) HIP_TRY(hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, db->stream));
+    uint64_t count = 0;
+    const int rc = join_consensus(db, "smafa_db_consensus", d_labels, d_ids, d_sizes, d_codes, nearest ? d_nearest : nullptr, div ? d_div : nullptr,
+                                  cap_clusters, &count);
+    if (rc && rc != SMAFA_ERR_CAPACITY) return rc;  // (nothing is written, the count included)
+    *n_clusters = count;
+    if (rc) return rc;  // SMAFA_ERR_CAPACITY: the count alone
+    RC_TRY(h.fetch(ids, d_ids, count * sizeof(uint32_t)));
+    RC_TRY(h.fetch(sizes, d_sizes, count * sizeof(uint32_t)));
+    RC_TRY(h.fetch(codes, d_codes, count * L));
+    RC_TRY(h.fetch(nearest, d_nearest, count * sizeof(uint32_t)));
+    if (n) RC_TRY(h.fetch(div, d_div, n * sizeof(uint32_t)));
+    RC_TRY(h.wait());
+    trim({&J.out});
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_consensus");
 }
 #undef RC_TRY
