@@ -575,6 +575,66 @@ int smafa_db_self_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint
 int smafa_db_self_peaks_launch(smafa_db *db, uint32_t max_div, uint32_t radius, void *d_labels, void *d_parents /* may be NULL */, void *d_weights /* may be NULL */, void *d_n_peaks /* uint64 */);
 int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t *labels, uint32_t *parents /* may be NULL */, uint32_t *weights /* may be NULL */, uint64_t cap, uint64_t *n_peaks);
 
+/* ------------------------------------------------- chimera check of the store (two-parent bimeras over the self-join) */
+/*
+ * "Which rows are one heavier row's head on another heavier row's tail": the step every amplicon denoiser takes behind its
+ * partition (UNOISE, UCHIME de novo, DADA2's isBimeraDenovo).  A PCR chimera starts as a copy of one abundant sequence and
+ * ends as a copy of another; smafa_db_self_peaks crowns such a row a centre of its own.  For rows of one length, column by
+ * column, the check is exact.  Let n = n_subjects, L = seq_len, max_div = D, radius = r <= D (SMAFA_NONE: r = D), min_fold =
+ * F >= 1.
+ *   weight[i]  exactly as in smafa_db_self_peaks at radius r: 1 + the number of OTHER subjects within r of i.  With weights_in
+ *              (n uint32) those are used instead and no weight is counted (r is still checked).  A row of weight 0 takes no
+ *              part, neither as a candidate nor as a parent.
+ *   p is an ELIGIBLE PARENT of q iff p != q, both weights are non-zero, distance(q, p) <= D (the scan's distance: the number
+ *              of columns whose codes differ), weight[p] > weight[q] and (uint64)weight[p] >= (uint64)F * weight[q].
+ *   pre(q, p)  for an eligible pair the rows differ in source columns d_0 < ... < d_{m-1}, m >= 1 (copies have equal weights,
+ *              so m = 0 never occurs): pre(q, p) = d_0, the length of the common prefix in the CALLER's column order, and
+ *              suf(q, p) = L - 1 - d_{m-1}, the length of the common suffix.  (Under weights_in copies may carry unequal weights:
+ *              rows that are equal column by column are never each other's parents, whatever their weights.)
+ *   left_parent[q]  = the eligible p of greatest (pre(q, p), -p): the longest prefix, ties to the smaller subject number;
+ *   left_len[q]     = that prefix length.  right_parent[q], right_len[q]: the same with suf.  Without an eligible parent both
+ *              parents are SMAFA_NONE and both lengths 0.
+ *   flags[q]   = 1 iff q has an eligible parent and left_len[q] + right_len[q] >= L, else 0.  One parent can never satisfy
+ *              this alone: pre + suf = L - 1 - (d_{m-1} - d_0) < L.  A flagged row therefore always has two distinct parents,
+ *              and any breakpoint b with L - right_len[q] <= b <= left_len[q] reproduces q as left_parent[:b] + right_parent[b:].
+ *   *n_chimeras = the number of flagged rows.
+ * Parents are looked for only within D of the candidate.  A bimera's distance to either parent is at most the parents' own
+ * distance, so D has to be at least the divergence of the parents one wants to catch.  max_div >= seq_len is legal and means
+ * "every other row is a candidate parent": the join then runs at seq_len, as smafa_db_self_hits runs it, and lists every pair —
+ * a pair with no column in common has pre = suf = 0 and can change a result only as a parent of last resort at length 0 with
+ * the smaller number.  (That is n (n - 1) / 2 pairs: a bound for small stores.)  radius >= seq_len with counted weights gives
+ * every row the weight n: no parent anywhere, nothing flagged, no scan.
+ * The answer is an exact integer function of the store, D, r, F and weights_in, and the same bytes from run to run and under
+ * smafa_set_prefilter / smafa_set_zone_level / smafa_set_index, every SMAFA_JOIN_* setting and SMAFA_DENSITY_KEEP_MAX.
+ * The pipeline form: weights_in = the cluster sizes of smafa_db_self_peaks on the peaks and 0 elsewhere checks the centres alone.
+ * Not in the reference.  The pairs never leave the device.  Three phases with kernel boundaries between them (chimera.hip.h):
+ * phase 1 is the peaks call's — the join at D, each kept pair within r raising both weights and EVERY kept pair moving to the
+ * handle's kept pair list (the list of the density and peaks calls: SMAFA_DENSITY_KEEP_MAX is its capacity, 0 forces the
+ * two-join path); weights_in is copied over the counted weights behind the join.  Phase 2 takes every pair whose weights make
+ * one row an eligible parent of the other, gathers the bit-plane words of both rows, walks the differing packed columns back to
+ * source columns and offers (length, -parent) to the lighter row's two 8-byte slots by atomic maximum — in ONE launch over the
+ * kept list where that held every pair, otherwise in a second join that reads the raw lists.  Both give the same bytes.  Phase
+ * 3 unpacks the slots and counts.  Handle-owned scratch: 20 B per subject plus the kept list.
+ * Checks, in this order, each SMAFA_ERR_INVALID with the argument named in smafa_last_error() and nothing written: a NULL
+ * handle; NULL flags; NULL n_chimeras; max_div = SMAFA_NONE; radius > max_div (other than SMAFA_NONE); min_fold = 0; host form
+ * only: cap < n_subjects.  Then the count is zeroed — the first write — and the arrays are written only by a call that
+ * succeeds.  An empty store writes nothing but the count; one row gives flags {0}, both parents SMAFA_NONE, both lengths 0.
+ * The self-join's one failure is inherited unchanged (SMAFA_ERR_NOMEM where 64 rows alone overfill the scratch list; the
+ * handle stays usable).
+ *
+ * smafa_db_self_chimeras_launch: device-resident form.  d_weights_in = device buffer of n_subjects uint32 or NULL; d_flags and
+ * (each or NULL) d_left_parent, d_left_len, d_right_parent, d_right_len, d_weights = device buffers of n_subjects uint32;
+ * d_n_chimeras = device uint64.  Synchronisation as for smafa_db_self_peaks_launch.  smafa_last_scan_ms / smafa_last_call_stats
+ * hold the device time and launches of record building, scans (of both joins, where two ran), weigh/keep passes, the offers
+ * and the verdict; smafa_last_call_kernels lists the scan-family instantiations first, then smafa_join::store_records_kernel,
+ * then smafa_join::inverse_order_kernel if it ran, then smafa_pk::init_peaks_kernel, smafa_pk::weigh_keep_kernel (a join ran),
+ * chimera::init_sides_kernel, chimera::offer_sides_kernel (a pair was kept) and chimera::verdict_kernel.
+ *
+ * smafa_db_self_chimeras: host form.  cap = capacity of `flags` (and of the five arrays behind it, unless NULL) in entries.
+ */
+int smafa_db_self_chimeras_launch(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t min_fold, const void *d_weights_in /* may be NULL */, void *d_flags, void *d_left_parent, void *d_left_len, void *d_right_parent, void *d_right_len, void *d_weights /* the last five may be NULL */, void *d_n_chimeras /* uint64 */);
+int smafa_db_self_chimeras(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t min_fold, const uint32_t *weights_in, uint32_t *flags, uint32_t *left_parent, uint32_t *left_len, uint32_t *right_parent, uint32_t *right_len, uint32_t *weights, uint64_t cap, uint64_t *n_chimeras);
+
 /* ------------------------------------------------- neighbour lists of the store (the self-join's graph in CSR form, k nearest) */
 /*
  * "Who is near row i, nearest first": the one general output of the self-join, in the form graph tools take (a CSR matrix,
@@ -888,6 +948,13 @@ int smafa_density(const char *db_path, uint32_t max_divergence, uint32_t min_pts
  * (smafa_db_self_peaks at max_divergence and radius), "{i}\t{label}\t{parent}\t{weight}\n" in subject order.  An empty DB
  * prints nothing. */
 int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, int out_fd, int device);
+/* `smafa chimeras` (not in the reference): the same DB, and per subject the verdict of the chimera check (smafa_db_self_chimeras
+ * at max_divergence, radius and min_fold), "{i}\t{flag}\t{left_parent}\t{left_len}\t{right_parent}\t{right_len}\t{weight}\n" in
+ * subject order, -1 for SMAFA_NONE.  weights_path NULL: the weights are counted at the radius.  Else a file of "{i}\t{weight}[\t...]\n"
+ * lines ("-": stdin; further columns ignored; in any order; a subject without a line has weight 0); a line that is not of that
+ * form, a second line for one subject or a subject number the DB does not have is SMAFA_ERR_INVALID with a text that names the
+ * line (exit status 1).  An empty DB prints nothing. */
+int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius, uint32_t min_fold, const char *weights_path, int out_fd, int device);
 /* `smafa neighbours` (not in the reference): the same DB, and per subject its neighbours within max_divergence, nearest first,
  * at most max_num_hits of them (SMAFA_NONE: all) — smafa_db_self_neighbours, a degrees-only call and then the sized one —
  * "{i}\t{j}\t{dist}\n" per entry, both directions of every pair, ordered by (i, dist, j).  An empty DB prints nothing. */

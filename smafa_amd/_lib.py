@@ -37,6 +37,7 @@ EXPORTS = [
     "smafa_db_self_levels_launch", "smafa_db_self_levels", "smafa_component_levels",
     "smafa_db_self_density_launch", "smafa_db_self_density", "smafa_density",
     "smafa_db_self_peaks_launch", "smafa_db_self_peaks", "smafa_peaks",
+    "smafa_db_self_chimeras_launch", "smafa_db_self_chimeras", "smafa_chimeras",
     "smafa_db_self_neighbours_launch", "smafa_db_self_neighbours", "smafa_neighbours",
     "smafa_db_self_since_launch", "smafa_db_self_hits_since", "smafa_db_self_components_update_launch",
     "smafa_db_self_components_update", "smafa_pairs_since",
@@ -184,6 +185,9 @@ def lib() -> C.CDLL:
     l.smafa_db_self_peaks_launch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     l.smafa_db_self_peaks.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
     l.smafa_peaks.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
+    l.smafa_db_self_chimeras_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.smafa_db_self_chimeras.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
+    l.smafa_chimeras.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int]
     l.smafa_db_self_neighbours_launch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]
     l.smafa_db_self_neighbours.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
     l.smafa_db_self_since_launch.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]

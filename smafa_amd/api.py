@@ -8,6 +8,7 @@ ABI of libsmafa_amd.so; nothing here computes distances on the CPU.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -18,6 +19,8 @@ from . import _lib
 from ._lib import ALPHABET_AA, ALPHABET_NT, NONE, Hit, SmafaError, SmafaPanic, check, lib
 
 HIT_DTYPE = np.dtype([("query", "<u4"), ("subject", "<u4"), ("dist", "<u4")])
+# what SubjectStore.self_chimeras returns: six uint32 arrays, one entry per subject, and the number of flagged rows
+Chimeras = collections.namedtuple("Chimeras", "flags left_parent left_len right_parent right_len weights n_chimeras")
 
 
 def _opt(v: Optional[int]) -> int:
@@ -341,6 +344,41 @@ class SubjectStore:
                                                C.c_void_p(d_parents) if d_parents else None,
                                                C.c_void_p(d_weights) if d_weights else None,
                                                C.c_void_p(d_n_peaks) if d_n_peaks else None))
+
+    # ---- chimera check -----------------------------------------------------------------------
+    def self_chimeras(self, max_divergence: int, min_fold: int = 2, radius: Optional[int] = 0, weights=None) -> Chimeras:
+        """Chimeras(flags, left_parent, left_len, right_parent, right_len, weights, n_chimeras) — smafa_db_self_chimeras: the
+        two-parent bimeras of the store.  A parent of row q is a row within max_divergence of it whose weight is greater and at
+        least min_fold times q's; left_parent[q] shares the longest prefix with q (left_len[q] columns), right_parent[q] the
+        longest suffix, ties to the smaller number, NONE and 0 without a parent; flags[q] = 1 iff left_len[q] + right_len[q] >=
+        seq_len: q is left_parent's head on right_parent's tail.  The weights are counted as self_peaks counts them at `radius`
+        (0: exact copies; None: max_divergence), or taken from `weights` (uint32, one per subject; a row of weight 0 takes no
+        part), and returned.  uint32, one per subject.  The pairs stay on the device."""
+        n = self.info().n_subjects
+        given = None
+        if weights is not None:
+            given = np.ascontiguousarray(weights, dtype=np.uint32)
+            if given.shape != (n,):
+                raise ValueError(f"weights has shape {given.shape}, the store has {n} subjects")
+            if n == 0:
+                given = np.zeros(1, dtype=np.uint32)
+        out = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(6)]
+        count = C.c_uint64(0)
+        check(lib().smafa_db_self_chimeras(self._h, _opt(max_divergence), _opt(radius), int(min_fold),
+                                           given.ctypes.data if given is not None else None, *(a.ctypes.data for a in out), n,
+                                           C.byref(count)))
+        return Chimeras(*(a[:n] for a in out), int(count.value))
+
+    def self_chimeras_launch(self, max_divergence: int, radius: Optional[int], min_fold: int, d_weights_in: int, d_flags: int,
+                             d_left_parent: int, d_left_len: int, d_right_parent: int, d_right_len: int, d_weights: int,
+                             d_n_chimeras: int) -> None:
+        """device-resident form (smafa_db_self_chimeras_launch): n_subjects uint32 weights in d_weights_in (0: counted at the
+        radius), as many flags in d_flags and — each 0 where not wanted — parents, lengths and weights in the five buffers
+        behind it, the number of flagged rows in *d_n_chimeras (device uint64)"""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().smafa_db_self_chimeras_launch(self._h, _opt(max_divergence), _opt(radius), int(min_fold), ptr(d_weights_in),
+                                                  ptr(d_flags), ptr(d_left_parent), ptr(d_left_len), ptr(d_right_parent),
+                                                  ptr(d_right_len), ptr(d_weights), ptr(d_n_chimeras)))
 
     # ---- neighbour lists ------------------------------------------------------------------
     def self_neighbours(self, max_divergence: int, k: Optional[int] = None, dists: bool = True, first_cap: int = 1 << 16):
@@ -798,6 +836,15 @@ def peaks(db_path: str, max_divergence: int, radius: Optional[int] = 0, out_fd: 
     """`smafa peaks`: "i\\tlabel\\tparent\\tweight" per subject of the DB file — its abundance-peak label and parent at
     max_divergence and its weight at `radius` (smafa_db_self_peaks) — to out_fd."""
     check(lib().smafa_peaks(os.fsencode(db_path), _opt(max_divergence), _opt(radius), out_fd, device))
+
+
+def chimeras(db_path: str, max_divergence: int, min_fold: int = 2, radius: Optional[int] = 0, weights_path: Optional[str] = None,
+             out_fd: int = 1, device: int = 0) -> None:
+    """`smafa chimeras`: "i\\tflag\\tleft_parent\\tleft_len\\tright_parent\\tright_len\\tweight" per subject of the DB file
+    (smafa_db_self_chimeras; -1 for no parent), the weights counted at `radius` or read from weights_path ("i\\tweight" lines,
+    "-": stdin), to out_fd."""
+    check(lib().smafa_chimeras(os.fsencode(db_path), _opt(max_divergence), _opt(radius), int(min_fold),
+                               os.fsencode(weights_path) if weights_path is not None else None, out_fd, device))
 
 
 def component_levels(db_path: str, max_divergence: int, out_fd: int = 1, device: int = 0) -> None:

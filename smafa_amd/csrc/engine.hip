@@ -31,6 +31,7 @@
 #include "reach.hip.h"
 #include "stable.hip.h"
 #include "consensus.hip.h"
+#include "chimera.hip.h"
 
 namespace smafa {
 

@@ -884,17 +884,18 @@ static int parse_labels(const std::string &text, size_t n, std::vector<uint32_t>
     return SMAFA_OK;
 }
 
-static int read_whole(const char *path, std::string &text) {
+// the whole of a verb's side file ("-": stdin); who: the verb, what: the file's kind, for the texts
+static int read_whole(const char *who, const char *what, const char *path, std::string &text) {
     const bool std_in = !strcmp(path, "-");
     const int fd = std_in ? 0 : open(path, O_RDONLY);
-    if (fd < 0) return set_error(SMAFA_ERR_IO, "smafa_consensus: cannot open labels file \"%s\": %s", path, strerror(errno));
+    if (fd < 0) return set_error(SMAFA_ERR_IO, "%s: cannot open %s file \"%s\": %s", who, what, path, strerror(errno));
     char buf[1 << 16];
     ssize_t got = 0;
     while ((got = read(fd, buf, sizeof buf)) > 0 || (got < 0 && errno == EINTR))
         if (got > 0) text.append(buf, (size_t)got);
     const int err = errno;
     if (!std_in) close(fd);
-    return got < 0 ? set_error(SMAFA_ERR_IO, "smafa_consensus: reading labels file \"%s\": %s", path, strerror(err)) : SMAFA_OK;
+    return got < 0 ? set_error(SMAFA_ERR_IO, "%s: reading %s file \"%s\": %s", who, what, path, strerror(err)) : SMAFA_OK;
 }
 
 // The consensus of every labelled cluster of a DB file (smafa_db_consensus), printed
@@ -905,7 +906,7 @@ int smafa_consensus(const char *db_path, const char *labels_path, int out_fd, in
     int rc = begin_store_verb("smafa_consensus", db_path, 0 /* no bound to check */, device, v);
     if (rc) return rc;
     std::string text;
-    rc = read_whole(labels_path, text);
+    rc = read_whole("smafa_consensus", "labels", labels_path, text);
     std::vector<uint32_t> labels;
     if (!rc) rc = parse_labels(text, v.n, labels);
     if (rc || v.empty) return rc;
@@ -1000,6 +1001,93 @@ int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, i
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_peaks");
+}
+
+// ------------------------------------------------------------------------------------ chimeras
+// A weights file: "{i}\t{weight}" and whatever columns follow per line, in any order; a subject without a line has weight 0.
+// `text` is the whole file; -> weights[n], or SMAFA_ERR_INVALID naming the first line that is not what it should be.
+static int parse_weights(const std::string &text, size_t n, std::vector<uint32_t> &weights) {
+    weights.assign(n, 0);
+    std::vector<bool> seen(n, false);
+    size_t at = 0, line = 0;
+    const auto bad = [&](const char *what) {
+        return set_error(SMAFA_ERR_INVALID, "smafa_chimeras: weights line %llu: %s", (unsigned long long)line + 1, what);
+    };
+    // an unsigned decimal number of at most ten digits at text[at ..), -> false where there is none
+    const auto number = [&](uint64_t *out) {
+        size_t digits = 0;
+        uint64_t v = 0;
+        while (at < text.size() && text[at] >= '0' && text[at] <= '9' && digits < 11) v = v * 10 + (uint64_t)(text[at++] - '0'), digits++;
+        *out = v;
+        return digits > 0 && digits < 11;
+    };
+    for (; at < text.size(); line++) {
+        uint64_t i = 0, weight = 0;
+        if (!number(&i)) return bad("no sequence number");
+        if (at >= text.size() || text[at] != '\t') return bad("no tab behind the sequence number");
+        at++;
+        if (i >= n) return bad("the sequence number is not one of the database's");
+        if (seen[i]) return bad("a second line for this sequence");
+        if (!number(&weight) || weight > 0xffffffffull) return bad("no weight (an unsigned 32-bit number)");
+        if (at < text.size() && text[at] != '\t' && text[at] != '\n' && text[at] != '\r') return bad("the weight is not a number");
+        seen[i] = true;
+        weights[i] = (uint32_t)weight;
+        while (at < text.size() && text[at] != '\n') at++;  // further columns
+        if (at < text.size()) at++;
+    }
+    return SMAFA_OK;
+}
+
+// The verdict of the chimera check for every subject of a DB file (smafa_db_self_chimeras), printed
+// "{i}\t{flag}\t{left_parent}\t{left_len}\t{right_parent}\t{right_len}\t{weight}\n" in subject order, -1 for SMAFA_NONE.
+int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius, uint32_t min_fold, const char *weights_path, int out_fd,
+                   int device) try {
+    StoreVerb v;
+    int rc = begin_store_verb("smafa_chimeras", db_path, max_divergence, device, v, [&] {
+        if (radius != SMAFA_NONE && radius > max_divergence)
+            return set_error(SMAFA_ERR_INVALID, "smafa_chimeras: radius %u is larger than max_divergence %u", radius, max_divergence);
+        if (min_fold == 0) return set_error(SMAFA_ERR_INVALID, "smafa_chimeras: min_fold is 0");
+        return (int)SMAFA_OK;
+    });
+    if (rc || v.empty) return rc;
+    const size_t n = v.n;
+    std::vector<uint32_t> given;
+    if (weights_path) {
+        std::string text;
+        rc = read_whole("smafa_chimeras", "weights", weights_path, text);
+        if (!rc) rc = parse_weights(text, n, given);
+        if (rc) return rc;
+    }
+    std::vector<uint32_t> flags(n), left(n), left_len(n), right(n), right_len(n), weights(n);
+    uint64_t n_chimeras = 0;
+    rc = smafa_db_self_chimeras(v.store.db, max_divergence, radius, min_fold, weights_path ? given.data() : nullptr, flags.data(), left.data(),
+                                left_len.data(), right.data(), right_len.data(), weights.data(), n, &n_chimeras);
+    if (!rc) rc = write_rows(out_fd, n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        const auto parent = [&](uint32_t p) {
+            if (p == SMAFA_NONE) text += "-1";
+            else append_u32(text, p);
+        };
+        append_u32(text, (uint32_t)i);
+        text.push_back('\t');
+        append_u32(text, flags[i]);
+        text.push_back('\t');
+        parent(left[i]);
+        text.push_back('\t');
+        append_u32(text, left_len[i]);
+        text.push_back('\t');
+        parent(right[i]);
+        text.push_back('\t');
+        append_u32(text, right_len[i]);
+        text.push_back('\t');
+        append_u32(text, weights[i]);
+        text.push_back('\n');
+    });
+    if (rc) return rc;
+    log_line(1, "%llu chimeras among %llu sequences within %u, weights %s, fold %u, took %llu seconds", (unsigned long long)n_chimeras,
+             (unsigned long long)n, max_divergence, weights_path ? "given" : "counted", min_fold, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_chimeras");
 }
 
 // ------------------------------------------------------------------------------------ neighbours

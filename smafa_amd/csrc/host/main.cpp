@@ -20,6 +20,8 @@
 //           number of neighbours within the bound of every subject)
 //   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
 //           and the weight of every subject)
+//   chimeras -d/--database FILE  --max-divergence INT  [--min-fold INT] [--radius INT] [--weights FILE|-]   (this build only: the
+//           chimera check, per subject its flag, its best left and right parent with the shared prefix / suffix length, its weight)
 //   neighbours -d/--database FILE  --max-divergence INT  [--max-num-hits INT]   (this build only: per subject its neighbours
 //           within the bound, nearest first)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
@@ -92,6 +94,15 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        the number of other sequences within the radius (default 0: the number of exact copies); parent = the heaviest\n"
             "        sequence within the bound, ties to the smaller number, the sequence itself if none outranks it (a peak);\n"
             "        label = the peak reached by following the parents)\n"
+            "chimeras -d, --database <FILE>  --max-divergence <INT>  [--min-fold <INT>] [--radius <INT>] [--weights <FILE|->]  [--device <N>]\n"
+            "        (not in the reference: two-parent chimeras among the database's own sequences, one\n"
+            "        \"i<TAB>flag<TAB>left_parent<TAB>left_len<TAB>right_parent<TAB>right_len<TAB>weight\" line per sequence; a parent is a\n"
+            "        sequence within the bound that is heavier, and at least min-fold (default 2) times as heavy; left_parent shares the\n"
+            "        longest prefix (left_len columns) with the sequence, right_parent the longest suffix, ties to the smaller number, -1\n"
+            "        for none; flag = 1 where left_len + right_len covers the sequence: it is left_parent's head on right_parent's tail;\n"
+            "        weight as in `peaks` (--radius, default 0: the number of exact copies), or from --weights, \"i<TAB>weight\" lines in any\n"
+            "        order (further columns are ignored, a sequence without a line has weight 0 and takes no part, -: stdin); the bound\n"
+            "        has to be at least the divergence of the parents one wants to catch)\n"
             "neighbours -d, --database <FILE>  --max-divergence <INT>  [--max-num-hits <INT>]  [--device <N>]  (not in the reference: the\n"
             "        neighbour lists of the database's own sequences, one \"i<TAB>j<TAB>divergence\" line per sequence i and neighbour j\n"
             "        within the bound, both directions of every pair, ordered by i, then divergence, then j; --max-num-hits: at most\n"
@@ -133,9 +144,9 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr;
     std::vector<const char *> count_paths;
-    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0;
+    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2;
     bool have_min_pts = false, have_since = false;
     unsigned long long since = 0;
     bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false, joined = false;
@@ -180,8 +191,12 @@ int main(int argc, char **argv) {
             joined = true;
         } else if (a == "--labels" && cmd == "consensus") {
             if (!(labels = value())) return usage("--labels needs a file, or - for stdin");
-        } else if (a == "--radius" && cmd == "peaks") {
+        } else if (a == "--radius" && (cmd == "peaks" || cmd == "chimeras")) {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
+        } else if (a == "--min-fold" && cmd == "chimeras") {
+            if (!parse_u32(value(), &min_fold) || min_fold == 0) return usage("--min-fold needs a positive integer");
+        } else if (a == "--weights" && cmd == "chimeras") {
+            if (!(weights = value())) return usage("--weights needs a file, or - for stdin");
         } else if (a == "--since" && cmd == "pairs") {
             const char *v = value();
             char *end = nullptr;
@@ -282,6 +297,10 @@ int main(int argc, char **argv) {
         if (!database) return usage("peaks needs --database");
         if (!have_max_div) return usage("peaks needs --max-divergence");
         rc = smafa_peaks(database, max_div, radius, 1, (int)device);
+    } else if (cmd == "chimeras") {
+        if (!database) return usage("chimeras needs --database");
+        if (!have_max_div) return usage("chimeras needs --max-divergence");
+        rc = smafa_chimeras(database, max_div, radius, min_fold, weights, 1, (int)device);
     } else if (cmd == "neighbours") {
         if (!database) return usage("neighbours needs --database");
         if (!have_max_div) return usage("neighbours needs --max-divergence");

@@ -1,7 +1,7 @@
 // self_join.hip.h — host code of the self-join of a resident store.  Two drivers walk the store and know no consumer: join_pass (every
 // row against the rows behind it) and delta_pass (the rows appended since a mark against the whole store).  Each cuts its spans
-// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Eleven calls
-// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_neighbours, join_forest,
+// its own way and runs every span through join_span, which scans the span's blocks piece by piece (join_pieces).  Twelve calls
+// consume the pieces: join_pairs, join_components, join_levels, join_density, join_peaks, join_chimeras, join_neighbours, join_forest,
 // join_reach_forest and join_stable (the reach forest's passes, then its own) over join_pass, delta_pairs and delta_components
 // over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
 // or more JoinConsumers: timed_consumer (a kernel per piece), watching (that, gated on a device counter read at every wait),
@@ -701,6 +701,82 @@ static int join_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t 
              "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s", n, max_div, radius, J.blocks + J.rescans,
              J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
              J.jump_rounds == 1 ? "" : "s");
+    return SMAFA_OK;
+}
+
+// smafa_db_self_chimeras_launch (chimera.hip.h): d_flags is n flags, d_count one counter, J.parent holds left[] and right[] (8 B
+// each per subject) and weight[] (4 B) behind them.  Phase 1 is the peaks call's: the join with smafa_pk::weigh_keep_kernel per
+// piece, which raises both weights of every kept pair within the radius and moves every kept pair to J.kept while that has room.
+// With d_weights_in the pairs are kept all the same and the caller's weights are copied over the counted ones behind the join.
+// The kept total then decides (kept_plan) how chimera::offer_sides_kernel gets the pairs, and chimera::verdict_kernel writes the
+// outputs and the count.  max_div >= seq_len: every other row is a candidate parent, and the join runs AT seq_len, as the pairs
+// call runs it — it lists every pair, those with no column in common included, which offer length 0 like any other.  Counted
+// weights at a radius >= seq_len are all n: no row has a parent and nothing is scanned.
+// radius <= max_div; min_fold >= 1; d_weights_in and the five arrays behind d_flags: n entries each, or nullptr
+static int join_chimeras(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t min_fold, const uint32_t *d_weights_in, uint32_t *d_flags,
+                         uint32_t *d_left_parent, uint32_t *d_left_len, uint32_t *d_right_parent, uint32_t *d_right_len,
+                         uint32_t *d_weights, unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool all_heavy = !d_weights_in && radius >= db->L;
+    const uint32_t scan_div = std::min(max_div, db->L);
+    JoinCall c{db, db->n < 2 || all_heavy};
+    RC_TRY(join_begin(c, d_count, 1, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * 5u * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(4 * sizeof(unsigned long long)));
+    unsigned long long *const left = J.parent.as<unsigned long long>(), *const right = left + n;
+    uint32_t *const weight = J.parent.as<uint32_t>() + 4 * (size_t)n;
+    RC_TRY(timed_begin(c, &J.count_ms, "chimeras: weight[] initialised"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 4 * sizeof(unsigned long long), db->stream));
+    hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, left, weight, n, all_heavy ? n : 1u, 0u);
+    RC_TRY(timed_end(c));
+    const uint32_t perm_words = 32u * db->W <= chimera::kPermLdsWords ? 32u * db->W : 0u;
+    const auto launch_weigh = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_pk::weigh_keep_kernel, list_grid(p.count), dim3(256), 0,
+                           db->stream, p.list, p.count, p.p0, p.S, p.R, p.order, J.pos_of.as<uint32_t>(), weight, radius,
+                           J.kept.as<smafa_hit>(), (unsigned long long)kept_room(db), J.ctl.as<unsigned long long>());
+    };
+    const auto launch_offer = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(chimera::offer_sides_kernel, list_grid(p.count), dim3(256), perm_words * sizeof(uint32_t), db->stream, p.list,
+                           p.count, p.p0, p.S, p.R, p.order, J.pos_of.as<uint32_t>(), weight, min_fold, db->d_planes, db->P, db->W, db->L,
+                           db->d_perm.as<uint32_t>(), perm_words, left, right);
+    };
+    const char *const weighed = "chimeras: a piece's rows weighed", *const offered = "chimeras: a piece's rows offered";
+    JoinConsumer weigh = keeping_consumer(c, &J.count_ms, weighed, launch_weigh);
+    JoinConsumer offer = timed_consumer(c, &J.link_ms, offered, launch_offer);
+    if (!c.no_scans) {
+        RC_TRY(join_positions(c));
+        RC_TRY(join_pass(c, scan_div, weigh));
+    }
+    unsigned long long kept_total = 0;
+    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    // every counted weight is final: the caller's weights over them, the empty slots, and the offers over the kept list, if that has
+    // every pair, in ONE timed pass
+    const KeptPlan plan = kept_plan(db, kept_total, "chimeras", "offer");
+    RC_TRY(timed_begin(c, &J.link_ms, plan == kKeptOnce ? offered : "chimeras: left[] and right[] initialised"));
+    if (d_weights_in) HIP_TRY(hipMemcpyAsync(weight, d_weights_in, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, db->stream));
+    hipLaunchKernelGGL(chimera::init_sides_kernel, row_grid(n), dim3(256), 0, db->stream, left, right, n);
+    HIP_TRY(hipGetLastError());
+    offer.used = plan == kKeptOnce;
+    if (offer.used) launch_offer(kept_piece(db, kept_total));
+    RC_TRY(timed_end(c, offer.used ? 2u : 1u));
+    if (plan == kKeptJoinAgain) RC_TRY(join_pass(c, scan_div, offer));
+    RC_TRY(join_flatten(c, [&] {
+        hipLaunchKernelGGL(chimera::verdict_kernel, row_grid(n), dim3(256), 0, db->stream, left, right, weight, n, db->L, d_flags, d_left_parent,
+                           d_left_len, d_right_parent, d_right_len, d_weights, d_count);
+    }));
+    join_finish(c);
+    note_call_kernel(db, "smafa_pk::init_peaks_kernel");
+    if (weigh.used) note_call_kernel(db, "smafa_pk::weigh_keep_kernel");
+    note_call_kernel(db, "chimera::init_sides_kernel");
+    if (offer.used) note_call_kernel(db, "chimera::offer_sides_kernel");
+    note_call_kernel(db, "chimera::verdict_kernel");
+    log_line(2, "chimeras of %u rows at bound %u, radius %u, fold %u%s: %u scans (%u of them repeats) in %u join%s, records %.3f ms, "
+             "scans %.3f ms, weigh/keep %.3f ms, offers %.3f ms, verdict %.3f ms, %llu pairs kept", n, max_div, radius, min_fold,
+             d_weights_in ? ", weights given" : "", J.blocks + J.rescans, J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms,
+             J.count_ms, J.link_ms, J.flatten_ms, kept_total);
     return SMAFA_OK;
 }
 // ---- the entry list of the neighbours call (neighbours.hip.h): two entries per kept pair, 8 B each — and 4 B more, the rows,

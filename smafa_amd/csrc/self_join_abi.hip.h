@@ -1,8 +1,8 @@
-// self_join_abi.hip.h — the C ABI of the self-join: the twenty-two smafa_db_self_* entry points, eleven calls in two forms each — and,
+// self_join_abi.hip.h — the C ABI of the self-join: the twenty-four smafa_db_self_* entry points, twelve calls in two forms each — and,
 // last, the two forms of smafa_db_consensus, which takes labels such as theirs and shares their host form.  The
 // *_launch form checks its arguments and hands the caller's device pointers to the call of self_join.hip.h.  The host form checks
 // the same, then runs the same call on the handle's own buffers and copies the results out: pairs_to_host for the two pair
-// lists, HostForm for the nine calls that return arrays and counters.
+// lists, HostForm for the ten calls that return arrays and counters.
 // A new call: its two entry points here, built from self_args / HostForm / trim; what it checks beyond self_args, and where it zeroes
 // its outputs among its checks, is its own (the order is part of the contract: tests hold what a failing check leaves untouched).
 // Included once by engine.hip, inside extern "C", behind self_join.hip.h.
@@ -13,7 +13,7 @@ static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "counters and offs
 // ---- argument checks: `who` is the entry point, the name is the argument's
 static int missing(const char *who, const char *name) { return set_error(SMAFA_ERR_INVALID, "%s: NULL %s", who, name); }
 
-// what twenty of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
+// what twenty-two of the entry points check first, in this order: the handle, two arguments, the bound (`needs`: the bound's text)
 static int self_args(const char *who, const smafa_db *db, bool has_a, const char *a, bool has_b, const char *b, uint32_t max_div,
                      const char *needs) {
     if (!db) return missing(who, "handle");
@@ -415,6 +415,60 @@ int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_self_peaks");
+}
+
+// ---- chimeras
+// behind self_args: the radius, then the fold (nothing is written before they pass)
+static int chimera_args(const char *who, uint32_t radius, uint32_t max_div, uint32_t min_fold) {
+    RC_TRY(radius_arg(who, radius, max_div));
+    if (min_fold == 0) return set_error(SMAFA_ERR_INVALID, "%s: min_fold is 0 (1: any heavier row may be a parent)", who);
+    return SMAFA_OK;
+}
+
+int smafa_db_self_chimeras_launch(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t min_fold, const void *d_weights_in, void *d_flags,
+                                  void *d_left_parent, void *d_left_len, void *d_right_parent, void *d_right_len, void *d_weights,
+                                  void *d_n_chimeras) try {
+    RC_TRY(self_args("smafa_db_self_chimeras_launch", db, d_flags, "flags", d_n_chimeras, "n_chimeras", max_div, "a chimera check needs a bound"));
+    RC_TRY(chimera_args("smafa_db_self_chimeras_launch", radius, max_div, min_fold));
+    return join_chimeras(db, max_div, radius == SMAFA_NONE ? max_div : radius, min_fold, (const uint32_t *)d_weights_in, (uint32_t *)d_flags,
+                         (uint32_t *)d_left_parent, (uint32_t *)d_left_len, (uint32_t *)d_right_parent, (uint32_t *)d_right_len,
+                         (uint32_t *)d_weights, (unsigned long long *)d_n_chimeras);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_chimeras_launch");
+}
+
+int smafa_db_self_chimeras(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t min_fold, const uint32_t *weights_in, uint32_t *flags,
+                           uint32_t *left_parent, uint32_t *left_len, uint32_t *right_parent, uint32_t *right_len, uint32_t *weights,
+                           uint64_t cap, uint64_t *n_chimeras) try {
+    RC_TRY(self_args("smafa_db_self_chimeras", db, flags, "flags", n_chimeras, "n_chimeras", max_div, "a chimera check needs a bound"));
+    RC_TRY(chimera_args("smafa_db_self_chimeras", radius, max_div, min_fold));
+    if (cap < db->n)  // (nothing is written, the count included)
+        return set_error(SMAFA_ERR_INVALID, "smafa_db_self_chimeras: cap: flags holds %llu entries, the store has %llu subjects",
+                         (unsigned long long)cap, (unsigned long long)db->n);
+    *n_chimeras = 0;
+    const HostForm h{db};
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // the flags, the five optional arrays behind them on their way to the caller and the caller's weights on their way in: 4 B x 7
+    // per subject
+    RC_TRY(h.stage(std::max<uint64_t>(n, 1) * 7u * sizeof(uint32_t), 1));
+    uint32_t *const d_flags = J.out.as<uint32_t>(), *const d_in = d_flags + 6 * n;
+    uint32_t *const taker[5] = {left_parent, left_len, right_parent, right_len, weights};
+    uint32_t *d_out[5];
+    for (int k = 0; k < 5; k++) d_out[k] = taker[k] ? d_flags + (uint64_t)(k + 1) * n : nullptr;
+    if (weights_in && n) HIP_TRY(hipMemcpyAsync(d_in, weights_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, db->stream));
+    RC_TRY(join_chimeras(db, max_div, radius == SMAFA_NONE ? max_div : radius, min_fold, weights_in ? d_in : nullptr, d_flags, d_out[0],
+                         d_out[1], d_out[2], d_out[3], d_out[4], h.cnt()));
+    unsigned long long count = 0;
+    RC_TRY(h.fetch(&count, h.cnt(), sizeof count));
+    RC_TRY(h.fetch(flags, d_flags, n * sizeof(uint32_t)));
+    for (int k = 0; k < 5; k++) RC_TRY(h.fetch(taker[k], d_out[k], n * sizeof(uint32_t)));
+    RC_TRY(h.wait());
+    *n_chimeras = count;
+    trim({&db->hits, &J.kept});
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_chimeras");
 }
 
 // ---- neighbours
