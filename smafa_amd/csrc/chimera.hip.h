@@ -46,10 +46,7 @@
 // the kernel boundaries.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/smafa_amd.h"
+#include "piece.hip.h"
 
 namespace chimera {
 
@@ -62,8 +59,7 @@ __global__ __launch_bounds__(256) void init_sides_kernel(unsigned long long *__r
     if (i < n) left[i] = right[i] = 0ull;
 }
 
-// order != nullptr: a raw piece list, rows {record number of the query row in its span, subject number, dist} as
-// smafa_pk::climb_kernel receives them; order == nullptr: the kept list, rows {a, b, dist} in subject numbers (p0, S, R unused).
+// Over either list form (piece.hip.h: pair_of), as smafa_pk::climb_kernel.
 // planes: the store's, P planes of W words per position; perm: 32 W entries, packed column -> source column; L: source columns;
 // perm_words: 32 W where perm[] is to be copied to LDS (the launch then gives 4 x perm_words bytes of it), else 0.
 __global__ __launch_bounds__(256) void offer_sides_kernel(const smafa_hit *__restrict__ list, unsigned long long total, uint32_t p0,
@@ -79,7 +75,7 @@ __global__ __launch_bounds__(256) void offer_sides_kernel(const smafa_hit *__res
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const smafa_hit h = list[i];
-        const uint32_t a = order ? order[p0 + (h.query % R) * S + h.query / R] : h.query, b = h.subject;
+        const uint32_t a = piece::pair_of(h, p0, S, R, order), b = h.subject;
         if (a == b) continue;
         const uint32_t wa = weight[a], wb = weight[b];
         if (wa == wb || wa == 0u || wb == 0u) continue;

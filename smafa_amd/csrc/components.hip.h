@@ -27,7 +27,7 @@
 // kernel boundary.
 #pragma once
 
-#include "kernels.hip.h"
+#include "piece.hip.h"
 
 namespace smafa_cc {
 
@@ -68,9 +68,8 @@ __device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b) 
     }
 }
 
-// The block's list as join_filter_kernel receives it: rows {query = record number of the query row in its span (position =
-// p0 + (query % R) * S + query / R), subject = subject NUMBER, dist}, self-pairs, mirror images and (block index) repeats
-// included — union is idempotent, so none of them needs filtering and neither pos_of[] nor the exactly-once rule is used.
+// A raw piece list (piece.hip.h), self-pairs, mirror images and (block index) repeats included — union is idempotent, so none
+// of them needs filtering and neither pos_of[] nor the exactly-once rule is used.
 // Early-out: one load of each parent; equal parents are one set already (in a dense family nearly every row).
 __global__ __launch_bounds__(256) void link_rows_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                         uint32_t p0, uint32_t S, uint32_t R,
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void link_rows_kernel(const smafa_hit *__restr
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const smafa_hit h = list[i];
-        const uint32_t a = order[p0 + (h.query % R) * S + h.query / R], b = h.subject;
+        const uint32_t a = order[piece::piece_pos(h.query, p0, S, R)], b = h.subject;
         if (a == b) continue;
         if (load_parent(parent, a) == load_parent(parent, b)) continue;
         unite(parent, a, b);
@@ -101,9 +100,7 @@ __global__ __launch_bounds__(256) void flatten_labels_kernel(const uint32_t *__r
         labels[i] = x;
         rep = x == i;
     }
-    const unsigned long long mask = __ballot(rep);
-    if (rep && smafa::lanes_below(mask) == 0u)  // the wave's first representative adds for all of them
-        atomicAdd(n_components, (unsigned long long)__builtin_popcountll(mask));
+    piece::wave_count(rep, n_components);  // the wave's first representative adds for all of them
 }
 
 }  // namespace smafa_cc

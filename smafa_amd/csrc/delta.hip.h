@@ -10,7 +10,7 @@
 //   seed_parents_kernel    parent[] of the union-find from the labels of the store as it was before the append, checked
 #pragma once
 
-#include "kernels.hip.h"
+#include "piece.hip.h"
 
 namespace smafa_dl {
 
@@ -49,12 +49,11 @@ __global__ __launch_bounds__(256) void gather_records_kernel(const uint32_t *__r
 //   a pair of two new rows is met twice, once by each one's scan, and kept where the partner has the smaller number;
 //   the self-pair (s == a) is dropped.
 // So every pair {i < j, j >= first_row} leaves exactly once, whatever the positions of its rows and whichever kernel
-// produced the list.  Output space as in join_filter_kernel: one wave-aggregated reservation on *out_count (zeroed by the
-// host once per call); rows past cap are counted and not stored.
+// produced the list.  Output space as in join_filter_kernel: piece::wave_append on *out_count (zeroed by the host once per
+// call); rows past cap are counted and not stored.
 __global__ __launch_bounds__(256) void delta_filter_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                            uint32_t base, const uint32_t *__restrict__ rows, smafa_hit *out,
                                                            unsigned long long cap, unsigned long long *out_count) {
-    const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long at = (unsigned long long)blockIdx.x * blockDim.x; at < total; at += stride) {
         const unsigned long long i = at + threadIdx.x;  // uniform trip count per workgroup
@@ -67,12 +66,7 @@ __global__ __launch_bounds__(256) void delta_filter_kernel(const smafa_hit *__re
             h.query = h.subject;
             h.subject = a;
         }
-        const unsigned long long mask = __ballot(keep);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(out_count, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
+        const unsigned long long slot = piece::wave_append(keep, out_count);
         if (keep && slot < cap) out[slot] = h;
     }
 }
@@ -97,8 +91,7 @@ __global__ __launch_bounds__(256) void seed_parents_kernel(const uint32_t *__res
         }
         parent[i] = to;
     }
-    const unsigned long long mask = __ballot(wrong);
-    if (wrong && smafa::lanes_below(mask) == 0u) atomicAdd(bad, (unsigned long long)__builtin_popcountll(mask));
+    piece::wave_count(wrong, bad);
 }
 
 }  // namespace smafa_dl

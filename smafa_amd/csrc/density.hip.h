@@ -36,8 +36,8 @@
 //   Union and atomicMin are idempotent, so link_cores_kernel is as correct on a raw piece list — self-pairs, mirror images
 //   and (block index) repeats included — as on the kept list, where each pair appears once in one orientation: a row is
 //   handled in both directions.
-//   the kept list: one wave-aggregated reservation per wave on the kept total, as join_filter_kernel reserves.  The ORDER
-//   of the kept rows depends on arrival; nothing that reads them does.
+//   the kept list: piece::wave_append on the kept total.  The ORDER of the kept rows depends on arrival; nothing that reads
+//   them does.
 //
 // No flags, no spinning, no hand-off between workgroups: the only synchronisation is the atomics above and the kernel
 // boundary.
@@ -65,10 +65,9 @@ __device__ __forceinline__ bool is_core(const uint32_t *__restrict__ degree, uin
     return degree[i] + 1u >= min_pts;  // (degree <= n - 1 < 2^32 - 1: no wrap)
 }
 
-// The piece's list as join_filter_kernel receives it, and its rule: a row is kept iff position(query row) <
-// pos_of[subject], which drops self-pairs, mirror images and the block index's repeats.  Per kept row both degrees are
-// raised, and the row leaves as {a, b, dist} in subject numbers for kept[first + ...], one reservation per wave on ctl[0]
-// (the kept total, exact at any capacity; zeroed by the host once per call); rows past cap are counted and not stored.
+// A raw piece list under the exactly-once rule (piece.hip.h).  Per kept row both degrees are raised, and the row leaves as
+// {a, b, dist} in subject numbers for the kept list through piece::wave_append on ctl[0] (the kept total, exact at any
+// capacity; zeroed by the host once per call); rows past cap are counted and not stored.
 // ctl[1] becomes non-zero once some add has made a row core (the value an add returns is the row's degree before it): the
 // host skips the link phase where no row is core.  One lane per wave writes it, and only while it still reads zero.
 __global__ __launch_bounds__(256) void count_keep_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
@@ -85,31 +84,21 @@ __global__ __launch_bounds__(256) void count_keep_kernel(const smafa_hit *__rest
         bool keep = false, made_core = false;
         if (i < total) {
             h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
+            keep = piece::keep_once(h, p0, S, R, order, pos_of);
             if (keep) {
-                h.query = order[qpos];  // (another position than the subject's: another subject number)
                 const uint32_t was_a = atomicAdd(degree + h.query, 1u), was_b = atomicAdd(degree + h.subject, 1u);
                 made_core = max(was_a, was_b) + 2u >= min_pts;
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (mask == 0ull) continue;
-        const bool any_core = __ballot(made_core) != 0ull;
-        unsigned long long first = 0;
-        if (lane == 0) {
-            first = atomicAdd(ctl, (unsigned long long)__builtin_popcountll(mask));
-            if (any_core && __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull) atomicOr(ctl + 1, 1ull);
-        }
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
+        if (__ballot(made_core) != 0ull && lane == 0 && __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull)
+            atomicOr(ctl + 1, 1ull);
+        const unsigned long long slot = piece::wave_append(keep, ctl);
         if (keep && slot < cap) kept[slot] = h;
     }
 }
 
-// Phase 2, degree[] final (plain loads).  order != nullptr: a raw piece list, rows {record number of the query row in its
-// span, subject number, dist} as link_rows_kernel receives them; order == nullptr: the kept list, rows {a, b, dist} in
-// subject numbers (p0, S, R unused).  Both core: the early-out of link_rows_kernel on equal parents, then unite.  Exactly one
+// Phase 2, degree[] final (plain loads), over either list form (piece.hip.h: pair_of).  Both core: the early-out of
+// link_rows_kernel on equal parents, then unite.  Exactly one
 // core: the other row is offered the core row's number (a load first: a slot that is low enough already costs no atomic; an
 // out-of-date value can only be too high, and then the atomicMin decides).  Neither: nothing.
 __global__ __launch_bounds__(256) void link_cores_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(256) void link_cores_kernel(const smafa_hit *__rest
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const smafa_hit h = list[i];
-        const uint32_t a = order ? order[p0 + (h.query % R) * S + h.query / R] : h.query, b = h.subject;
+        const uint32_t a = piece::pair_of(h, p0, S, R, order), b = h.subject;
         if (a == b) continue;
         const bool ca = is_core(degree, a, min_pts), cb = is_core(degree, b, min_pts);
         if (ca && cb) {
@@ -166,8 +155,7 @@ __global__ __launch_bounds__(256) void flatten_density_kernel(const uint32_t *__
         flags[2] = x == kNone;
     }
     for (int c = 0; c < 3; c++) {
-        const unsigned long long mask = __ballot(flags[c]);
-        if (flags[c] && smafa::lanes_below(mask) == 0u) atomicAdd(&s_counts[c], (uint32_t)__builtin_popcountll(mask));
+        piece::wave_count(flags[c], &s_counts[c]);
     }
     __syncthreads();
     if (threadIdx.x < 3u && s_counts[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)s_counts[threadIdx.x]);

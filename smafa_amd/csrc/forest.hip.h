@@ -69,72 +69,84 @@ __device__ __forceinline__ bool unite_won(uint32_t *parent, uint32_t a, uint32_t
     return false;
 }
 
-// The piece's list as join_filter_kernel receives it, and its rule: a row is kept iff position(query row) <
-// pos_of[subject], which drops self-pairs, mirror images and the block index's repeats.  A kept row leaves as {a, b, dist}
-// in subject numbers for kept[first + ...], one reservation per wave on ctl[0] (the kept total, exact at any capacity;
-// zeroed by the host once per call); rows past cap are counted and not stored.  parent[] is not touched.
+// The loop body of keep_pairs_kernel and of smafa_mr::tally_keep_kernel, row i of a raw piece list under the exactly-once rule
+// (piece.hip.h); the whole wave calls it, i < total or not.  A kept row leaves as {a, b, dist} in subject numbers for the kept
+// list through piece::wave_append on ctl[0] (the kept total, exact at any capacity; zeroed by the host once per call); rows past
+// cap are counted and not stored.  per_row(h) sees every kept row, stored or not.
+template <class PerRow>
+__device__ __forceinline__ void keep_row(const smafa_hit *__restrict__ list, unsigned long long total, unsigned long long i, uint32_t p0,
+                                         uint32_t S, uint32_t R, const uint32_t *__restrict__ order, const uint32_t *__restrict__ pos_of,
+                                         smafa_hit *kept, unsigned long long cap, unsigned long long *ctl, PerRow per_row) {
+    smafa_hit h = {0, 0, 0};
+    bool keep = false;
+    if (i < total) {
+        h = list[i];
+        keep = piece::keep_once(h, p0, S, R, order, pos_of);
+        if (keep) per_row(h);
+    }
+    const unsigned long long slot = piece::wave_append(keep, ctl);
+    if (keep && slot < cap) kept[slot] = h;
+}
+
+struct NothingPerRow {
+    __device__ __forceinline__ void operator()(const smafa_hit &) const {}
+};
+
+// keep_row and nothing else: parent[] is not touched
 __global__ __launch_bounds__(256) void keep_pairs_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                          uint32_t p0, uint32_t S, uint32_t R,
                                                          const uint32_t *__restrict__ order,
                                                          const uint32_t *__restrict__ pos_of, smafa_hit *kept,
                                                          unsigned long long cap, unsigned long long *ctl) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride) {
-        const unsigned long long i = base + threadIdx.x;  // uniform trip count per workgroup
-        smafa_hit h = {0, 0, 0};
-        bool keep = false;
-        if (i < total) {
-            h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
-            if (keep) h.query = order[qpos];  // (another position than the subject's: another subject number)
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(ctl, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
-        if (keep && slot < cap) kept[slot] = h;
-    }
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;  // (uniform trip count per workgroup)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride)
+        keep_row(list, total, base + threadIdx.x, p0, S, R, order, pos_of, kept, cap, ctl, NothingPerRow{});
 }
 
-// One weight class: the rows with dist == only_dist, all others pass by.  order != nullptr: a raw piece list, rows {record
-// number of the query row in its span, subject number, dist} as link_rows_kernel receives them; order == nullptr: the kept
-// list, rows {a, b, dist} in subject numbers (p0, S, R unused).  The early-out of link_rows_kernel comes first: equal parents
-// are one set already, and no CAS of this row could win.  A lane that won writes its row, smaller number first, to
-// edges[first + ...], one reservation per wave on *n_edges (the running edge total of the call: classes below this one have
-// filled edges[0 .. *n_edges) when the launch starts).  cap = n - 1 is never reached (header); the compare keeps a wrong
-// parent[] from writing past the caller's buffer.
+// The loop body of span_edges_kernel and of smafa_mr::span_reach_kernel, row i of a list in either form (piece.hip.h: pair_of);
+// the whole wave calls it, i < total or not.  One weight class, cls.t: all other rows pass by — cls.maybe(dist) before any
+// gather, cls.is(dist, a, b) with the two subjects in hand.  Self-pairs are skipped, and the early-out of link_rows_kernel
+// comes first: equal parents are one set already, and no CAS of this row could win.  A lane that won writes {min, max, cls.t}
+// (a DistClass row carries t already: the store of the weight is for the classes whose weight is not the distance) through
+// piece::wave_append on *n_edges (the running edge total of the call: classes below this one have filled edges[0 .. *n_edges)
+// when the launch starts).  cap = n - 1 is never reached (header); the compare keeps a wrong parent[] from writing past the
+// caller's buffer.
+template <class Class>
+__device__ __forceinline__ void span_row(const smafa_hit *__restrict__ list, unsigned long long total, unsigned long long i, uint32_t p0,
+                                         uint32_t S, uint32_t R, const uint32_t *__restrict__ order, uint32_t *parent, smafa_hit *edges,
+                                         unsigned long long cap, unsigned long long *n_edges, Class cls) {
+    smafa_hit h = {0, 0, 0};
+    bool won = false;
+    if (i < total) {
+        h = list[i];
+        if (cls.maybe(h.dist)) {
+            const uint32_t a = piece::pair_of(h, p0, S, R, order), b = h.subject;
+            if (a != b && cls.is(h.dist, a, b) && smafa_cc::load_parent(parent, a) != smafa_cc::load_parent(parent, b))
+                won = unite_won(parent, a, b);
+            h.query = min(a, b);
+            h.subject = max(a, b);
+            h.dist = cls.t;
+        }
+    }
+    const unsigned long long slot = piece::wave_append(won, n_edges);
+    if (won && slot < cap) edges[slot] = h;
+}
+
+// the rows with dist == t
+struct DistClass {
+    uint32_t t;
+    __device__ __forceinline__ bool maybe(uint32_t dist) const { return dist == t; }
+    __device__ __forceinline__ bool is(uint32_t, uint32_t, uint32_t) const { return true; }
+};
+
 __global__ __launch_bounds__(256) void span_edges_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                          uint32_t p0, uint32_t S, uint32_t R,
                                                          const uint32_t *__restrict__ order, uint32_t *parent,
                                                          uint32_t only_dist, smafa_hit *edges, unsigned long long cap,
                                                          unsigned long long *n_edges) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride) {
-        const unsigned long long i = base + threadIdx.x;  // uniform trip count per workgroup
-        smafa_hit h = {0, 0, 0};
-        bool won = false;
-        if (i < total) {
-            h = list[i];
-            if (h.dist == only_dist) {
-                const uint32_t a = order ? order[p0 + (h.query % R) * S + h.query / R] : h.query, b = h.subject;
-                if (a != b && smafa_cc::load_parent(parent, a) != smafa_cc::load_parent(parent, b)) won = unite_won(parent, a, b);
-                h.query = min(a, b);
-                h.subject = max(a, b);
-            }
-        }
-        const unsigned long long mask = __ballot(won);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(n_edges, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
-        if (won && slot < cap) edges[slot] = h;
-    }
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;  // (uniform trip count per workgroup)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride)
+        span_row(list, total, base + threadIdx.x, p0, S, R, order, parent, edges, cap, n_edges, DistClass{only_dist});
 }
 
 // Bounds no two rows can exceed, after the class seq_len - 1: parent[] is final and read-only (the kernel boundary made every
@@ -148,14 +160,8 @@ __global__ __launch_bounds__(256) void star_roots_kernel(const uint32_t *__restr
                                                          uint32_t T) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool root = i != 0u && i < n && parent[i] == i;
-    const unsigned long long mask = __ballot(root);
-    if (mask != 0ull) {
-        unsigned long long first = 0;
-        if ((threadIdx.x & 63u) == 0u) first = atomicAdd(n_edges, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
-        if (root && slot < cap) edges[slot] = smafa_hit{0u, i, seq_len};
-    }
+    const unsigned long long slot = piece::wave_append(root, n_edges);
+    if (root && slot < cap) edges[slot] = smafa_hit{0u, i, seq_len};
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long t = (unsigned long long)seq_len + i; t < T; t += stride) level_ends[t] = (unsigned long long)n - 1ull;
 }

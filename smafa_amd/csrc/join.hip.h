@@ -9,7 +9,7 @@
 //                          position(subject row), and leaves with subject numbers, the smaller first
 #pragma once
 
-#include "kernels.hip.h"
+#include "piece.hip.h"
 
 namespace smafa_join {
 
@@ -69,19 +69,14 @@ __global__ void inverse_order_kernel(const uint32_t *__restrict__ order, uint32_
     if (p < n) pos_of[order[p]] = p;
 }
 
-// The block's list holds rows {query = record number of the query row in its span (store_records_kernel: position =
-// p0 + (query % R) * S + query / R), subject = subject NUMBER, dist}: every pair the
-// scan of the block found, self-pairs and — for subjects inside or (block index) in front of the block — mirror images
-// included.  A pair of positions a < b is met as (a, b) by the block that holds a and, where b's block sees a at all, again
-// as (b, a): keeping a row iff position(query) < position(subject) keeps each pair once and drops the self-pairs, whichever
-// kernel produced the list.  Kept rows leave as {min, max of the two subject numbers, dist} through one wave-aggregated
-// reservation on *out_count (zeroed by the host once per join); rows past cap are counted and not stored.
+// A raw piece list under the exactly-once rule (piece.hip.h: the row format, keep_once).  Kept rows leave as {min, max of the
+// two subject numbers, dist} through piece::wave_append on *out_count (zeroed by the host once per join); rows past cap are
+// counted and not stored.
 __global__ __launch_bounds__(256) void join_filter_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                           uint32_t p0, uint32_t S, uint32_t R,
                                                           const uint32_t *__restrict__ order,
                                                           const uint32_t *__restrict__ pos_of, smafa_hit *out,
                                                           unsigned long long cap, unsigned long long *out_count) {
-    const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride) {
         const unsigned long long i = base + threadIdx.x;  // uniform trip count per workgroup
@@ -89,20 +84,14 @@ __global__ __launch_bounds__(256) void join_filter_kernel(const smafa_hit *__res
         bool keep = false;
         if (i < total) {
             h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
+            keep = piece::keep_once(h, p0, S, R, order, pos_of);
             if (keep) {
-                const uint32_t a = order[qpos], b = h.subject;
+                const uint32_t a = h.query, b = h.subject;
                 h.query = min(a, b);
                 h.subject = max(a, b);
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(out_count, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
+        const unsigned long long slot = piece::wave_append(keep, out_count);
         if (keep && slot < cap) out[slot] = h;
     }
 }

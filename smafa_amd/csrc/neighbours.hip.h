@@ -24,9 +24,8 @@
 // counting join in front of the filling one or a second pass over a kept list, and the order within a row would still need
 // a sort per row.  The sort is the library's radix sort; everything around it is a map over rows or over entries.
 //
-// What is atomic: the entry total alone.  ONE reservation per workgroup and loop iteration — every wave ballots, the four
-// wave counts meet in LDS, one lane adds twice their sum to *total and the waves take their shares of what it returns (the
-// form of smafa_pk::weigh_keep_kernel).  The exactly-once rule presents each unordered pair to exactly one lane of one
+// What is atomic: the entry total alone, through piece::block_append with two entries per kept row: ONE reservation per
+// workgroup and loop iteration.  The exactly-once rule presents each unordered pair to exactly one lane of one
 // launch, so the list holds each directed pair once; its ORDER depends on arrival, and the sort — whose keys are all
 // distinct — removes that.  No flags between workgroups, no spinning: the only synchronisation is that atomic and the
 // kernel boundary.
@@ -36,13 +35,12 @@
 
 namespace smafa_nb {
 
-// The piece's list as join_filter_kernel receives it, and its rule: a row is kept iff position(query row) <
-// pos_of[subject].  Every kept row {a, b, d} leaves as two entries at entries[first + 2 * its rank among the kept rows]:
+// A raw piece list under the exactly-once rule (piece.hip.h).  Every kept row {a, b, d} leaves as two entries at the slot
+// piece::block_append gives it and the one behind:
 // shift != 0: (a << shift | d << 32 | b) and (b << shift | d << 32 | a); shift == 0: (d << 32 | b) with rows[] = a, and
 // (d << 32 | a) with rows[] = b.  *total (zeroed by the host once per call) counts every entry; the host has made room for
 // two entries per row of the list in front of the launch, and an entry past cap is counted and not stored all the same.
-// The trip count of the loop is uniform per workgroup and the LDS words alternate by the parity of the iteration, as in
-// smafa_pk::weigh_keep_kernel.
+// The trip count of the loop is uniform per workgroup, so the two barriers of an append are met by all four waves.
 __global__ __launch_bounds__(256) void mirror_pack_kernel(const smafa_hit *__restrict__ list, unsigned long long total_rows,
                                                           uint32_t p0, uint32_t S, uint32_t R,
                                                           const uint32_t *__restrict__ order,
@@ -52,42 +50,28 @@ __global__ __launch_bounds__(256) void mirror_pack_kernel(const smafa_hit *__res
                                                           unsigned long long *total) {
     __shared__ uint32_t s_wave[2][4];
     __shared__ unsigned long long s_first[2];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     uint32_t set = 0;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total_rows; base += stride, set ^= 1u) {
         const unsigned long long i = base + threadIdx.x;
-        uint32_t a = 0, b = 0, d = 0;
+        smafa_hit h = {0, 0, 0};
         bool keep = false;
         if (i < total_rows) {
-            const smafa_hit h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
-            if (keep) a = order[qpos], b = h.subject, d = h.dist;  // (another position than the subject's: another subject number)
+            h = list[i];
+            keep = piece::keep_once(h, p0, S, R, order, pos_of);
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) s_wave[set][wave] = (uint32_t)__builtin_popcountll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t all = s_wave[set][0] + s_wave[set][1] + s_wave[set][2] + s_wave[set][3];
-            s_first[set] = all ? atomicAdd(total, 2ull * all) : 0ull;
-        }
-        __syncthreads();
-        if (keep) {
-            uint32_t rank = smafa::lanes_below(mask);
-            for (uint32_t w = 0; w < wave; w++) rank += s_wave[set][w];
-            const unsigned long long slot = s_first[set] + 2ull * rank;
-            if (slot + 1ull < cap) {
-                const unsigned long long dd = (unsigned long long)d << 32;
-                if (shift) {
-                    entries[slot] = ((unsigned long long)a << shift) | dd | b;
-                    entries[slot + 1] = ((unsigned long long)b << shift) | dd | a;
-                } else {
-                    entries[slot] = dd | b;
-                    entries[slot + 1] = dd | a;
-                    rows[slot] = a;
-                    rows[slot + 1] = b;
-                }
+        const unsigned long long slot = piece::block_append(keep, total, 2u, s_wave, s_first, set);
+        if (keep && slot + 1ull < cap) {
+            const uint32_t a = h.query, b = h.subject;
+            const unsigned long long dd = (unsigned long long)h.dist << 32;
+            if (shift) {
+                entries[slot] = ((unsigned long long)a << shift) | dd | b;
+                entries[slot + 1] = ((unsigned long long)b << shift) | dd | a;
+            } else {
+                entries[slot] = dd | b;
+                entries[slot + 1] = dd | a;
+                rows[slot] = a;
+                rows[slot + 1] = b;
             }
         }
     }

@@ -38,9 +38,8 @@
 //             value can only be too low, and then the atomicMax decides.  atomicMax is idempotent, so climb_kernel is as
 //             correct on a raw piece list — self-pairs, mirror images and (block index) repeats included — as on the kept
 //             list, where each pair appears once in one orientation.
-//   the kept list: ONE reservation per workgroup and loop iteration on the kept total — every wave ballots, the four wave
-//             counts meet in LDS, one lane adds their sum to ctl[0] and the waves take their shares of what it returns.  The
-//             ORDER of the kept rows depends on arrival; nothing that reads them does.
+//   the kept list: piece::block_append on the kept total, ONE reservation per workgroup and loop iteration.  The ORDER of
+//             the kept rows depends on arrival; nothing that reads them does.
 //   the crown one slot, atomicMax of every key, one atomic per wave after a reduction across the lanes: the maximum of a set.
 //   labels[]  jump_kernel: slot i is written by thread i alone, with an ancestor of i in parent[]'s forest — the value it
 //             read at lab[lab[i]].  Whatever a racing thread reads in a slot is therefore an ancestor of that slot's row, old
@@ -76,14 +75,10 @@ __global__ __launch_bounds__(256) void init_peaks_kernel(unsigned long long *__r
     }
 }
 
-// The piece's list as join_filter_kernel receives it, and its rule: a row is kept iff position(query row) <
-// pos_of[subject], which drops self-pairs, mirror images and the block index's repeats.  A kept row within the radius raises
-// both weights; EVERY kept row leaves as {a, b, dist} in subject numbers for kept[first + ...]; rows past cap are counted in
+// A raw piece list under the exactly-once rule (piece.hip.h).  A kept row within the radius raises both weights; EVERY kept
+// row leaves as {a, b, dist} in subject numbers for the kept list through piece::block_append; rows past cap are counted in
 // ctl[0] (the kept total, exact at any capacity; zeroed by the host once per call) and not stored.  The trip count of the
-// loop is uniform per workgroup, so the two barriers of an iteration are met by all four waves.  The LDS words alternate
-// between two sets by the parity of the iteration: a wave that is already publishing its count of iteration k + 1 writes the
-// set that the slower waves, still reading iteration k, do not look at, and nobody reaches iteration k + 2 before everybody
-// has passed the first barrier of k + 1.
+// loop is uniform per workgroup, so the two barriers of an append are met by all four waves.
 __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
                                                          uint32_t p0, uint32_t S, uint32_t R,
                                                          const uint32_t *__restrict__ order,
@@ -92,7 +87,6 @@ __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__rest
                                                          unsigned long long *ctl) {
     __shared__ uint32_t s_wave[2][4];
     __shared__ unsigned long long s_first[2];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     uint32_t set = 0;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride, set ^= 1u) {
@@ -101,42 +95,26 @@ __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__rest
         bool keep = false;
         if (i < total) {
             h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
-            if (keep) {
-                h.query = order[qpos];  // (another position than the subject's: another subject number)
-                if (h.dist <= radius) {
-                    atomicAdd(weight + h.query, 1u);
-                    atomicAdd(weight + h.subject, 1u);
-                }
+            keep = piece::keep_once(h, p0, S, R, order, pos_of);
+            if (keep && h.dist <= radius) {
+                atomicAdd(weight + h.query, 1u);
+                atomicAdd(weight + h.subject, 1u);
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) s_wave[set][wave] = (uint32_t)__builtin_popcountll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t all = s_wave[set][0] + s_wave[set][1] + s_wave[set][2] + s_wave[set][3];
-            s_first[set] = all ? atomicAdd(ctl, (unsigned long long)all) : 0ull;
-        }
-        __syncthreads();
-        if (keep) {
-            unsigned long long slot = s_first[set] + smafa::lanes_below(mask);
-            for (uint32_t w = 0; w < wave; w++) slot += s_wave[set][w];
-            if (slot < cap) kept[slot] = h;
-        }
+        const unsigned long long slot = piece::block_append(keep, ctl, 1u, s_wave, s_first, set);
+        if (keep && slot < cap) kept[slot] = h;
     }
 }
 
-// Phase 2, weight[] final (plain loads).  order != nullptr: a raw piece list, rows {record number of the query row in its
-// span, subject number, dist} as link_rows_kernel receives them; order == nullptr: the kept list, rows {a, b, dist} in
-// subject numbers (p0, S, R unused).  The row of the lower key is offered the higher key.
+// Phase 2, weight[] final (plain loads), over either list form (piece.hip.h: pair_of).  The row of the lower key is offered
+// the higher key.
 __global__ __launch_bounds__(256) void climb_kernel(const smafa_hit *__restrict__ list, unsigned long long total, uint32_t p0,
                                                     uint32_t S, uint32_t R, const uint32_t *__restrict__ order,
                                                     const uint32_t *__restrict__ weight, unsigned long long *best) {
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const smafa_hit h = list[i];
-        const uint32_t a = order ? order[p0 + (h.query % R) * S + h.query / R] : h.query, b = h.subject;
+        const uint32_t a = piece::pair_of(h, p0, S, R, order), b = h.subject;
         if (a == b) continue;
         const unsigned long long ka = key_of(weight[a], a), kb = key_of(weight[b], b);
         const uint32_t lower = ka < kb ? a : b;
@@ -177,8 +155,7 @@ __global__ __launch_bounds__(256) void settle_kernel(const unsigned long long *_
         if (weights) weights[i] = weight[i];
         peak = parent == i;
     }
-    const unsigned long long mask = __ballot(peak);
-    if (peak && smafa::lanes_below(mask) == 0u) atomicAdd(&s_peaks, (uint32_t)__builtin_popcountll(mask));
+    piece::wave_count(peak, &s_peaks);
     __syncthreads();
     if (threadIdx.x == 0u && s_peaks) atomicAdd(n_peaks, (unsigned long long)s_peaks);
 }
@@ -195,8 +172,7 @@ __global__ __launch_bounds__(256) void jump_kernel(uint32_t *lab, uint32_t n, ui
             moved = true;
         }
     }
-    const unsigned long long mask = __ballot(moved);
-    if (moved && smafa::lanes_below(mask) == 0u) __hip_atomic_store(changed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (piece::wave_first(moved)) __hip_atomic_store(changed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace smafa_pk

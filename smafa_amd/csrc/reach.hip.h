@@ -8,12 +8,12 @@
 // edges {a, b, w}, a < b, ordered by w; for every t the edges with w <= t are acyclic and connect exactly the pairs within t
 // whose ends are both core at t — the core rows' clusters of the density call at bound t, for every t from one join.
 // The tenth consumer of a finished piece's scratch list, in a namespace of its own:
-//   tally_keep_kernel   smafa_sf::keep_pairs_kernel's body — per row the exactly-once rule keeps, the row {a, b, dist} moves to the
+//   tally_keep_kernel   smafa_sf::keep_row, keep_pairs_kernel's loop body — per row the exactly-once rule keeps, the row moves to the
 //                       handle's kept pair list while that has room — and, stored or not, the row is tallied at both ends:
 //                       hist[a * E + dist]++, hist[b * E + dist]++ (exact at any capacity of the list, as the density call's degrees)
 //   core_dist_kernel    one lane per subject: the running sum from 1 over the row's E tallies, core[i] = the first t at which it
 //                       reaches min_pts, else `fallback`; the rows that are not sparse are counted
-//   span_reach_kernel   smafa_sf::span_edges_kernel with the weight above: one launch per weight class t, per row with w == t
+//   span_reach_kernel   smafa_sf::span_row, span_edges_kernel's loop body, with the weight above: one launch per class t, per row with w == t
 //                       unite_won(a, b); the lane whose own CAS made the hook writes {min, max, w}
 // smafa_sf::init_forest_kernel, unite_won and star_roots_kernel are used as they are; the union-find is components.hip.h's.
 //
@@ -31,40 +31,26 @@
 
 namespace smafa_mr {
 
-// The piece's list as smafa_sf::keep_pairs_kernel receives it, and its rule: a row is kept iff position(query row) <
-// pos_of[subject].  A kept row {a, b, dist} in subject numbers goes to kept[first + ...], one reservation per wave on ctl[0]
-// (the kept total); rows past cap are counted and not stored.  Every kept row, stored or not, raises hist[a * E + dist] and
-// hist[b * E + dist] (the join ran at bound E - 1: dist < E; the compare keeps a wrong row from writing outside hist[]).
+// Every kept row of smafa_sf::keep_row, stored or not, raises hist[a * E + dist] and hist[b * E + dist] (the join ran at bound
+// E - 1: dist < E; the compare keeps a wrong row from writing outside hist[]).
+struct TallyPerRow {
+    uint32_t *hist;
+    uint32_t E;
+    __device__ __forceinline__ void operator()(const smafa_hit &h) const {
+        if (h.dist < E) {
+            atomicAdd(hist + (size_t)h.query * E + h.dist, 1u);
+            atomicAdd(hist + (size_t)h.subject * E + h.dist, 1u);
+        }
+    }
+};
+
 __global__ __launch_bounds__(256) void tally_keep_kernel(const smafa_hit *__restrict__ list, unsigned long long total, uint32_t p0,
                                                          uint32_t S, uint32_t R, const uint32_t *__restrict__ order,
                                                          const uint32_t *__restrict__ pos_of, smafa_hit *kept, unsigned long long cap,
                                                          unsigned long long *ctl, uint32_t *hist, uint32_t E) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride) {
-        const unsigned long long i = base + threadIdx.x;  // uniform trip count per workgroup
-        smafa_hit h = {0, 0, 0};
-        bool keep = false;
-        if (i < total) {
-            h = list[i];
-            const uint32_t qpos = p0 + (h.query % R) * S + h.query / R;
-            keep = qpos < pos_of[h.subject];
-            if (keep) {
-                h.query = order[qpos];  // (another position than the subject's: another subject number)
-                if (h.dist < E) {
-                    atomicAdd(hist + (size_t)h.query * E + h.dist, 1u);
-                    atomicAdd(hist + (size_t)h.subject * E + h.dist, 1u);
-                }
-            }
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(ctl, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
-        if (keep && slot < cap) kept[slot] = h;
-    }
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;  // (uniform trip count per workgroup)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride)
+        smafa_sf::keep_row(list, total, base + threadIdx.x, p0, S, R, order, pos_of, kept, cap, ctl, TallyPerRow{hist, E});
 }
 
 // Behind the join every tally is final (the kernel boundary; plain loads).  ball(i, t) = 1 + hist[i * E + 0 .. t]; core[i] = the
@@ -94,41 +80,22 @@ __global__ __launch_bounds__(256) void core_dist_kernel(const uint32_t *__restri
     if (mask != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_dense, (unsigned long long)__builtin_popcountll(mask));
 }
 
-// One weight class: the rows with max(dist, core[a], core[b]) == only_dist, all others pass by — a row with dist > only_dist
-// before any gather, because w >= dist.  The two list forms of smafa_sf::span_edges_kernel: order != nullptr, a raw piece list;
-// order == nullptr, the kept list in subject numbers.  SMAFA_NONE (a sparse end) matches no class.  Self-pairs are skipped, equal
-// parents are one set already, and a lane that won writes {min, max, w} to edges[first + ...], one reservation per wave on
-// *n_edges; cap = n - 1 is never reached (forest.hip.h), the compare keeps a wrong parent[] from writing past the caller's buffer.
+// The rows with max(dist, core[a], core[b]) == t for smafa_sf::span_row — a row with dist > t passes by before any gather,
+// because w >= dist.  SMAFA_NONE (a sparse end) matches no class.
+struct ReachClass {
+    const uint32_t *__restrict__ core;
+    uint32_t t;
+    __device__ __forceinline__ bool maybe(uint32_t dist) const { return dist <= t; }
+    __device__ __forceinline__ bool is(uint32_t dist, uint32_t a, uint32_t b) const { return max(dist, max(core[a], core[b])) == t; }
+};
+
 __global__ __launch_bounds__(256) void span_reach_kernel(const smafa_hit *__restrict__ list, unsigned long long total, uint32_t p0,
                                                          uint32_t S, uint32_t R, const uint32_t *__restrict__ order,
                                                          const uint32_t *__restrict__ core, uint32_t *parent, uint32_t only_dist,
                                                          smafa_hit *edges, unsigned long long cap, unsigned long long *n_edges) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride) {
-        const unsigned long long i = base + threadIdx.x;  // uniform trip count per workgroup
-        smafa_hit h = {0, 0, 0};
-        bool won = false;
-        if (i < total) {
-            h = list[i];
-            if (h.dist <= only_dist) {
-                const uint32_t a = order ? order[p0 + (h.query % R) * S + h.query / R] : h.query, b = h.subject;
-                if (a != b && max(h.dist, max(core[a], core[b])) == only_dist &&
-                    smafa_cc::load_parent(parent, a) != smafa_cc::load_parent(parent, b))
-                    won = smafa_sf::unite_won(parent, a, b);
-                h.query = min(a, b);
-                h.subject = max(a, b);
-                h.dist = only_dist;
-            }
-        }
-        const unsigned long long mask = __ballot(won);
-        if (mask == 0ull) continue;
-        unsigned long long first = 0;
-        if (lane == 0) first = atomicAdd(n_edges, (unsigned long long)__builtin_popcountll(mask));
-        first = smafa::shfl_u64(first, 0);
-        const unsigned long long slot = first + smafa::lanes_below(mask);
-        if (won && slot < cap) edges[slot] = h;
-    }
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;  // (uniform trip count per workgroup)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < total; base += stride)
+        smafa_sf::span_row(list, total, base + threadIdx.x, p0, S, R, order, parent, edges, cap, n_edges, ReachClass{core, only_dist});
 }
 
 }  // namespace smafa_mr

@@ -6,6 +6,9 @@
 // over delta_pass.  A call is a JoinCall between join_begin and join_finish with one
 // or more JoinConsumers: timed_consumer (a kernel per piece), watching (that, gated on a device counter read at every wait),
 // keeping_consumer (that, with J.kept grown by the gate).  Their C ABI is self_join_abi.hip.h.
+// What the calls share behind the join: read_ctl (the totals of J.ctl and the wait that brings them), kept_plan and kept_piece (the
+// kept list read once, or the store joined again), join_flatten (the last launch, waited for), and for the two forests span_classes
+// (the weight classes one after another, over either list form) and star_roots.  What their kernels share is piece.hip.h.
 // Included once by engine.hip, inside namespace smafa, behind smafa_db and scan_range.
 #pragma once
 
@@ -86,8 +89,14 @@ static int timed_sync(JoinCall &c) {
         *c.slot += ms;
         if (c.what) log_line(3, "%s, %.3f ms", c.what, ms);
     }
-    c.slot = nullptr;
+    c.slot = nullptr, c.what = nullptr;
     return SMAFA_OK;
+}
+
+// the first `words` totals of J.ctl for the host, and the wait that brings them
+static int read_ctl(JoinCall &c, unsigned long long *out, size_t words) {
+    HIP_TRY(hipMemcpyAsync(out, c.db->join.ctl.p, words * sizeof *out, hipMemcpyDeviceToHost, c.db->stream));
+    return timed_sync(c);
 }
 
 // What every call starts with: the statistics of the call before forgotten, `counters` zeros behind d_count, and — unless
@@ -580,8 +589,7 @@ static int join_density(smafa_db *db, uint32_t max_div, uint32_t min_pts, uint32
         RC_TRY(join_positions(c));
         RC_TRY(join_pass(c, max_div, count));
         unsigned long long ctl[2] = {0, 0};  // every degree is final: the kept total; "some row is core"
-        HIP_TRY(hipMemcpyAsync(ctl, J.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, db->stream));
-        RC_TRY(timed_sync(c));
+        RC_TRY(read_ctl(c, ctl, 2));
         // (no core row: nothing to link, every row keeps the set and the attach[] it was given)
         const KeptPlan plan = min_pts > 1u && !ctl[1] ? kKeptNothing : kept_plan(db, ctl[0], "density", "link");
         if (plan == kKeptOnce) RC_TRY(consume(link, kept_piece(db, ctl[0])));
@@ -674,8 +682,7 @@ static int join_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t 
         RC_TRY(join_pass(c, scan_div, weigh));
     }
     unsigned long long kept_total = 0;
-    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
-    RC_TRY(timed_sync(c));
+    RC_TRY(read_ctl(c, &kept_total, 1));
     // every weight is final: the rows' own keys — or the crown — and the climb over the kept list, if that has every pair, in ONE
     // timed pass (its trace text: the last kind of pass that ran)
     const KeptPlan plan = crowned ? kKeptNothing : kept_plan(db, kept_total, "peaks", "climb");
@@ -750,8 +757,7 @@ static int join_chimeras(smafa_db *db, uint32_t max_div, uint32_t radius, uint32
         RC_TRY(join_pass(c, scan_div, weigh));
     }
     unsigned long long kept_total = 0;
-    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
-    RC_TRY(timed_sync(c));
+    RC_TRY(read_ctl(c, &kept_total, 1));
     // every counted weight is final: the caller's weights over them, the empty slots, and the offers over the kept list, if that has
     // every pair, in ONE timed pass
     const KeptPlan plan = kept_plan(db, kept_total, "chimeras", "offer");
@@ -862,8 +868,7 @@ static int join_neighbours(smafa_db *db, uint32_t max_div, uint32_t k, unsigned 
     });
     RC_TRY(join_pass(c, scan_div, pack));
     unsigned long long entries = 0, total = 0;
-    HIP_TRY(hipMemcpyAsync(&entries, J.ctl.p, sizeof entries, hipMemcpyDeviceToHost, db->stream));
-    RC_TRY(timed_sync(c));
+    RC_TRY(read_ctl(c, &entries, 1));
     if (entries > kSortItemsMax) return too_many(entries);
     const unsigned long long *sorted = nullptr, *lower = d_offsets;
     const uint32_t *rows = nullptr;
@@ -942,6 +947,54 @@ static int join_neighbours(smafa_db *db, uint32_t max_div, uint32_t k, unsigned 
     return SMAFA_OK;
 }
 
+// The span phase of the two forests (`who`: "forest" or "reach", for the texts): the weight classes 0 .. E - 1 one after another,
+// a kernel boundary between two classes.  only_dist is the caller's, the class that launch_span and `span` (the consumer made of
+// it) handle.  kKeptOnce: E launches over the kept list in one timed pass; kKeptJoinAgain: the store joined once more PER CLASS,
+// at bound t with the raw piece lists spanned at only_dist = t (every pair of class t is within t).  Behind class t the running
+// edge total is copied into level_ends[t] on the stream — behind the class's last launch, in front of the next class's first.
+// A wait ends the phase.
+template <class Launch>
+static int span_classes(JoinCall &c, const char *who, uint32_t E, unsigned long long kept_total, KeptPlan plan, JoinConsumer &span,
+                        Launch launch_span, uint32_t &only_dist, unsigned long long *d_level_ends, const unsigned long long *n_edges) {
+    smafa_db *db = c.db;
+    const auto end_class = [&] {
+        HIP_TRY(hipMemcpyAsync(d_level_ends + only_dist, n_edges, sizeof(unsigned long long), hipMemcpyDeviceToDevice, db->stream));
+        return SMAFA_OK;
+    };
+    char what[64];  // (read by the wait below, which forgets it)
+    snprintf(what, sizeof what, "%s: the kept list spanned, class by class", who);
+    if (plan == kKeptOnce) {
+        RC_TRY(timed_begin(c, &db->join.link_ms, what));
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            launch_span(kept_piece(db, kept_total));
+            RC_TRY(end_class());
+        }
+        RC_TRY(timed_end(c, E));
+        span.used = true;
+    } else if (plan == kKeptJoinAgain) {
+        log_line(2, "%s: %llu pairs, the kept list holds %llu: the store is joined once more per class, at the bounds 0 .. %u", who,
+                 kept_total, (unsigned long long)kept_room(db), E - 1u);
+        for (only_dist = 0; only_dist < E; only_dist++) {
+            RC_TRY(join_pass(c, only_dist, span));
+            RC_TRY(end_class());
+        }
+    }
+    return timed_sync(c);
+}
+
+// Bounds no two rows can exceed, behind the last class: star_roots_kernel hangs every surviving root under row 0 and fills
+// level_ends[L ..], waited for.
+static int star_roots(JoinCall &c, const char *what, const uint32_t *parent, smafa_hit *d_edges, unsigned long long *n_edges,
+                      unsigned long long *d_level_ends, uint32_t n_levels) {
+    smafa_db *db = c.db;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(timed_pass(c, &db->join.flatten_ms, what, [&] {
+        hipLaunchKernelGGL(smafa_sf::star_roots_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n, db->L, d_edges,
+                           (unsigned long long)(n - 1u), n_edges, d_level_ends, n_levels);
+    }));
+    return timed_sync(c);
+}
+
 // smafa_db_self_forest_launch (forest.hip.h): d_edges is n - 1 rows, d_level_ends max_div + 1 counters, J.parent one union-find,
 // J.ctl the kept total and the running edge total.  The join runs ONCE at bound E - 1 (E = min(max_div, L - 1) + 1 scanned
 // classes, as join_levels) with keep_pairs_kernel per piece (the exactly-once rule, so pos_of[]), which only moves the kept
@@ -978,40 +1031,13 @@ static int join_forest(smafa_db *db, uint32_t max_div, smafa_hit *d_edges, unsig
         hipLaunchKernelGGL(smafa_sf::span_edges_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
                            p.order, parent, only_dist, d_edges, room, n_edges);
     };
-    const auto end_class = [&] {  // (stream-ordered: behind the class's last launch, in front of the next class's first)
-        HIP_TRY(hipMemcpyAsync(d_level_ends + only_dist, n_edges, sizeof(unsigned long long), hipMemcpyDeviceToDevice, db->stream));
-        return SMAFA_OK;
-    };
     JoinConsumer span = timed_consumer(c, &J.link_ms, "forest: a class of a piece's rows spanned", launch_span);
     RC_TRY(join_pass(c, scan_div, keep));
     unsigned long long kept_total = 0;
-    HIP_TRY(hipMemcpyAsync(&kept_total, J.ctl.p, sizeof kept_total, hipMemcpyDeviceToHost, db->stream));
-    RC_TRY(timed_sync(c));
-    const KeptPlan plan = kept_plan(db, kept_total, "forest", "span");
-    if (plan == kKeptOnce) {
-        RC_TRY(timed_begin(c, &J.link_ms, "forest: the kept list spanned, class by class"));
-        for (only_dist = 0; only_dist < E; only_dist++) {
-            launch_span(kept_piece(db, kept_total));
-            RC_TRY(end_class());
-        }
-        RC_TRY(timed_end(c, E));
-        span.used = true;
-    } else if (plan == kKeptJoinAgain) {
-        log_line(2, "forest: %llu pairs, the kept list holds %llu: the store is joined once more per class, at the bounds 0 .. %u",
-                 kept_total, (unsigned long long)kept_room(db), scan_div);
-        for (only_dist = 0; only_dist < E; only_dist++) {
-            RC_TRY(join_pass(c, only_dist, span));
-            RC_TRY(end_class());
-        }
-    }
-    RC_TRY(timed_sync(c));
-    if (all_near) {
-        RC_TRY(timed_pass(c, &J.flatten_ms, "forest: the surviving roots hung under row 0", [&] {
-            hipLaunchKernelGGL(smafa_sf::star_roots_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n, db->L, d_edges, room, n_edges,
-                               d_level_ends, n_levels);
-        }));
-        RC_TRY(timed_sync(c));
-    }
+    RC_TRY(read_ctl(c, &kept_total, 1));
+    RC_TRY(span_classes(c, "forest", E, kept_total, kept_plan(db, kept_total, "forest", "span"), span, launch_span, only_dist, d_level_ends,
+                        n_edges));
+    if (all_near) RC_TRY(star_roots(c, "forest: the surviving roots hung under row 0", parent, d_edges, n_edges, d_level_ends, n_levels));
     join_finish(c);
     note_call_kernel(db, "smafa_sf::init_forest_kernel");
     if (keep.used) note_call_kernel(db, "smafa_sf::keep_pairs_kernel");
@@ -1069,10 +1095,6 @@ static int reach_passes(JoinCall &c, uint32_t max_div, uint32_t min_pts, smafa_h
         hipLaunchKernelGGL(smafa_mr::span_reach_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R,
                            p.order, core, parent, only_dist, d_edges, room, n_edges);
     };
-    const auto end_class = [&] {  // (stream-ordered: behind the class's last launch, in front of the next class's first)
-        HIP_TRY(hipMemcpyAsync(d_level_ends + only_dist, n_edges, sizeof(unsigned long long), hipMemcpyDeviceToDevice, db->stream));
-        return SMAFA_OK;
-    };
     JoinConsumer span = timed_consumer(c, &J.link_ms, "reach: a class of a piece's rows spanned", launch_span);
     RC_TRY(join_pass(c, scan_div, tally));
     RC_TRY(timed_pass(c, &J.filter_ms, "reach: the core distances", [&] {
@@ -1080,35 +1102,12 @@ static int reach_passes(JoinCall &c, uint32_t max_div, uint32_t min_pts, smafa_h
                            all_near ? db->L : SMAFA_NONE, core, d_cores, n_dense);
     }));
     unsigned long long totals[2] = {0, 0};  // every tally is final: the kept total; the rows that are not sparse
-    HIP_TRY(hipMemcpyAsync(totals, J.ctl.p, sizeof totals, hipMemcpyDeviceToHost, db->stream));
-    RC_TRY(timed_sync(c));
+    RC_TRY(read_ctl(c, totals, 2));
     const unsigned long long kept_total = totals[0];
     // (fewer than two rows that are not sparse: no pair has a weight)
     const KeptPlan plan = totals[1] < 2 ? kKeptNothing : kept_plan(db, kept_total, "reach", "span");
-    if (plan == kKeptOnce) {
-        RC_TRY(timed_begin(c, &J.link_ms, "reach: the kept list spanned, class by class"));
-        for (only_dist = 0; only_dist < E; only_dist++) {
-            launch_span(kept_piece(db, kept_total));
-            RC_TRY(end_class());
-        }
-        RC_TRY(timed_end(c, E));
-        span.used = true;
-    } else if (plan == kKeptJoinAgain) {
-        log_line(2, "reach: %llu pairs, the kept list holds %llu: the store is joined once more per class, at the bounds 0 .. %u",
-                 kept_total, (unsigned long long)kept_room(db), scan_div);
-        for (only_dist = 0; only_dist < E; only_dist++) {
-            RC_TRY(join_pass(c, only_dist, span));
-            RC_TRY(end_class());
-        }
-    }
-    RC_TRY(timed_sync(c));
-    if (all_near) {
-        RC_TRY(timed_pass(c, &J.flatten_ms, "reach: the surviving roots hung under row 0", [&] {
-            hipLaunchKernelGGL(smafa_sf::star_roots_kernel, row_grid(n), dim3(256), 0, db->stream, parent, n, db->L, d_edges, room, n_edges,
-                               d_level_ends, n_levels);
-        }));
-        RC_TRY(timed_sync(c));
-    }
+    RC_TRY(span_classes(c, "reach", E, kept_total, plan, span, launch_span, only_dist, d_level_ends, n_edges));
+    if (all_near) RC_TRY(star_roots(c, "reach: the surviving roots hung under row 0", parent, d_edges, n_edges, d_level_ends, n_levels));
     run = {scan_div, all_near, tally.used, span.used, kept_total, totals[1]};
     return SMAFA_OK;
 }

@@ -9,7 +9,8 @@ of the six older self-join calls on any build of the library — profiles/r17_de
                 built block index: after a warm-up, 3 alternated runs timed by the wall clock around the launch form and a
                 sync, nothing else inside the timed region; then 3 alternated runs under the level-2 trace, untimed, for the
                 gather / scans / filter milliseconds.  Checked per store: the delta call at first_row = 0 counts what the full
-                call counts, and every run repeats its warm-up's count.
+                call counts, and every run repeats its warm-up's count.  --stores related: synth.related_subjects(families,
+                100, div 0..0.08) at bound 5 in their place, where pairs dominate and the filter stage has work.
   --part old    one library (SMAFA_AMD_LIB, or this tree's) through ctypes alone, so that a build of the PARENT commit runs
                 the very same script: the six older calls — pairs (count only), components, levels, density, peaks,
                 neighbours — in their launch forms on the ONE-APPEND bench stores, 3 alternated runs each after a warm-up.
@@ -53,10 +54,14 @@ def part_run(args):
     lib = _lib.lib()
     d_count = torch.zeros(1, dtype=torch.int64, device="cuda")
     cases = [(int(m), False) for m in args.new.split(",")] + [(args.sorted_rows, True)]
-    for name, alphabet, D in (("aa", 1, 5), ("nt", 0, 3)):
+    # related: synth.related_subjects(families, 100, div 0..0.08) at bound 5, where pairs dominate and the filter stage has work
+    for name, alphabet, D in (("aa", 1, 5), ("nt", 0, 3), ("related", 1, 5)):
         if name not in args.stores.split(","):
             continue
-        codes = synth.subjects(args.rows, 60, alphabet)
+        if name == "related":
+            codes = synth.related_subjects(args.families, 100, div_lo=0.0, div_hi=0.08)
+        else:
+            codes = synth.subjects(args.rows, 60, alphabet)
         n = len(codes)
         for m, in_order in cases:
             if m <= 0 or m > n:
@@ -240,6 +245,7 @@ def main():
     ap.add_argument("--json", default="delta_probe.jsonl")
     ap.add_argument("--stores", default="aa,nt")
     ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--families", type=int, default=10_000)
     ap.add_argument("--new", default="10000,100000,1000000")
     ap.add_argument("--sorted-rows", type=int, default=100_000)
     ap.add_argument("--label", default="this")

@@ -4,7 +4,7 @@
                  the very same script.  Stores (--stores, comma separated): aa / nt — the bench's 10M x 60 stores
                  (smafa_amd.synth.subjects; amino acids at bound 5, nucleotides at bound 3); related —
                  synth.related_subjects(families, 100, div 0..0.08) at bound 5, where pairs dominate; dense — the 4 000-row
-                 store of the tests at bound 3.  Per store, after a warm-up, 3 rounds of: the components call at D, the
+                 store of the tests at bound 3 (--bound: another bound, e.g. 60 on the dense store for the star stage).  Per store, after a warm-up, 3 rounds of: the components call at D, the
                  levels call (the yardstick: the same single join) and — where the library has it — the forest call, and
                  once the forest call of a handle made under SMAFA_DENSITY_KEEP_MAX=0 (the slow path: one more join per
                  class).  Wall clock around call + smafa_sync, and the stage times of the library's level-2 trace line; one
@@ -83,6 +83,8 @@ def part_run(args):
         else:
             alphabet, D = 0, 3
             codes = dense_store()[0]
+        if args.bound is not None:  # (a bound >= the rows' length: the star stage)
+            D = args.bound
         n = len(codes)
         db = make(codes, alphabet)
         d_counts = torch.zeros(D + 1, dtype=torch.int64, device="cuda")
@@ -182,6 +184,7 @@ def main():
     ap.add_argument("--stores", default="aa,nt,related,dense")
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--families", type=int, default=10_000)
+    ap.add_argument("--bound", type=int, help="this bound in place of the store's own")
     ap.add_argument("--label", default="this", help="which library this is: this / parent")
     ap.add_argument("--json", required=True)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_forest.txt"))

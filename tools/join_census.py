@@ -1,4 +1,4 @@
-"""Launch census of the nine self-join calls: launches, scans and the kernel list of smafa_last_call_stats /
+"""Launch census of the twelve self-join calls: launches, scans and the kernel list of smafa_last_call_stats /
 smafa_last_call_kernels, per call and case — tests/join_launch_census.json, which tests/test_gpu_join_launch_census.py holds
 this tree against.
 
@@ -29,7 +29,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 CALLS = ["pairs", "components", "levels", "density", "peaks"]  # recorded from the commit before the driver/consumer split
 NEWER_CALLS = ["neighbours", "forest", "pairs_since", "components_update"]  # recorded later (--calls), each from its own parent
-ALL_CALLS = CALLS + NEWER_CALLS
+ALL_CALLS = CALLS + NEWER_CALLS  # (the nine of the tables recorded before piece.hip.h: a test of those commits runs these)
+NEWEST_CALLS = ["reach_forest", "stable", "chimeras"]  # recorded from the commit before the kernels' shared pieces (piece.hip.h)
+EVERY_CALL = ALL_CALLS + NEWEST_CALLS
 KNOBS = ["SMAFA_JOIN_BLOCK", "SMAFA_JOIN_STRIDE", "SMAFA_JOIN_SCRATCH_MAX", "SMAFA_DENSITY_KEEP_MAX", "SMAFA_NEIGHBOUR_SORT"]
 NONE = 0xFFFFFFFF  # SMAFA_NONE
 
@@ -86,6 +88,9 @@ def load(path):
     lib.smafa_db_self_peaks.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
     lib.smafa_db_self_neighbours.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
     lib.smafa_db_self_forest.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_reach_forest.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp]
+    lib.smafa_db_self_stable.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]
+    lib.smafa_db_self_chimeras.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
     lib.smafa_db_self_hits_since.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
     lib.smafa_db_self_components_update.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]
     lib.smafa_last_call_stats.argtypes = [vp, C.POINTER(C.c_float), u32p, u32p]
@@ -142,6 +147,13 @@ def census(lib, call):
             elif call == "forest":
                 edges = np.zeros((max(n, 2) - 1, 3), dtype=np.uint32)
                 ok(lib.smafa_db_self_forest(h, D, edges.ctypes.data, len(edges), counts))
+            elif call == "reach_forest":  # min_pts 3, as the density call's; the cores too
+                edges = np.zeros((max(n, 2) - 1, 3), dtype=np.uint32)
+                ok(lib.smafa_db_self_reach_forest(h, D, 3, edges.ctypes.data, len(edges), counts, extra[0].ctypes.data))
+            elif call == "stable":  # min_pts 3, min_cluster_size 2; neither the joined levels nor the cores
+                ok(lib.smafa_db_self_stable(h, D, 3, 2, labels.ctypes.data, None, None, n, counts))
+            elif call == "chimeras":  # counted weights at the peaks call's radius, fold 2, the flags alone
+                ok(lib.smafa_db_self_chimeras(h, D, radius, 2, None, labels.ctypes.data, None, None, None, None, None, n, counts))
             elif call == "pairs_since":  # no room for rows, as pairs
                 ok(lib.smafa_db_self_hits_since(h, n // 2, D, None, 0, counts), allowed=(-3,))
             else:
@@ -169,9 +181,9 @@ def main():
     lib = load(path)
     build = lib.smafa_build_id().decode()
     named = args.calls.split(",") if args.calls else CALLS
-    unknown = sorted(set(named) - set(ALL_CALLS))
+    unknown = sorted(set(named) - set(EVERY_CALL))
     if unknown:
-        raise SystemExit("join_census: no such call: %s (there are: %s)" % (", ".join(unknown), ", ".join(ALL_CALLS)))
+        raise SystemExit("join_census: no such call: %s (there are: %s)" % (", ".join(unknown), ", ".join(EVERY_CALL)))
     if args.calls:
         if not os.path.exists(args.out):
             raise SystemExit("join_census: --calls merges into %s, which is not there; record the whole table first" % args.out)
