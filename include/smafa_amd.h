@@ -772,6 +772,66 @@ int smafa_db_self_components_update(smafa_db *db, uint64_t first_row, uint32_t m
 int smafa_db_consensus_launch(smafa_db *db, const void *d_labels, void *d_ids, void *d_sizes, void *d_codes, void *d_nearest /* may be NULL */, void *d_div /* may be NULL */, uint64_t cap_clusters, uint64_t *n_clusters /* host */);
 int smafa_db_consensus(smafa_db *db, const uint32_t *labels, uint32_t *ids, uint32_t *sizes, uint8_t *codes, uint32_t *nearest, uint32_t *div, uint64_t cap_clusters, uint64_t *n_clusters);
 
+/* ------------------------------------------------- abundance table: reads assigned to their nearest subject and counted */
+/*
+ * The last step of an amplicon pipeline: the reads of every sample mapped back to the kept sequences and counted, cluster x
+ * sample (`usearch -otutab`, DADA2's sequence table).  Not in the reference.
+ * Inputs: the store's n subjects; m reads (a resident query set, or code rows); a bound max_div; per subject a label (uint32, any
+ * value; labels NULL: a subject's label is its own number); per read a sample number below n_samples (samples NULL: every read is
+ * in sample 0; n_samples >= 1) and a weight (uint32; weights NULL: every read weighs 1 — for dereplicated reads with sizes).
+ *   A read is ASSIGNED to the subject at the smallest distance <= max_div, a tie to the smaller subject number (`smafa cluster`'s
+ *   argmin rule): subject[q] is that number and dist[q] its distance.  With no subject within the bound, or an empty store, both
+ *   are SMAFA_NONE and the read is UNASSIGNED.
+ *   A read's label is the label of its subject; an unassigned read has the label SMAFA_NONE — the same "in no cluster" as a noise
+ *   label, as in smafa_db_consensus.
+ *   The TABLE: one entry {label, sample, count} per (label, sample) that holds at least one read of weight > 0, count the uint64
+ *   sum of those reads' weights, ordered by (label, sample) ascending — SMAFA_NONE comes last.
+ *   subject_counts[i] (uint64, optional) = the weight of all reads assigned to subject i, over all samples: what
+ *   `smafa chimeras --weights` takes.
+ *   totals[0] = the number of entries, [1] = the assigned weight, [2] = the unassigned weight, [3] = the number of reads whose
+ *   sample number is >= n_samples.  Those reads take no part in anything else: they are in no entry, no subject count and no
+ *   weight total (subject[] and dist[], which count nothing, are written for them as for any read).
+ * The answer is an exact integer function of the inputs: the same bytes from run to run and under smafa_set_prefilter /
+ * smafa_set_zone_level / smafa_set_index and every SMAFA_ASSIGN_* setting.
+ *
+ * Checks, in this order, each SMAFA_ERR_INVALID with the argument named in smafa_last_error() and nothing written: a NULL handle;
+ * a NULL query set (host form: NULL query_codes with n_queries > 0); NULL totals; max_div = SMAFA_NONE; n_samples = 0; NULL
+ * entries with cap > 0; (launch form) a query set packed for another store; (host form) code bytes outside the alphabet, then a
+ * sample number >= n_samples — checked on the host before any device work, the text names the first such read.  Behind the
+ * checks totals[] is zeroed — the launch form's first enqueued operation, the host form's first store — and every other output
+ * is written only by a call that succeeds.
+ *
+ * On the device (assign.hip.h): the reads go in spans of SMAFA_ASSIGN_SPAN (read when the handle is made; default 65 536, whole
+ * 64s).  Each span is scanned as smafa_scan_launch(max_div, max_num_hits = 1) scans it — the rows are the subjects at each read's
+ * minimum distance — into the handle's row list; where a span's rows do not fit, the list grows, doubling, up to
+ * SMAFA_ASSIGN_ROWS_MAX rows (default: SMAFA_JOIN_SCRATCH_MAX's value), then the span is halved.  Only where 64 reads alone
+ * overflow that limit — a store of millions of exact copies — the call fails: SMAFA_ERR_NOMEM, the count in smafa_last_error(),
+ * and the handle stays usable.  One lane per row then takes the 64-bit minimum of (dist << 32 | subject) per read; one lane per
+ * read looks the label up and writes a (label, sample) key and its weight; the device radix sort orders the m pairs over the
+ * key bits in use; the first element of each run of equal keys is marked, an exclusive sum numbers the entries and a segmented
+ * sum across each wave adds the weights, one 64-bit atomic per run and wave.  Reads of weight 0 get a key behind every other
+ * and are cut off with the tail.  Fewer than 2^31 reads per call (the device sort's item limit).  Handle-owned scratch: 36 B per
+ * read besides the row list.
+ *
+ * smafa_db_assign_launch: device-resident form.  d_labels = n_subjects uint32 or NULL; d_samples, d_weights = n_queries uint32 or
+ * NULL; d_subject, d_dist = n_queries uint32 or NULL (not wanted); d_subject_counts = n_subjects uint64 or NULL; d_entries = cap
+ * smafa_table_entry (NULL with cap = 0 counts only); d_totals = 4 uint64.  totals[0] is exact at any capacity and the first cap
+ * entries IN TABLE ORDER are stored; the entries from totals[0] up to min(cap, n_queries) are zeroed, none behind that is touched.  Like smafa_db_self_launch the call synchronises the handle's stream between its spans and
+ * once at its end.  smafa_last_scan_ms / smafa_last_call_stats hold the device time and launches of all its spans and of its own
+ * passes; smafa_last_call_kernels lists the scan-family instantiations the call launched, then assign::init_kernel,
+ * best_kernel (some row was listed), bin_kernel, heads_kernel and fold_kernel (no read at all: init_kernel alone).
+ *
+ * smafa_db_assign: host form; it makes and destroys a query set of its own.  More than cap entries: SMAFA_ERR_CAPACITY, totals[]
+ * written (totals[0] = the entries needed), nothing else; nothing is kept for the retry.
+ */
+typedef struct {
+    uint32_t label;
+    uint32_t sample;
+    uint64_t count;
+} smafa_table_entry;
+int smafa_db_assign_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, const void *d_labels /* n_subjects uint32, may be NULL */, const void *d_samples /* n_queries uint32, may be NULL */, uint32_t n_samples, const void *d_weights /* n_queries uint32, may be NULL */, void *d_subject /* n_queries uint32, may be NULL */, void *d_dist /* n_queries uint32, may be NULL */, void *d_subject_counts /* n_subjects uint64, may be NULL */, void *d_entries /* cap smafa_table_entry; NULL with cap == 0 counts only */, uint64_t cap, void *d_totals /* 4 uint64 */);
+int smafa_db_assign(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div, const uint32_t *labels, const uint32_t *samples, uint32_t n_samples, const uint32_t *weights, uint32_t *subject, uint32_t *dist, uint64_t *subject_counts, smafa_table_entry *entries, uint64_t cap, uint64_t totals[4]);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -955,6 +1015,17 @@ int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, i
  * form, a second line for one subject or a subject number the DB does not have is SMAFA_ERR_INVALID with a text that names the
  * line (exit status 1).  An empty DB prints nothing. */
 int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius, uint32_t min_fold, const char *weights_path, int out_fd, int device);
+/* `smafa table` (not in the reference): the same DB, the reads of a FASTA/FASTQ(+gzip) file — of the store's length, or the call
+ * fails as smafa_query does — and smafa_db_assign at max_divergence.  labels_path (or NULL: a subject's label is its own number):
+ * the file `smafa consensus` reads, except that the file may end early — a subject without a line has label -1.  samples_path and
+ * weights_path (or NULL): "{read}\t{value}[\t...]\n" lines over read numbers, in any order; a read without a line is in sample 0 /
+ * weighs 1; n_samples = the largest sample number + 1.  "-" is stdin for at most one of the three.  A line that is not of that
+ * form, a second line for one read or a read number the file does not have is SMAFA_ERR_INVALID with a text that names the line.
+ * Output: "{label}\t{sample}\t{count}\n" per entry in table order, -1 for SMAFA_NONE; per_read != 0: "{read}\t{subject}\t{dist}\n"
+ * per read instead, -1 in both columns for an unassigned read; per_sequence != 0: "{i}\t{count}\n" per subject
+ * (subject_counts: what `smafa chimeras --weights -` reads).  per_read and per_sequence together are SMAFA_ERR_INVALID.  An empty
+ * DB prints nothing. */
+int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_divergence, const char *labels_path, const char *samples_path, const char *weights_path, int per_read, int per_sequence, int out_fd, int device);
 /* `smafa neighbours` (not in the reference): the same DB, and per subject its neighbours within max_divergence, nearest first,
  * at most max_num_hits of them (SMAFA_NONE: all) — smafa_db_self_neighbours, a degrees-only call and then the sized one —
  * "{i}\t{j}\t{dist}\n" per entry, both directions of every pair, ordered by (i, dist, j).  An empty DB prints nothing. */

@@ -21,6 +21,11 @@ from ._lib import ALPHABET_AA, ALPHABET_NT, NONE, Hit, SmafaError, SmafaPanic, c
 HIT_DTYPE = np.dtype([("query", "<u4"), ("subject", "<u4"), ("dist", "<u4")])
 # what SubjectStore.self_chimeras returns: six uint32 arrays, one entry per subject, and the number of flagged rows
 Chimeras = collections.namedtuple("Chimeras", "flags left_parent left_len right_parent right_len weights n_chimeras")
+# one entry of the abundance table (smafa_table_entry), and what SubjectStore.assign returns: the entries in table order, per read
+# its subject and distance (or None), per subject the weight assigned to it (or None), and the four totals
+TABLE_DTYPE = np.dtype([("label", "<u4"), ("sample", "<u4"), ("count", "<u8")])
+TableEntry = TABLE_DTYPE
+Assigned = collections.namedtuple("Assigned", "entries subject dist subject_counts totals")
 
 
 def _opt(v: Optional[int]) -> int:
@@ -541,6 +546,59 @@ class SubjectStore:
         check(rc)
         return int(count.value)
 
+    # ---- abundance table ------------------------------------------------------------------------
+    def assign(self, query_codes, max_divergence: int, labels=None, samples=None, n_samples: Optional[int] = None, weights=None,
+               per_read: bool = True, subject_counts: bool = False) -> Assigned:
+        """(entries, subject, dist, subject_counts, totals) — smafa_db_assign: every read assigned to the subject at the smallest
+        distance <= max_divergence (a tie to the smaller number; NONE where there is none) and counted.  labels (uint32,
+        n_subjects; None: a subject's label is its own number), samples (uint32 per read; None: sample 0), n_samples (default:
+        max(samples) + 1), weights (uint32 per read; None: 1).  entries (TABLE_DTYPE) holds one {label, sample, count} per (label,
+        sample) with a read of weight > 0, ordered by (label, sample), NONE last; subject, dist (uint32 per read; per_read=False:
+        None); subject_counts (uint64 per subject, where asked for); totals = [entries, assigned weight, unassigned weight, reads
+        with a sample number out of range].  Grows the entry buffer and calls again on ERR_CAPACITY."""
+        q = np.ascontiguousarray(query_codes, dtype=np.uint8).reshape(-1, self.seq_len)
+        m, n = q.shape[0], len(self)
+
+        def given(a, count, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.uint32)
+            if a.shape != (count,):
+                raise ValueError(f"{what} has shape {a.shape}, expected ({count},)")
+            return a
+
+        labels, samples, weights = given(labels, n, "labels"), given(samples, m, "samples"), given(weights, m, "weights")
+        if n_samples is None:
+            n_samples = int(samples.max()) + 1 if samples is not None and m else 1
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        subject = np.full(m, NONE, dtype=np.uint32) if per_read else None
+        dist = np.full(m, NONE, dtype=np.uint32) if per_read else None
+        counts = np.zeros(n, dtype=np.uint64) if subject_counts else None
+        totals = np.zeros(4, dtype=np.uint64)
+        cap = min(m, 1 << 16)
+        while True:
+            entries = np.zeros(cap, dtype=TABLE_DTYPE)
+            rc = lib().smafa_db_assign(self._h, q.ctypes.data if m else None, m, _opt(max_divergence), ptr(labels),
+                                       samples.ctypes.data if samples is not None else None, int(n_samples),
+                                       weights.ctypes.data if weights is not None else None, ptr(subject), ptr(dist), ptr(counts),
+                                       entries.ctypes.data if cap else None, cap, totals.ctypes.data)
+            if rc == _lib.ERR_CAPACITY:
+                cap = int(totals[0])
+                continue
+            check(rc)
+            return Assigned(entries[: int(totals[0])], subject, dist, counts, totals)
+
+    def assign_launch(self, qset: QuerySet, max_divergence: int, d_labels: int, d_samples: int, n_samples: int, d_weights: int,
+                      d_subject: int, d_dist: int, d_subject_counts: int, d_entries: int, cap: int, d_totals: int) -> None:
+        """device-resident form (smafa_db_assign_launch): n_subjects uint32 labels in d_labels, one uint32 per read in d_samples and
+        d_weights (0: none given); one uint32 per read to d_subject and d_dist, n_subjects uint64 to d_subject_counts (0: not
+        wanted); the first cap entries in table order to d_entries (16 B each; 0 with cap 0: counted only); four uint64 to
+        d_totals.  The call has waited for its work when it returns."""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().smafa_db_assign_launch(self._h, qset._h, _opt(max_divergence), ptr(d_labels), ptr(d_samples), int(n_samples),
+                                           ptr(d_weights), ptr(d_subject), ptr(d_dist), ptr(d_subject_counts), ptr(d_entries), int(cap),
+                                           ptr(d_totals)))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -877,6 +935,15 @@ def consensus(db_path: str, labels_path: str, out_fd: int = 1, device: int = 0) 
     """`smafa consensus`: "label\\tsize\\tnearest\\tmax_div\\tSEQUENCE" per cluster of the labels file ("i\\tlabel" per subject of the
     DB file, as the label verbs print it; "-": stdin) in ascending label order (smafa_db_consensus), to out_fd."""
     check(lib().smafa_consensus(os.fsencode(db_path), os.fsencode(labels_path), out_fd, device))
+
+
+def table(db_path: str, query_fasta: str, max_divergence: int, labels_path: Optional[str] = None, samples_path: Optional[str] = None,
+          weights_path: Optional[str] = None, per_read: bool = False, per_sequence: bool = False, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa table`: "label<TAB>sample<TAB>count" lines of the reads of query_fasta against the DB (smafa_table); per_read:
+    "read<TAB>subject<TAB>dist" lines; per_sequence: "i<TAB>count" lines, what `chimeras --weights` reads"""
+    enc = lambda p: os.fsencode(p) if p is not None else None  # noqa: E731
+    check(lib().smafa_table(os.fsencode(db_path), os.fsencode(query_fasta), _opt(max_divergence), enc(labels_path), enc(samples_path),
+                            enc(weights_path), 1 if per_read else 0, 1 if per_sequence else 0, out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

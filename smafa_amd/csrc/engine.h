@@ -65,6 +65,23 @@ inline PieceRule join_piece_rule(uint64_t count, uint64_t capacity, uint64_t cei
     return {kPieceHalve, half > 64 ? half : 64};
 }
 
+// The abundance table's span rule (assign_abi.hip.h: assign_reads).  A span of reads is scanned in the tightening mode (each read's
+// bound follows its smallest distance) into `room` rows of the handle's row list; in that mode a count above the room only says
+// "did not fit".  The first room holds 64 rows per read of the span, at least 4096, at most the ceiling (SMAFA_ASSIGN_ROWS_MAX).
+// A span that did not fit: the room doubles, up to the ceiling, and the same reads are scanned again; at the ceiling the span is
+// cut to max(64, ((reads / 2 + 63) / 64) * 64) reads, and a span of 64 reads or fewer fails.  The reduced span is kept.
+inline uint64_t assign_first_room(uint64_t span, uint64_t ceiling) {
+    const uint64_t want = span * 64 > 4096 ? span * 64 : 4096;
+    return want < ceiling ? want : ceiling;
+}
+inline PieceRule assign_span_rule(uint64_t count, uint64_t room, uint64_t ceiling, uint64_t reads) {
+    if (count <= room) return {kPieceTake, reads};
+    if (room < ceiling) return {kPieceGrow, reads};
+    if (reads <= 64) return {kPieceFail, reads};
+    const uint64_t half = (reads / 2 + 63) / 64 * 64;
+    return {kPieceHalve, half > 64 ? half : 64};
+}
+
 // How the neighbours call (self_join.hip.h: join_neighbours) orders its entries (row, dist, neighbour): a pure function of the
 // store's rows, the bound and the sequence length.  dist_bits holds the largest distance the join can report,
 // min(max_div, seq_len); row_bits holds n - 1.  Where both fit 32 bits an entry is ONE 64-bit key, row << (32 + dist_bits) |

@@ -32,6 +32,7 @@
 #include "stable.hip.h"
 #include "consensus.hip.h"
 #include "chimera.hip.h"
+#include "assign.hip.h"
 
 namespace smafa {
 
@@ -257,6 +258,9 @@ struct smafa_db {
         // window of consensus_chunk sorted entries; the sort's double buffers are keys_a / keys_b / idx_a / idx_b (16 B per position).
         // count_ms (groups), filter_ms (keys, sort and bounds), link_ms (tally and vote), flatten_ms (measure and finish)
         DevBuf cons;
+        // abundance table (assign.hip.h): parent holds best[] (8 B per read), mark[] and its sums (4 B x 2 per read), live for one
+        // call; the sort's double buffers are keys_a / keys_b (8 B per read) and idx_a / idx_b (4 B per read).  count_ms (init),
+        // link_ms (the best passes), flatten_ms (bin, sort, heads, sums and fold)
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -264,6 +268,9 @@ struct smafa_db {
     uint64_t density_keep_max = 1ull << 27;  // rows the kept pair list (density and peaks calls) may grow to; 0: never kept, the store is joined
                                              // twice (SMAFA_DENSITY_KEEP_MAX; default: the value of join_scratch_max)
     uint64_t consensus_chunk = 4096;  // sorted entries per wave of consensus::tally_vote_kernel (SMAFA_CONSENSUS_CHUNK)
+    uint64_t assign_span = 65536;     // reads per scan of the abundance table (SMAFA_ASSIGN_SPAN)
+    uint64_t assign_rows_max = 1ull << 27;  // rows the row list may grow to for one span before the span is halved (SMAFA_ASSIGN_ROWS_MAX;
+                                            // default: the value of join_scratch_max)
     bool neighbour_two_sorts = false;  // neighbours: the two-sort order also where one key would hold an entry (SMAFA_NEIGHBOUR_SORT=2, tests)
     bool call_timed = false;        // the last call was a self-join: smafa_last_scan_ms reports the totals over its blocks
     size_t tile_words() const { return (size_t)P * W * kWaveTile; }
@@ -1079,6 +1086,9 @@ int smafa_db_create(smafa_db **out, int device, int alphabet, uint32_t seq_len) 
     if (const char *jv = getenv("SMAFA_CONSENSUS_CHUNK"))
         db->consensus_chunk = std::min<uint64_t>(1u << 20, std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64));
     if (const char *jv = getenv("SMAFA_NEIGHBOUR_SORT")) db->neighbour_two_sorts = atoi(jv) == 2;
+    if (const char *jv = getenv("SMAFA_ASSIGN_SPAN")) db->assign_span = std::min<uint64_t>(1u << 24, std::max<uint64_t>(64, strtoull(jv, nullptr, 10) / 64 * 64));
+    db->assign_rows_max = db->join_scratch_max;
+    if (const char *jv = getenv("SMAFA_ASSIGN_ROWS_MAX")) db->assign_rows_max = std::max<uint64_t>(64, strtoull(jv, nullptr, 10));
     db->density_keep_max = db->join_scratch_max;
     if (const char *jv = getenv("SMAFA_DENSITY_KEEP_MAX")) {  // any number of rows, 0 included (two joins); not a number: ignored, aloud
         char *end = nullptr;
@@ -1629,6 +1639,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 }
 
 #include "self_join_abi.hip.h"  // the smafa_db_self_* entry points: argument checks, the device-pointer forms, the host forms
+#include "assign_abi.hip.h"     // the abundance table: its call (assign_reads) and the two smafa_db_assign entry points
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {
     if (!db || !query_codes || (!distances && db->n)) return set_error(SMAFA_ERR_INVALID, "smafa_distances: NULL argument");

@@ -851,11 +851,12 @@ int smafa_stable(const char *db_path, uint32_t max_divergence, uint32_t min_pts,
 // ------------------------------------------------------------------------------------ consensus
 // A labels file as the label verbs print it: line j is "{j}\t{label}" and whatever columns follow, label -1 for SMAFA_NONE.  `text`
 // is the whole file; -> labels[n], or SMAFA_ERR_INVALID naming the first line that is not what it should be.
-static int parse_labels(const std::string &text, size_t n, std::vector<uint32_t> &labels) {
+// who: the verb, for the texts; may_end_early: the subjects behind the file's last line keep SMAFA_NONE (`smafa table`)
+static int parse_labels(const char *who, const std::string &text, size_t n, bool may_end_early, std::vector<uint32_t> &labels) {
     labels.assign(n, SMAFA_NONE);
     size_t at = 0, line = 0;
     const auto bad = [&](const char *what) {
-        return set_error(SMAFA_ERR_INVALID, "smafa_consensus: labels line %llu: %s", (unsigned long long)line + 1, what);
+        return set_error(SMAFA_ERR_INVALID, "%s: labels line %llu: %s", who, (unsigned long long)line + 1, what);
     };
     // an unsigned decimal number of at most ten digits at text[at ..), -> false where there is none
     const auto number = [&](uint64_t *out) {
@@ -880,7 +881,7 @@ static int parse_labels(const std::string &text, size_t n, std::vector<uint32_t>
         while (at < text.size() && text[at] != '\n') at++;  // further columns
         if (at < text.size()) at++;
     }
-    if (line < n) return bad("the file ends here, the database has more sequences");
+    if (line < n && !may_end_early) return bad("the file ends here, the database has more sequences");
     return SMAFA_OK;
 }
 
@@ -908,7 +909,7 @@ int smafa_consensus(const char *db_path, const char *labels_path, int out_fd, in
     std::string text;
     rc = read_whole("smafa_consensus", "labels", labels_path, text);
     std::vector<uint32_t> labels;
-    if (!rc) rc = parse_labels(text, v.n, labels);
+    if (!rc) rc = parse_labels("smafa_consensus", text, v.n, false, labels);
     if (rc || v.empty) return rc;
     std::string().swap(text);
     smafa_db_info_t info{};
@@ -1006,12 +1007,15 @@ int smafa_peaks(const char *db_path, uint32_t max_divergence, uint32_t radius, i
 // ------------------------------------------------------------------------------------ chimeras
 // A weights file: "{i}\t{weight}" and whatever columns follow per line, in any order; a subject without a line has weight 0.
 // `text` is the whole file; -> weights[n], or SMAFA_ERR_INVALID naming the first line that is not what it should be.
-static int parse_weights(const std::string &text, size_t n, std::vector<uint32_t> &weights) {
-    weights.assign(n, 0);
+// who: the verb, what: the file's kind ("weights", "samples"), value: what its second column holds, absent: the value of a row
+// without a line — `smafa table` reads its two per-read files with this too
+static int parse_weights(const char *who, const char *what, const char *value, uint32_t absent, const std::string &text, size_t n,
+                         std::vector<uint32_t> &weights) {
+    weights.assign(n, absent);
     std::vector<bool> seen(n, false);
     size_t at = 0, line = 0;
-    const auto bad = [&](const char *what) {
-        return set_error(SMAFA_ERR_INVALID, "smafa_chimeras: weights line %llu: %s", (unsigned long long)line + 1, what);
+    const auto bad = [&](const std::string &why) {
+        return set_error(SMAFA_ERR_INVALID, "%s: %s line %llu: %s", who, what, (unsigned long long)line + 1, why.c_str());
     };
     // an unsigned decimal number of at most ten digits at text[at ..), -> false where there is none
     const auto number = [&](uint64_t *out) {
@@ -1028,8 +1032,8 @@ static int parse_weights(const std::string &text, size_t n, std::vector<uint32_t
         at++;
         if (i >= n) return bad("the sequence number is not one of the database's");
         if (seen[i]) return bad("a second line for this sequence");
-        if (!number(&weight) || weight > 0xffffffffull) return bad("no weight (an unsigned 32-bit number)");
-        if (at < text.size() && text[at] != '\t' && text[at] != '\n' && text[at] != '\r') return bad("the weight is not a number");
+        if (!number(&weight) || weight > 0xffffffffull) return bad(std::string("no ") + value + " (an unsigned 32-bit number)");
+        if (at < text.size() && text[at] != '\t' && text[at] != '\n' && text[at] != '\r') return bad(std::string("the ") + value + " is not a number");
         seen[i] = true;
         weights[i] = (uint32_t)weight;
         while (at < text.size() && text[at] != '\n') at++;  // further columns
@@ -1055,7 +1059,7 @@ int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius
     if (weights_path) {
         std::string text;
         rc = read_whole("smafa_chimeras", "weights", weights_path, text);
-        if (!rc) rc = parse_weights(text, n, given);
+        if (!rc) rc = parse_weights("smafa_chimeras", "weights", "weight", 0, text, n, given);
         if (rc) return rc;
     }
     std::vector<uint32_t> flags(n), left(n), left_len(n), right(n), right_len(n), weights(n);
@@ -1088,6 +1092,103 @@ int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_chimeras");
+}
+
+// ------------------------------------------------------------------------------------ table
+// The abundance table of a reads file against a DB file (smafa_db_assign), printed "{label}\t{sample}\t{count}\n" per entry in
+// table order — or "{read}\t{subject}\t{dist}\n" per read (per_read), or "{i}\t{count}\n" per subject (per_sequence); -1 for
+// SMAFA_NONE.  An empty DB prints nothing.
+int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_divergence, const char *labels_path, const char *samples_path,
+                const char *weights_path, int per_read, int per_sequence, int out_fd, int device) try {
+    const char *const who = "smafa_table";
+    StoreVerb v;
+    int rc = begin_store_verb(who, db_path, max_divergence, device, v, [&] {
+        if (!query_fasta) return set_error(SMAFA_ERR_INVALID, "%s: NULL reads path", who);
+        if (per_read && per_sequence) return set_error(SMAFA_ERR_INVALID, "%s: per_read and per_sequence exclude each other", who);
+        int from_stdin = 0;
+        for (const char *path : {labels_path, samples_path, weights_path}) from_stdin += path && !strcmp(path, "-");
+        if (from_stdin > 1) return set_error(SMAFA_ERR_INVALID, "%s: at most one of the labels, samples and weights files may be stdin", who);
+        return (int)SMAFA_OK;
+    });
+    if (rc || v.empty) return rc;
+    smafa_db_info_t info{};
+    rc = smafa_db_info(v.store.db, &info);
+    if (rc) return rc;
+    FreeGuard codes;
+    uint8_t *rows = nullptr;
+    uint64_t m = 0;
+    uint32_t L = 0;
+    log_line(1, "Reading reads file \"%s\"", query_fasta);
+    rc = smafa_fastx_load(query_fasta, info.alphabet, &rows, &m, &L);
+    if (rc) return rc;
+    codes.p = rows;
+    if (m && L != info.seq_len)  // src/lib.rs:72-79, as `smafa query` fails
+        return set_error(SMAFA_ERR_PANIC, "Cannot compute distances between seq of length %u and windows of lengths %u", L, info.seq_len);
+    std::vector<uint32_t> labels, samples, weights;
+    const auto side_file = [&](const char *path, const char *what, const auto &parse) {
+        std::string text;
+        const int frc = read_whole(who, what, path, text);
+        return frc ? frc : parse(text);
+    };
+    if (labels_path) rc = side_file(labels_path, "labels", [&](const std::string &text) { return parse_labels(who, text, v.n, true, labels); });
+    if (!rc && samples_path)
+        rc = side_file(samples_path, "samples", [&](const std::string &text) { return parse_weights(who, "samples", "sample", 0, text, m, samples); });
+    if (!rc && weights_path)
+        rc = side_file(weights_path, "weights", [&](const std::string &text) { return parse_weights(who, "weights", "weight", 1, text, m, weights); });
+    if (rc) return rc;
+    uint32_t top = 0;
+    for (uint32_t s : samples) top = std::max(top, s);
+    if (top == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: sample number %u is too large", who, top);
+    const uint32_t n_samples = top + 1u;
+    std::vector<uint32_t> subject(per_read ? m : 0), dist(per_read ? m : 0);
+    std::vector<uint64_t> subject_counts(per_sequence ? v.n : 0);
+    std::vector<smafa_table_entry> entries((size_t)std::min<uint64_t>(m, (uint64_t)1 << 16));
+    uint64_t totals[4] = {0, 0, 0, 0};
+    const auto call = [&] {
+        return smafa_db_assign(v.store.db, rows, m, max_divergence, labels_path ? labels.data() : nullptr, samples_path ? samples.data() : nullptr,
+                               n_samples, weights_path ? weights.data() : nullptr, per_read ? subject.data() : nullptr,
+                               per_read ? dist.data() : nullptr, per_sequence ? subject_counts.data() : nullptr,
+                               entries.empty() ? nullptr : entries.data(), entries.size(), totals);
+    };
+    rc = call();
+    if (rc == SMAFA_ERR_CAPACITY) {
+        entries.resize(totals[0]);
+        rc = call();
+    }
+    if (rc) return rc;
+    const auto field = [](std::string &text, uint32_t f) {
+        if (f == SMAFA_NONE) text += "-1";
+        else append_u32(text, f);
+    };
+    if (per_read) rc = write_rows(out_fd, m, kRowsPerWrite, [&](std::string &text, size_t q) {
+        append_u32(text, (uint32_t)q);
+        text.push_back('\t');
+        field(text, subject[q]);
+        text.push_back('\t');
+        field(text, dist[q]);
+        text.push_back('\n');
+    });
+    else if (per_sequence) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_u32(text, (uint32_t)i);
+        text.push_back('\t');
+        text += std::to_string((unsigned long long)subject_counts[i]);
+        text.push_back('\n');
+    });
+    else rc = write_rows(out_fd, totals[0], kRowsPerWrite, [&](std::string &text, size_t e) {
+        field(text, entries[e].label);
+        text.push_back('\t');
+        append_u32(text, entries[e].sample);
+        text.push_back('\t');
+        text += std::to_string((unsigned long long)entries[e].count);
+        text.push_back('\n');
+    });
+    if (rc) return rc;
+    log_line(1, "%llu table entries of %llu reads in %u samples against %llu sequences within %u: weight %llu assigned, %llu unassigned, took %llu seconds",
+             (unsigned long long)totals[0], (unsigned long long)m, n_samples, (unsigned long long)v.n, max_divergence,
+             (unsigned long long)totals[1], (unsigned long long)totals[2], v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_table");
 }
 
 // ------------------------------------------------------------------------------------ neighbours

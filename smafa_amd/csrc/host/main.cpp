@@ -22,6 +22,9 @@
 //           and the weight of every subject)
 //   chimeras -d/--database FILE  --max-divergence INT  [--min-fold INT] [--radius INT] [--weights FILE|-]   (this build only: the
 //           chimera check, per subject its flag, its best left and right parent with the shared prefix / suffix length, its weight)
+//   table   -d/--database FILE  -q/--query FILE  --max-divergence INT  [--labels FILE|-] [--samples FILE|-] [--weights FILE|-]
+//           [--per-read | --per-sequence]   (this build only: the reads assigned to their nearest subject within the bound and
+//           counted per (label, sample); or per read its subject and distance; or per subject its count)
 //   neighbours -d/--database FILE  --max-divergence INT  [--max-num-hits INT]   (this build only: per subject its neighbours
 //           within the bound, nearest first)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
@@ -103,6 +106,15 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        weight as in `peaks` (--radius, default 0: the number of exact copies), or from --weights, \"i<TAB>weight\" lines in any\n"
             "        order (further columns are ignored, a sequence without a line has weight 0 and takes no part, -: stdin); the bound\n"
             "        has to be at least the divergence of the parents one wants to catch)\n"
+            "table   -d, --database <FILE>  -q, --query <FILE>  --max-divergence <INT>  [--labels <FILE|->] [--samples <FILE|->]\n"
+            "        [--weights <FILE|->] [--per-read | --per-sequence]  [--device <N>]  (not in the reference: the abundance table; every\n"
+            "        read of the query file is assigned to the database sequence with the fewest differences within the bound, ties to\n"
+            "        the smaller number, and counted: one \"label<TAB>sample<TAB>count\" line per (label, sample) with a read, ordered by\n"
+            "        label, then sample; the label of a read without a sequence within the bound is -1; --labels: a file as for\n"
+            "        `consensus` (a sequence without a line: -1), default: every sequence is its own label; --samples, --weights:\n"
+            "        \"read<TAB>value\" lines in any order, a read without a line is in sample 0 / weighs 1; at most one file is - (stdin);\n"
+            "        --per-read: \"read<TAB>subject<TAB>divergence\" lines instead, -1 -1 for a read without a sequence; --per-sequence:\n"
+            "        \"i<TAB>count\" lines, the weight assigned to each sequence:  smafa table ... --per-sequence | smafa chimeras ... --weights -)\n"
             "neighbours -d, --database <FILE>  --max-divergence <INT>  [--max-num-hits <INT>]  [--device <N>]  (not in the reference: the\n"
             "        neighbour lists of the database's own sequences, one \"i<TAB>j<TAB>divergence\" line per sequence i and neighbour j\n"
             "        within the bound, both directions of every pair, ordered by i, then divergence, then j; --max-num-hits: at most\n"
@@ -144,12 +156,12 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2;
     bool have_min_pts = false, have_since = false;
     unsigned long long since = 0;
-    bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false, joined = false;
+    bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false, joined = false, per_read = false, per_sequence = false;
     std::vector<int> devices;  // query: more than one handle
     int alphabet = SMAFA_ALPHABET_NT;
     int verbosity = 1;  // the reference logs at info level unless told otherwise (bird_tool_utils set_log_level)
@@ -169,7 +181,7 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &max_div)) return usage("--max-divergence needs an unsigned integer");
             have_max_div = true;
         } else if (a == "-q" || a == "--query") {
-            if (cmd == "query") {
+            if (cmd == "query" || cmd == "table") {
                 if (!(query = value())) return usage("--query needs a value");
             } else {
                 verbosity = 0;  // elsewhere -q is --quiet
@@ -189,14 +201,20 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &min_cluster_size)) return usage("--min-cluster-size needs an unsigned integer");
         } else if (a == "--joined" && cmd == "stable") {
             joined = true;
-        } else if (a == "--labels" && cmd == "consensus") {
+        } else if (a == "--labels" && (cmd == "consensus" || cmd == "table")) {
             if (!(labels = value())) return usage("--labels needs a file, or - for stdin");
         } else if (a == "--radius" && (cmd == "peaks" || cmd == "chimeras")) {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
         } else if (a == "--min-fold" && cmd == "chimeras") {
             if (!parse_u32(value(), &min_fold) || min_fold == 0) return usage("--min-fold needs a positive integer");
-        } else if (a == "--weights" && cmd == "chimeras") {
+        } else if (a == "--weights" && (cmd == "chimeras" || cmd == "table")) {
             if (!(weights = value())) return usage("--weights needs a file, or - for stdin");
+        } else if (a == "--samples" && cmd == "table") {
+            if (!(samples = value())) return usage("--samples needs a file, or - for stdin");
+        } else if (a == "--per-read" && cmd == "table") {
+            per_read = true;
+        } else if (a == "--per-sequence" && cmd == "table") {
+            per_sequence = true;
         } else if (a == "--since" && cmd == "pairs") {
             const char *v = value();
             char *end = nullptr;
@@ -301,6 +319,11 @@ int main(int argc, char **argv) {
         if (!database) return usage("chimeras needs --database");
         if (!have_max_div) return usage("chimeras needs --max-divergence");
         rc = smafa_chimeras(database, max_div, radius, min_fold, weights, 1, (int)device);
+    } else if (cmd == "table") {
+        if (!database || !query) return usage("table needs --database and --query");
+        if (!have_max_div) return usage("table needs --max-divergence");
+        if (per_read && per_sequence) return usage("--per-read and --per-sequence exclude each other");
+        rc = smafa_table(database, query, max_div, labels, samples, weights, per_read ? 1 : 0, per_sequence ? 1 : 0, 1, (int)device);
     } else if (cmd == "neighbours") {
         if (!database) return usage("neighbours needs --database");
         if (!have_max_div) return usage("neighbours needs --max-divergence");
