@@ -40,6 +40,7 @@ extern "C" {
 #define SMAFA_ALPHABET_AA 1 /* build-defined extension: A-Z * - (case-folded), codes 0..27; not in the reference */
 
 #define SMAFA_NONE UINT32_MAX /* "option absent" for max_div / max_num_hits / limit_per_sequence */
+#define SMAFA_TAXON_ROOT 0xfffffffeu /* smafa_db_classify: the taxon of a read whose best hits share no rank; no lineage may hold it */
 
 #define SMAFA_DB_VERSION 2u /* CURRENT_DB_VERSION, src/lib.rs:18 */
 
@@ -832,6 +833,73 @@ typedef struct {
 int smafa_db_assign_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, const void *d_labels /* n_subjects uint32, may be NULL */, const void *d_samples /* n_queries uint32, may be NULL */, uint32_t n_samples, const void *d_weights /* n_queries uint32, may be NULL */, void *d_subject /* n_queries uint32, may be NULL */, void *d_dist /* n_queries uint32, may be NULL */, void *d_subject_counts /* n_subjects uint64, may be NULL */, void *d_entries /* cap smafa_table_entry; NULL with cap == 0 counts only */, uint64_t cap, void *d_totals /* 4 uint64 */);
 int smafa_db_assign(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div, const uint32_t *labels, const uint32_t *samples, uint32_t n_samples, const uint32_t *weights, uint32_t *subject, uint32_t *dist, uint64_t *subject_counts, smafa_table_entry *entries, uint64_t cap, uint64_t totals[4]);
 
+/* ------------------------------------------------- classification: reads given the LCA of their best hits and counted */
+/*
+ * What SingleM does with the rows of `smafa query`: each read takes the lowest common ancestor (LCA) of the lineages of its
+ * equally-best hits.  The abundance table above assigns a read to ONE subject; a read equally near two genera belongs to their
+ * common family, not to whichever was appended first.  Not in the reference.
+ * Inputs: the store's n subjects; m reads (a resident query set, or code rows); a bound max_div (required); slack >= 0; lineage,
+ * n x n_ranks uint32, row-major, 1 <= n_ranks <= 16: lineage[i][r] is the id of subject i's taxon at rank r, rank 0 the most
+ * general, SMAFA_NONE = "not classified at this rank or below" (a row is read up to its first SMAFA_NONE; a row that begins with
+ * one has no lineage); samples, n_samples and weights as smafa_db_assign takes them.
+ * Per read q:
+ *   d(q)      the smallest distance of any subject within max_div.
+ *   B(q)      the subjects s with dist(q, s) <= min(d(q) + slack, max_div): slack 0 — the equally-best hits.
+ *   anchor(q) the smallest subject number among those at d(q): subject[q], with dist[q] = d(q) — smafa_db_assign's subject and
+ *             dist, byte for byte.
+ *   cp(a, s)  the number of leading ranks r with lineage[a][r] == lineage[s][r] != SMAFA_NONE.
+ *   depth[q]  the minimum over s in B(q) of cp(anchor, s).  s = anchor is included, so an anchor classified to 3 ranks caps the
+ *             depth at 3.  Where the ids form a tree this is the depth of the LCA of B(q): every member's lineage passes through
+ *             the anchor's up to the rank at which it leaves it, so ONE minimum per read decides — no per-rank state.
+ *   taxon[q]  lineage[anchor][depth - 1] where depth > 0; SMAFA_TAXON_ROOT (0xfffffffe) where depth is 0; SMAFA_NONE where no
+ *             subject is within max_div (or the store is empty) — then subject, dist and depth are SMAFA_NONE too and ties is 0.
+ *   ties[q]   |B(q)|.
+ * The call compares ids rank by rank and asks nothing else of them.  Ids are compared WITHOUT their ancestors: two different
+ * nodes that carry one id (a genus name under two families, say) are one taxon in the table.  Giving every node an id of its
+ * own — interning (parent id, name), as `smafa classify` does — is the caller's affair.
+ *   The TABLE: one smafa_table_entry {label = taxon, sample, count = the uint64 sum of weights} per (taxon, sample) that holds a
+ *   read of weight > 0, ordered by (taxon, sample) ascending: SMAFA_TAXON_ROOT sorts behind every taxon, SMAFA_NONE (the
+ *   unassigned reads) last.  Weight 0, a sample number >= n_samples and a short cap are handled exactly as by smafa_db_assign.
+ *   totals[0] = the number of entries, [1] = the assigned weight (the root's included), [2] = the unassigned weight, [3] = the
+ *   number of reads whose sample number is >= n_samples (they take no part in anything else; their per-read outputs are
+ *   written), [4] = the weight placed on the root, [5] = the number of reads with ties > 1 (of any weight, [3]'s excepted).
+ * The answer is an exact integer function of the inputs: the same bytes from run to run and under smafa_set_prefilter /
+ * smafa_set_zone_level / smafa_set_index and every SMAFA_ASSIGN_* setting.
+ *
+ * Checks, in this order, each SMAFA_ERR_INVALID with the argument named in smafa_last_error() and nothing written: a NULL handle;
+ * a NULL query set (host form: NULL query_codes with n_queries > 0); NULL totals; max_div = SMAFA_NONE; n_samples = 0; NULL
+ * entries with cap > 0; n_ranks outside 1 .. 16; NULL lineage for a store that has subjects; (launch form) a query set packed
+ * for another store; (host form) code bytes outside the alphabet, then a sample number >= n_samples, then the lineage — the
+ * value SMAFA_TAXON_ROOT anywhere, or an id behind a SMAFA_NONE in its row — each on the host before any device work, the text
+ * names the first such place.  The launch form does not look at the lineage: it reads each row up to its first SMAFA_NONE.
+ * Behind the checks totals[] is zeroed — the launch form's first enqueued operation, the host form's first store — and every
+ * other output is written only by a call that succeeds.
+ *
+ * On the device (classify.hip.h): smafa_db_assign's spans, row list and span rule (SMAFA_ASSIGN_SPAN, SMAFA_ASSIGN_ROWS_MAX).
+ * With slack 0 a span is scanned as smafa_scan_launch(max_div, max_num_hits = 1) scans it; with slack > 0 as
+ * smafa_scan_launch(max_div, SMAFA_NONE): every row within the bound.  A span whose rows do not fit is scanned again with the
+ * list doubled, then halved, before any kernel of the call has seen it; 64 reads that alone overflow the limit fail the call:
+ * SMAFA_ERR_NOMEM, and the handle stays usable.  Per taken span the table's 64-bit minimum (assign::best_kernel), then one lane
+ * per row compares the row's lineage with the anchor's and the rows of one read that sit side by side in a wave are reduced
+ * first: one 32-bit atomic minimum (depth) and one atomic add (ties) per run and wave.  Then one lane per read writes the
+ * outputs and the (taxon, sample) key, and the table's sort, heads, exclusive sum and segmented sum follow unchanged.  Fewer
+ * than 2^31 reads per call.  Handle-owned scratch: 48 B per read besides the row list.
+ *
+ * smafa_db_classify_launch: device-resident form.  d_lineage = n_subjects x n_ranks uint32 (NULL for an empty store); d_samples,
+ * d_weights = n_queries uint32 or NULL; d_subject, d_dist, d_taxon, d_depth, d_ties = n_queries uint32 or NULL (not wanted);
+ * d_entries = cap smafa_table_entry (NULL with cap = 0 counts only); d_totals = 6 uint64.  totals[0] is exact at any capacity and
+ * the first cap entries IN TABLE ORDER are stored; the entries from totals[0] up to min(cap, n_queries) are zeroed, none behind
+ * that is touched.  The call synchronises the handle's stream between its spans and at its end.  smafa_last_scan_ms /
+ * smafa_last_call_stats hold the device time and launches of all its spans and of its own passes; smafa_last_call_kernels lists
+ * the scan-family instantiations the call launched, then classify::start_kernel, assign::best_kernel and classify::agree_kernel
+ * (some row was listed), classify::key_kernel, assign::heads_kernel and assign::fold_kernel (no read at all: start_kernel alone).
+ *
+ * smafa_db_classify: host form; it makes and destroys a query set of its own.  More than cap entries: SMAFA_ERR_CAPACITY,
+ * totals[] written (totals[0] = the entries needed), nothing else; nothing is kept for the retry.
+ */
+int smafa_db_classify_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, uint32_t slack, const void *d_lineage /* n_subjects x n_ranks uint32 */, uint32_t n_ranks, const void *d_samples /* n_queries uint32, may be NULL */, uint32_t n_samples, const void *d_weights /* n_queries uint32, may be NULL */, void *d_subject /* n_queries uint32, may be NULL */, void *d_dist /* may be NULL */, void *d_taxon /* may be NULL */, void *d_depth /* may be NULL */, void *d_ties /* may be NULL */, void *d_entries /* cap smafa_table_entry; NULL with cap == 0 counts only */, uint64_t cap, void *d_totals /* 6 uint64 */);
+int smafa_db_classify(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div, uint32_t slack, const uint32_t *lineage, uint32_t n_ranks, const uint32_t *samples, uint32_t n_samples, const uint32_t *weights, uint32_t *subject, uint32_t *dist, uint32_t *taxon, uint32_t *depth, uint32_t *ties, smafa_table_entry *entries, uint64_t cap, uint64_t totals[6]);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -1026,6 +1094,18 @@ int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius
  * (subject_counts: what `smafa chimeras --weights -` reads).  per_read and per_sequence together are SMAFA_ERR_INVALID.  An empty
  * DB prints nothing. */
 int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_divergence, const char *labels_path, const char *samples_path, const char *weights_path, int per_read, int per_sequence, int out_fd, int device);
+/* `smafa classify` (not in the reference): the same DB and reads file as `smafa table`, and smafa_db_classify at max_divergence
+ * and slack.  taxonomy_path (required): "{i}\t{name};{name};...[\t...]\n" lines over subject numbers, in any order, rank 0 first;
+ * names are trimmed of blanks (SingleM's "Root; d__Bacteria; ..." reads as it stands), further columns are ignored, a trailing
+ * ';' or an empty second column adds no name; a subject without a line (or without a name) has no lineage.  More than 16 names
+ * on a line, an empty name between two others, a rank-0 name "root" or "unassigned", a second line for one subject or a subject
+ * number the DB does not have is SMAFA_ERR_INVALID with a text that names the line.  Ids are interned by (parent id, name) in order
+ * of first appearance in the file, so every node has an id of its own and the table's order is a function of the file alone.
+ * samples_path, weights_path (or NULL): as for smafa_table.  "-" is stdin for at most one of the three.
+ * Output: "{lineage}\t{sample}\t{count}\n" per entry in table order, the lineage the names joined by ';' down to the node, "root"
+ * for SMAFA_TAXON_ROOT, "unassigned" for SMAFA_NONE; per_read != 0: "{read}\t{subject}\t{dist}\t{ties}\t{depth}\t{lineage}\n" per
+ * read instead, -1 for subject, dist and depth of an unassigned read.  An empty DB prints nothing. */
+int smafa_classify(const char *db_path, const char *query_fasta, uint32_t max_divergence, uint32_t slack, const char *taxonomy_path, const char *samples_path, const char *weights_path, int per_read, int out_fd, int device);
 /* `smafa neighbours` (not in the reference): the same DB, and per subject its neighbours within max_divergence, nearest first,
  * at most max_num_hits of them (SMAFA_NONE: all) — smafa_db_self_neighbours, a degrees-only call and then the sized one —
  * "{i}\t{j}\t{dist}\n" per entry, both directions of every pair, ordered by (i, dist, j).  An empty DB prints nothing. */

@@ -26,6 +26,10 @@ Chimeras = collections.namedtuple("Chimeras", "flags left_parent left_len right_
 TABLE_DTYPE = np.dtype([("label", "<u4"), ("sample", "<u4"), ("count", "<u8")])
 TableEntry = TABLE_DTYPE
 Assigned = collections.namedtuple("Assigned", "entries subject dist subject_counts totals")
+# what SubjectStore.classify returns: the (taxon, sample) entries in table order (TABLE_DTYPE, label = taxon), per read its anchor,
+# distance, taxon, depth and ties, and the six totals.  TAXON_ROOT: the taxon of a read whose best hits share no rank
+Classified = collections.namedtuple("Classified", "entries subject dist taxon depth ties totals")
+TAXON_ROOT = 0xFFFFFFFE
 
 
 def _opt(v: Optional[int]) -> int:
@@ -599,6 +603,64 @@ class SubjectStore:
                                            ptr(d_weights), ptr(d_subject), ptr(d_dist), ptr(d_subject_counts), ptr(d_entries), int(cap),
                                            ptr(d_totals)))
 
+    # ---- classification: the LCA of the best hits -------------------------------------------------
+    def classify(self, query_codes, max_divergence: int, lineage, slack: int = 0, samples=None, n_samples: Optional[int] = None,
+                 weights=None) -> Classified:
+        """(entries, subject, dist, taxon, depth, ties, totals) — smafa_db_classify: every read given the lowest common ancestor of
+        the lineages of its best hits, the subjects within its smallest distance + slack (all within max_divergence), and counted.
+        lineage (uint32, n_subjects x n_ranks, 1 <= n_ranks <= 16): the taxon id of each subject at each rank, rank 0 the most
+        general, NONE from the rank at which a subject is not classified.  samples, n_samples, weights: as for assign.  entries
+        (TABLE_DTYPE, label = the taxon) holds one {taxon, sample, count} per (taxon, sample) with a read of weight > 0, ordered by
+        (taxon, sample), TAXON_ROOT behind every taxon, NONE last; subject, dist (assign's), taxon, depth (the number of ranks the
+        best hits share; NONE for an unassigned read) and ties (the number of best hits) are uint32 per read; totals = [entries,
+        assigned weight, unassigned weight, reads with a sample number out of range, weight on the root, reads with ties > 1].
+        Grows the entry buffer and calls again on ERR_CAPACITY."""
+        q = np.ascontiguousarray(query_codes, dtype=np.uint8).reshape(-1, self.seq_len)
+        m, n = q.shape[0], len(self)
+        lineage = np.ascontiguousarray(lineage, dtype=np.uint32)
+        if lineage.ndim != 2 or lineage.shape[0] != n:
+            raise ValueError(f"lineage has shape {lineage.shape}, expected ({n}, n_ranks)")
+
+        def given(a, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.uint32)
+            if a.shape != (m,):
+                raise ValueError(f"{what} has shape {a.shape}, expected ({m},)")
+            return a
+
+        samples, weights = given(samples, "samples"), given(weights, "weights")
+        if n_samples is None:
+            n_samples = int(samples.max()) + 1 if samples is not None and m else 1
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        subject, dist, taxon, depth = (np.full(m, NONE, dtype=np.uint32) for _ in range(4))
+        ties = np.zeros(m, dtype=np.uint32)
+        totals = np.zeros(6, dtype=np.uint64)
+        cap = min(m, 1 << 16)
+        while True:
+            entries = np.zeros(cap, dtype=TABLE_DTYPE)
+            rc = lib().smafa_db_classify(self._h, ptr(q), m, _opt(max_divergence), int(slack), ptr(lineage), int(lineage.shape[1]),
+                                         samples.ctypes.data if samples is not None else None, int(n_samples),
+                                         weights.ctypes.data if weights is not None else None, ptr(subject), ptr(dist), ptr(taxon), ptr(depth),
+                                         ptr(ties), entries.ctypes.data if cap else None, cap, totals.ctypes.data)
+            if rc == _lib.ERR_CAPACITY:
+                cap = int(totals[0])
+                continue
+            check(rc)
+            return Classified(entries[: int(totals[0])], subject, dist, taxon, depth, ties, totals)
+
+    def classify_launch(self, qset: QuerySet, max_divergence: int, slack: int, d_lineage: int, n_ranks: int, d_samples: int, n_samples: int,
+                        d_weights: int, d_subject: int, d_dist: int, d_taxon: int, d_depth: int, d_ties: int, d_entries: int, cap: int,
+                        d_totals: int) -> None:
+        """device-resident form (smafa_db_classify_launch): n_subjects x n_ranks uint32 in d_lineage, one uint32 per read in d_samples
+        and d_weights (0: none given); one uint32 per read to d_subject, d_dist, d_taxon, d_depth and d_ties (0: not wanted); the
+        first cap entries in table order to d_entries (16 B each; 0 with cap 0: counted only); six uint64 to d_totals.  The call
+        has waited for its work when it returns."""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().smafa_db_classify_launch(self._h, qset._h, _opt(max_divergence), int(slack), ptr(d_lineage), int(n_ranks), ptr(d_samples),
+                                             int(n_samples), ptr(d_weights), ptr(d_subject), ptr(d_dist), ptr(d_taxon), ptr(d_depth), ptr(d_ties),
+                                             ptr(d_entries), int(cap), ptr(d_totals)))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -944,6 +1006,15 @@ def table(db_path: str, query_fasta: str, max_divergence: int, labels_path: Opti
     enc = lambda p: os.fsencode(p) if p is not None else None  # noqa: E731
     check(lib().smafa_table(os.fsencode(db_path), os.fsencode(query_fasta), _opt(max_divergence), enc(labels_path), enc(samples_path),
                             enc(weights_path), 1 if per_read else 0, 1 if per_sequence else 0, out_fd, device))
+
+
+def classify(db_path: str, query_fasta: str, max_divergence: int, taxonomy_path: str, slack: int = 0, samples_path: Optional[str] = None,
+             weights_path: Optional[str] = None, per_read: bool = False, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa classify`: "lineage<TAB>sample<TAB>count" lines of the reads of query_fasta against the DB under the taxonomy file
+    (smafa_classify); per_read: "read<TAB>subject<TAB>dist<TAB>ties<TAB>depth<TAB>lineage" lines"""
+    enc = lambda p: os.fsencode(p) if p is not None else None  # noqa: E731
+    check(lib().smafa_classify(os.fsencode(db_path), os.fsencode(query_fasta), _opt(max_divergence), int(slack), enc(taxonomy_path),
+                               enc(samples_path), enc(weights_path), 1 if per_read else 0, out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

@@ -33,6 +33,7 @@
 #include "consensus.hip.h"
 #include "chimera.hip.h"
 #include "assign.hip.h"
+#include "classify.hip.h"
 
 namespace smafa {
 
@@ -261,6 +262,8 @@ struct smafa_db {
         // abundance table (assign.hip.h): parent holds best[] (8 B per read), mark[] and its sums (4 B x 2 per read), live for one
         // call; the sort's double buffers are keys_a / keys_b (8 B per read) and idx_a / idx_b (4 B per read).  count_ms (init),
         // link_ms (the best passes), flatten_ms (bin, sort, heads, sums and fold)
+        // LCA classification (classify.hip.h): the same, with depth[] and ties[] (4 B x 2 per read) between best[] and mark[];
+        // filter_ms (the agree passes)
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1640,6 +1643,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 
 #include "self_join_abi.hip.h"  // the smafa_db_self_* entry points: argument checks, the device-pointer forms, the host forms
 #include "assign_abi.hip.h"     // the abundance table: its call (assign_reads) and the two smafa_db_assign entry points
+#include "classify_abi.hip.h"   // the LCA classification: its call (classify_reads) and the two smafa_db_classify entry points
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {
     if (!db || !query_codes || (!distances && db->n)) return set_error(SMAFA_ERR_INVALID, "smafa_distances: NULL argument");

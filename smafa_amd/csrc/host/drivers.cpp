@@ -17,6 +17,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1189,6 +1190,187 @@ int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_diver
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_table");
+}
+
+// ------------------------------------------------------------------------------------ classify
+// The nodes of a taxonomy file, interned by (parent id, name) in order of first appearance: a node's id is its number here, so
+// two nodes of one name under different parents never share an id.
+struct TaxonNodes {
+    std::vector<uint32_t> parent;  // SMAFA_NONE: a rank-0 node
+    std::vector<std::string> name;
+    std::map<std::pair<uint32_t, std::string>, uint32_t> id_of;
+    uint32_t intern(uint32_t up, const std::string &text) {
+        const auto at = id_of.find({up, text});
+        if (at != id_of.end()) return at->second;
+        const uint32_t id = (uint32_t)name.size();
+        id_of.emplace(std::make_pair(up, text), id);
+        parent.push_back(up);
+        name.push_back(text);
+        return id;
+    }
+    // the names joined by ';' down to the node; "root" and "unassigned" for the two special values
+    void append_lineage(std::string &text, uint32_t id) const {
+        if (id == SMAFA_NONE) return (void)(text += "unassigned");
+        if (id == SMAFA_TAXON_ROOT || id >= name.size()) return (void)(text += "root");
+        uint32_t path[16], depth = 0;
+        for (uint32_t at = id; at != SMAFA_NONE && depth < 16; at = parent[at]) path[depth++] = at;
+        while (depth) {
+            text += name[path[--depth]];
+            if (depth) text.push_back(';');
+        }
+    }
+};
+
+// A taxonomy file: "{i}\t{name};{name};..." and whatever columns follow per line, in any order, names trimmed of blanks; a
+// subject without a line has no lineage.  `text` is the whole file; -> rows[n][16] of node ids (SMAFA_NONE behind a row's last
+// name) and *ranks, the longest row (at least 1), or SMAFA_ERR_INVALID naming the first line that is not what it should be.
+static int parse_taxonomy(const char *who, const std::string &text, size_t n, TaxonNodes &nodes, std::vector<uint32_t> &rows, uint32_t *ranks) {
+    rows.assign(n * 16, SMAFA_NONE);
+    *ranks = 1;
+    std::vector<bool> seen(n, false);
+    size_t at = 0, line = 0;
+    const auto bad = [&](const char *why) {
+        return set_error(SMAFA_ERR_INVALID, "%s: taxonomy line %llu: %s", who, (unsigned long long)line + 1, why);
+    };
+    for (; at < text.size(); line++) {
+        size_t digits = 0;
+        uint64_t i = 0;
+        while (at < text.size() && text[at] >= '0' && text[at] <= '9' && digits < 11) i = i * 10 + (uint64_t)(text[at++] - '0'), digits++;
+        if (digits == 0 || digits >= 11) return bad("no sequence number");
+        if (at >= text.size() || text[at] != '\t') return bad("no tab behind the sequence number");
+        at++;
+        if (i >= n) return bad("the sequence number is not one of the database's");
+        if (seen[i]) return bad("a second line for this sequence");
+        seen[i] = true;
+        size_t end = at;
+        while (end < text.size() && text[end] != '\t' && text[end] != '\n') end++;
+        uint32_t depth = 0, up = SMAFA_NONE;
+        bool gap = false;  // an empty name: fine at the end of the column, not in front of another name
+        for (size_t a = at; a <= end;) {
+            size_t b = a;
+            while (b < end && text[b] != ';') b++;
+            size_t first = a, last = b;
+            while (first < last && (text[first] == ' ' || text[first] == '\r')) first++;
+            while (last > first && (text[last - 1] == ' ' || text[last - 1] == '\r')) last--;
+            if (first == last) {
+                gap = true;
+            } else {
+                if (gap) return bad("an empty name in front of another");
+                if (depth == 16) return bad("more than 16 names");
+                const std::string name = text.substr(first, last - first);
+                if (depth == 0 && (name == "root" || name == "unassigned")) return bad("the first name is \"root\" or \"unassigned\", which the output keeps for itself");
+                up = nodes.intern(up, name);
+                rows[i * 16 + depth++] = up;
+            }
+            a = b + 1;
+        }
+        *ranks = std::max(*ranks, depth);
+        at = end;
+        while (at < text.size() && text[at] != '\n') at++;  // further columns
+        if (at < text.size()) at++;
+    }
+    return SMAFA_OK;
+}
+
+// The classification of a reads file against a DB file (smafa_db_classify), printed "{lineage}\t{sample}\t{count}\n" per entry in
+// table order — or "{read}\t{subject}\t{dist}\t{ties}\t{depth}\t{lineage}\n" per read (per_read).  An empty DB prints nothing.
+int smafa_classify(const char *db_path, const char *query_fasta, uint32_t max_divergence, uint32_t slack, const char *taxonomy_path,
+                   const char *samples_path, const char *weights_path, int per_read, int out_fd, int device) try {
+    const char *const who = "smafa_classify";
+    StoreVerb v;
+    int rc = begin_store_verb(who, db_path, max_divergence, device, v, [&] {
+        if (!query_fasta) return set_error(SMAFA_ERR_INVALID, "%s: NULL reads path", who);
+        if (!taxonomy_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL taxonomy path", who);
+        int from_stdin = 0;
+        for (const char *path : {taxonomy_path, samples_path, weights_path}) from_stdin += path && !strcmp(path, "-");
+        if (from_stdin > 1) return set_error(SMAFA_ERR_INVALID, "%s: at most one of the taxonomy, samples and weights files may be stdin", who);
+        return (int)SMAFA_OK;
+    });
+    if (rc || v.empty) return rc;
+    smafa_db_info_t info{};
+    rc = smafa_db_info(v.store.db, &info);
+    if (rc) return rc;
+    FreeGuard codes;
+    uint8_t *rows = nullptr;
+    uint64_t m = 0;
+    uint32_t L = 0;
+    log_line(1, "Reading reads file \"%s\"", query_fasta);
+    rc = smafa_fastx_load(query_fasta, info.alphabet, &rows, &m, &L);
+    if (rc) return rc;
+    codes.p = rows;
+    if (m && L != info.seq_len)  // src/lib.rs:72-79, as `smafa query` fails
+        return set_error(SMAFA_ERR_PANIC, "Cannot compute distances between seq of length %u and windows of lengths %u", L, info.seq_len);
+    TaxonNodes nodes;
+    std::vector<uint32_t> wide, samples, weights;
+    uint32_t ranks = 1;
+    const auto side_file = [&](const char *path, const char *what, const auto &parse) {
+        std::string text;
+        const int frc = read_whole(who, what, path, text);
+        return frc ? frc : parse(text);
+    };
+    rc = side_file(taxonomy_path, "taxonomy", [&](const std::string &text) { return parse_taxonomy(who, text, v.n, nodes, wide, &ranks); });
+    if (!rc && samples_path)
+        rc = side_file(samples_path, "samples", [&](const std::string &text) { return parse_weights(who, "samples", "sample", 0, text, m, samples); });
+    if (!rc && weights_path)
+        rc = side_file(weights_path, "weights", [&](const std::string &text) { return parse_weights(who, "weights", "weight", 1, text, m, weights); });
+    if (rc) return rc;
+    std::vector<uint32_t> lineage(v.n * ranks);  // the rows cut to the longest
+    for (size_t i = 0; i < v.n; i++) std::copy(wide.begin() + i * 16, wide.begin() + i * 16 + ranks, lineage.begin() + i * ranks);
+    std::vector<uint32_t>().swap(wide);
+    uint32_t top = 0;
+    for (uint32_t s : samples) top = std::max(top, s);
+    if (top == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: sample number %u is too large", who, top);
+    const uint32_t n_samples = top + 1u;
+    const size_t per = per_read ? m : 0;
+    std::vector<uint32_t> subject(per), dist(per), taxon(per), depth(per), ties(per);
+    std::vector<smafa_table_entry> entries((size_t)std::min<uint64_t>(m, (uint64_t)1 << 16));
+    uint64_t totals[6] = {0, 0, 0, 0, 0, 0};
+    const auto call = [&] {
+        return smafa_db_classify(v.store.db, rows, m, max_divergence, slack, lineage.data(), ranks, samples_path ? samples.data() : nullptr, n_samples,
+                                 weights_path ? weights.data() : nullptr, per_read ? subject.data() : nullptr, per_read ? dist.data() : nullptr,
+                                 per_read ? taxon.data() : nullptr, per_read ? depth.data() : nullptr, per_read ? ties.data() : nullptr,
+                                 entries.empty() ? nullptr : entries.data(), entries.size(), totals);
+    };
+    rc = call();
+    if (rc == SMAFA_ERR_CAPACITY) {
+        entries.resize(totals[0]);
+        rc = call();
+    }
+    if (rc) return rc;
+    const auto field = [](std::string &text, uint32_t f) {
+        if (f == SMAFA_NONE) text += "-1";
+        else append_u32(text, f);
+    };
+    if (per_read) rc = write_rows(out_fd, m, kRowsPerWrite, [&](std::string &text, size_t q) {
+        append_u32(text, (uint32_t)q);
+        text.push_back('\t');
+        field(text, subject[q]);
+        text.push_back('\t');
+        field(text, dist[q]);
+        text.push_back('\t');
+        append_u32(text, ties[q]);
+        text.push_back('\t');
+        field(text, depth[q]);
+        text.push_back('\t');
+        nodes.append_lineage(text, taxon[q]);
+        text.push_back('\n');
+    });
+    else rc = write_rows(out_fd, totals[0], kRowsPerWrite, [&](std::string &text, size_t e) {
+        nodes.append_lineage(text, entries[e].label);
+        text.push_back('\t');
+        append_u32(text, entries[e].sample);
+        text.push_back('\t');
+        text += std::to_string((unsigned long long)entries[e].count);
+        text.push_back('\n');
+    });
+    if (rc) return rc;
+    log_line(1, "%llu taxon entries of %llu reads in %u samples against %llu sequences within %u, slack %u, %u ranks: weight %llu assigned (%llu on the "
+             "root), %llu unassigned, %llu reads with ties, took %llu seconds",
+             (unsigned long long)totals[0], (unsigned long long)m, n_samples, (unsigned long long)v.n, max_divergence, slack, ranks,
+             (unsigned long long)totals[1], (unsigned long long)totals[4], (unsigned long long)totals[2], (unsigned long long)totals[5], v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_classify");
 }
 
 // ------------------------------------------------------------------------------------ neighbours

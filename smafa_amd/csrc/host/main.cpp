@@ -25,6 +25,9 @@
 //   table   -d/--database FILE  -q/--query FILE  --max-divergence INT  [--labels FILE|-] [--samples FILE|-] [--weights FILE|-]
 //           [--per-read | --per-sequence]   (this build only: the reads assigned to their nearest subject within the bound and
 //           counted per (label, sample); or per read its subject and distance; or per subject its count)
+//   classify -d/--database FILE  -q/--query FILE  --max-divergence INT  --taxonomy FILE|-  [--slack INT] [--samples FILE|-]
+//           [--weights FILE|-] [--per-read]   (this build only: the reads given the lowest common ancestor of the lineages of their
+//           best hits and counted per (taxon, sample); or per read its anchor, distance, ties, depth and lineage)
 //   neighbours -d/--database FILE  --max-divergence INT  [--max-num-hits INT]   (this build only: per subject its neighbours
 //           within the bound, nearest first)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
@@ -115,6 +118,16 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        \"read<TAB>value\" lines in any order, a read without a line is in sample 0 / weighs 1; at most one file is - (stdin);\n"
             "        --per-read: \"read<TAB>subject<TAB>divergence\" lines instead, -1 -1 for a read without a sequence; --per-sequence:\n"
             "        \"i<TAB>count\" lines, the weight assigned to each sequence:  smafa table ... --per-sequence | smafa chimeras ... --weights -)\n"
+            "classify -d, --database <FILE>  -q, --query <FILE>  --max-divergence <INT>  --taxonomy <FILE|->  [--slack <INT>]\n"
+            "        [--samples <FILE|->] [--weights <FILE|->] [--per-read]  [--device <N>]  (not in the reference: what SingleM does with\n"
+            "        the rows of `query`; every read of the query file takes the lowest common ancestor of the lineages of its best hits —\n"
+            "        the database sequences within its fewest differences + slack (default 0), all within the bound — and is counted: one\n"
+            "        \"lineage<TAB>sample<TAB>count\" line per (taxon, sample) with a read, the lineage the names joined by ; down to the\n"
+            "        node, \"root\" where the hits share no rank, \"unassigned\" for a read without a sequence within the bound; --taxonomy:\n"
+            "        \"i<TAB>name;name;...\" lines in any order, most general name first, at most 16, blanks around a name are dropped,\n"
+            "        further columns are ignored, a sequence without a line has no lineage; --samples, --weights: as for `table`; at most\n"
+            "        one file is - (stdin); --per-read: \"read<TAB>subject<TAB>divergence<TAB>ties<TAB>depth<TAB>lineage\" lines instead,\n"
+            "        -1 for subject, divergence and depth of a read without a sequence)\n"
             "neighbours -d, --database <FILE>  --max-divergence <INT>  [--max-num-hits <INT>]  [--device <N>]  (not in the reference: the\n"
             "        neighbour lists of the database's own sequences, one \"i<TAB>j<TAB>divergence\" line per sequence i and neighbour j\n"
             "        within the bound, both directions of every pair, ordered by i, then divergence, then j; --max-num-hits: at most\n"
@@ -156,9 +169,9 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr, *taxonomy = nullptr;
     std::vector<const char *> count_paths;
-    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2;
+    uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2, slack = 0;
     bool have_min_pts = false, have_since = false;
     unsigned long long since = 0;
     bool have_max_div = false, packed = false, no_gpu = false, levels = false, cores = false, joined = false, per_read = false, per_sequence = false;
@@ -181,7 +194,7 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &max_div)) return usage("--max-divergence needs an unsigned integer");
             have_max_div = true;
         } else if (a == "-q" || a == "--query") {
-            if (cmd == "query" || cmd == "table") {
+            if (cmd == "query" || cmd == "table" || cmd == "classify") {
                 if (!(query = value())) return usage("--query needs a value");
             } else {
                 verbosity = 0;  // elsewhere -q is --quiet
@@ -207,12 +220,16 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &radius)) return usage("--radius needs an unsigned integer");
         } else if (a == "--min-fold" && cmd == "chimeras") {
             if (!parse_u32(value(), &min_fold) || min_fold == 0) return usage("--min-fold needs a positive integer");
-        } else if (a == "--weights" && (cmd == "chimeras" || cmd == "table")) {
+        } else if (a == "--weights" && (cmd == "chimeras" || cmd == "table" || cmd == "classify")) {
             if (!(weights = value())) return usage("--weights needs a file, or - for stdin");
-        } else if (a == "--samples" && cmd == "table") {
+        } else if (a == "--samples" && (cmd == "table" || cmd == "classify")) {
             if (!(samples = value())) return usage("--samples needs a file, or - for stdin");
-        } else if (a == "--per-read" && cmd == "table") {
+        } else if (a == "--per-read" && (cmd == "table" || cmd == "classify")) {
             per_read = true;
+        } else if (a == "--taxonomy" && cmd == "classify") {
+            if (!(taxonomy = value())) return usage("--taxonomy needs a file, or - for stdin");
+        } else if (a == "--slack" && cmd == "classify") {
+            if (!parse_u32(value(), &slack)) return usage("--slack needs an unsigned integer");
         } else if (a == "--per-sequence" && cmd == "table") {
             per_sequence = true;
         } else if (a == "--since" && cmd == "pairs") {
@@ -324,6 +341,11 @@ int main(int argc, char **argv) {
         if (!have_max_div) return usage("table needs --max-divergence");
         if (per_read && per_sequence) return usage("--per-read and --per-sequence exclude each other");
         rc = smafa_table(database, query, max_div, labels, samples, weights, per_read ? 1 : 0, per_sequence ? 1 : 0, 1, (int)device);
+    } else if (cmd == "classify") {
+        if (!database || !query) return usage("classify needs --database and --query");
+        if (!have_max_div) return usage("classify needs --max-divergence");
+        if (!taxonomy) return usage("classify needs --taxonomy");
+        rc = smafa_classify(database, query, max_div, slack, taxonomy, samples, weights, per_read ? 1 : 0, 1, (int)device);
     } else if (cmd == "neighbours") {
         if (!database) return usage("neighbours needs --database");
         if (!have_max_div) return usage("neighbours needs --max-divergence");
