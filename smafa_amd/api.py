@@ -36,6 +36,43 @@ def _opt(v: Optional[int]) -> int:
     return NONE if v is None else int(v)
 
 
+# ---- what SubjectStore.assign and SubjectStore.classify share
+def _given(a, count, what):
+    """a side array as contiguous uint32 of `count` elements (None: not given)"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.shape != (count,):
+        raise ValueError(f"{what} has shape {a.shape}, expected ({count},)")
+    return a
+
+
+def _per_read(samples, weights, n_samples, m):
+    """(samples, weights, n_samples) for m reads; n_samples None: the largest sample number + 1"""
+    samples, weights = _given(samples, m, "samples"), _given(weights, m, "weights")
+    if n_samples is None:
+        n_samples = int(samples.max()) + 1 if samples is not None and m else 1
+    return samples, weights, int(n_samples)
+
+
+def _ptr(a, empty=False):
+    """the address of an array, None where there is none — or, unless `empty`, nothing in it"""
+    return a.ctypes.data if a is not None and (empty or a.size) else None
+
+
+def _with_entries(m, totals, call):
+    """the entries of call(entries address, capacity), which fills totals; an entry buffer that was too small (ERR_CAPACITY) is
+    grown to totals[0], the number the call asks for, and the call made again"""
+    cap = min(m, 1 << 16)
+    while True:
+        entries = np.zeros(cap, dtype=TABLE_DTYPE)
+        rc = call(entries.ctypes.data if cap else None, cap)
+        if rc != _lib.ERR_CAPACITY:
+            check(rc)
+            return entries[: int(totals[0])]
+        cap = int(totals[0])
+
+
 def device_count() -> int:
     return lib().smafa_device_count()
 
@@ -562,35 +599,16 @@ class SubjectStore:
         with a sample number out of range].  Grows the entry buffer and calls again on ERR_CAPACITY."""
         q = np.ascontiguousarray(query_codes, dtype=np.uint8).reshape(-1, self.seq_len)
         m, n = q.shape[0], len(self)
-
-        def given(a, count, what):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.uint32)
-            if a.shape != (count,):
-                raise ValueError(f"{what} has shape {a.shape}, expected ({count},)")
-            return a
-
-        labels, samples, weights = given(labels, n, "labels"), given(samples, m, "samples"), given(weights, m, "weights")
-        if n_samples is None:
-            n_samples = int(samples.max()) + 1 if samples is not None and m else 1
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        labels = _given(labels, n, "labels")
+        samples, weights, n_samples = _per_read(samples, weights, n_samples, m)
         subject = np.full(m, NONE, dtype=np.uint32) if per_read else None
         dist = np.full(m, NONE, dtype=np.uint32) if per_read else None
         counts = np.zeros(n, dtype=np.uint64) if subject_counts else None
         totals = np.zeros(4, dtype=np.uint64)
-        cap = min(m, 1 << 16)
-        while True:
-            entries = np.zeros(cap, dtype=TABLE_DTYPE)
-            rc = lib().smafa_db_assign(self._h, q.ctypes.data if m else None, m, _opt(max_divergence), ptr(labels),
-                                       samples.ctypes.data if samples is not None else None, int(n_samples),
-                                       weights.ctypes.data if weights is not None else None, ptr(subject), ptr(dist), ptr(counts),
-                                       entries.ctypes.data if cap else None, cap, totals.ctypes.data)
-            if rc == _lib.ERR_CAPACITY:
-                cap = int(totals[0])
-                continue
-            check(rc)
-            return Assigned(entries[: int(totals[0])], subject, dist, counts, totals)
+        entries = _with_entries(m, totals, lambda e, cap: lib().smafa_db_assign(
+            self._h, _ptr(q), m, _opt(max_divergence), _ptr(labels), _ptr(samples, True), n_samples, _ptr(weights, True), _ptr(subject),
+            _ptr(dist), _ptr(counts), e, cap, totals.ctypes.data))
+        return Assigned(entries, subject, dist, counts, totals)
 
     def assign_launch(self, qset: QuerySet, max_divergence: int, d_labels: int, d_samples: int, n_samples: int, d_weights: int,
                       d_subject: int, d_dist: int, d_subject_counts: int, d_entries: int, cap: int, d_totals: int) -> None:
@@ -620,34 +638,14 @@ class SubjectStore:
         lineage = np.ascontiguousarray(lineage, dtype=np.uint32)
         if lineage.ndim != 2 or lineage.shape[0] != n:
             raise ValueError(f"lineage has shape {lineage.shape}, expected ({n}, n_ranks)")
-
-        def given(a, what):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.uint32)
-            if a.shape != (m,):
-                raise ValueError(f"{what} has shape {a.shape}, expected ({m},)")
-            return a
-
-        samples, weights = given(samples, "samples"), given(weights, "weights")
-        if n_samples is None:
-            n_samples = int(samples.max()) + 1 if samples is not None and m else 1
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        samples, weights, n_samples = _per_read(samples, weights, n_samples, m)
         subject, dist, taxon, depth = (np.full(m, NONE, dtype=np.uint32) for _ in range(4))
         ties = np.zeros(m, dtype=np.uint32)
         totals = np.zeros(6, dtype=np.uint64)
-        cap = min(m, 1 << 16)
-        while True:
-            entries = np.zeros(cap, dtype=TABLE_DTYPE)
-            rc = lib().smafa_db_classify(self._h, ptr(q), m, _opt(max_divergence), int(slack), ptr(lineage), int(lineage.shape[1]),
-                                         samples.ctypes.data if samples is not None else None, int(n_samples),
-                                         weights.ctypes.data if weights is not None else None, ptr(subject), ptr(dist), ptr(taxon), ptr(depth),
-                                         ptr(ties), entries.ctypes.data if cap else None, cap, totals.ctypes.data)
-            if rc == _lib.ERR_CAPACITY:
-                cap = int(totals[0])
-                continue
-            check(rc)
-            return Classified(entries[: int(totals[0])], subject, dist, taxon, depth, ties, totals)
+        entries = _with_entries(m, totals, lambda e, cap: lib().smafa_db_classify(
+            self._h, _ptr(q), m, _opt(max_divergence), int(slack), _ptr(lineage), int(lineage.shape[1]), _ptr(samples, True), n_samples,
+            _ptr(weights, True), _ptr(subject), _ptr(dist), _ptr(taxon), _ptr(depth), _ptr(ties), e, cap, totals.ctypes.data))
+        return Classified(entries, subject, dist, taxon, depth, ties, totals)
 
     def classify_launch(self, qset: QuerySet, max_divergence: int, slack: int, d_lineage: int, n_ranks: int, d_samples: int, n_samples: int,
                         d_weights: int, d_subject: int, d_dist: int, d_taxon: int, d_depth: int, d_ties: int, d_entries: int, cap: int,

@@ -66,6 +66,17 @@ __device__ __forceinline__ u64 run_scan(u64 v, uint32_t lane, uint32_t first, Op
     return v;
 }
 
+// the sum of `v` over the wave's 64 lanes, in every lane
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        v += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+    return v;
+}
+
+// the key of a read that takes no part in the table: all ones over the key's 32 + sample_bits bits
+__device__ __forceinline__ u64 dead_key(uint32_t sample_bits) { return sample_bits >= 32u ? ~0ull : (1ull << (32u + sample_bits)) - 1ull; }
+
 __global__ __launch_bounds__(256) void init_kernel(u64 *__restrict__ best, uint64_t m, u64 *__restrict__ subject_counts, uint64_t n,
                                                    u64 *__restrict__ totals) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(256) void bin_kernel(const u64 *__restrict__ best, 
         stray = sample >= n_samples;
         const uint32_t w = stray ? 0u : weights ? weights[q] : 1u;
         const uint32_t g = !found ? SMAFA_NONE : group_of ? group_of[s] : s;
-        const u64 dead = sample_bits >= 32u ? ~0ull : (1ull << (32u + sample_bits)) - 1ull;
+        const u64 dead = dead_key(sample_bits);
         keys[q] = w ? ((u64)g << sample_bits) | sample : dead;
         values[q] = w;
         if (found) in = w;
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(256) void bin_kernel(const u64 *__restrict__ best, 
     // the three totals: summed over the wave, one atomic each
     const u64 strays = __ballot(stray);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {  // (wave_sum's steps for both at once: two calls of it schedule differently)
         in += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(in >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)in, off, 64);
         out += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(out >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)out, off, 64);
     }
@@ -143,7 +154,7 @@ __global__ __launch_bounds__(256) void bin_kernel(const u64 *__restrict__ best, 
 __global__ __launch_bounds__(256) void heads_kernel(const u64 *__restrict__ keys, uint32_t m, uint32_t sample_bits, uint32_t *__restrict__ mark) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i > m) return;
-    const u64 dead = sample_bits >= 32u ? ~0ull : (1ull << (32u + sample_bits)) - 1ull;
+    const u64 dead = dead_key(sample_bits);
     mark[i] = i < m && keys[i] != dead && (i == 0u || keys[i - 1u] != keys[i]) ? 1u : 0u;
 }
 
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(256) void fold_kernel(const u64 *__restrict__ keys,
                                                    const uint32_t *__restrict__ sum, uint32_t m, uint32_t sample_bits, smafa_table_entry *entries,
                                                    u64 cap, u64 *__restrict__ totals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
-    const u64 dead = sample_bits >= 32u ? ~0ull : (1ull << (32u + sample_bits)) - 1ull;
+    const u64 dead = dead_key(sample_bits);
     uint32_t e = SMAFA_NONE;  // (the dead tail and the lanes past the end: one run that adds nothing)
     u64 w = 0ull;
     bool head = false;

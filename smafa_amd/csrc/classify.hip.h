@@ -104,13 +104,6 @@ __global__ __launch_bounds__(256) void agree_kernel(const smafa_hit *__restrict_
     }
 }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
-    return v;
-}
-
 // samples: nullptr — sample 0.  weights: nullptr — weight 1.  subject, dist, taxon, depth_out, ties_out: nullptr where not wanted.
 // totals[1]: assigned weight, [2]: unassigned weight, [3]: reads whose sample number is out of range, [4]: weight on the root,
 // [5]: reads (of a sample in range) with more than one member.
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(256) void key_kernel(const u64 *__restrict__ best, 
         const uint32_t sample = samples ? samples[q] : 0u;
         stray = sample >= n_samples;
         const uint32_t w = stray ? 0u : weights ? weights[q] : 1u;
-        const u64 dead = sample_bits >= 32u ? ~0ull : (1ull << (32u + sample_bits)) - 1ull;
+        const u64 dead = assign::dead_key(sample_bits);
         keys[q] = w ? ((u64)x << sample_bits) | sample : dead;
         values[q] = w;
         if (found) in = w;
@@ -147,7 +140,7 @@ __global__ __launch_bounds__(256) void key_kernel(const u64 *__restrict__ best, 
     }
     // the five totals: summed over the wave, one atomic each
     const u64 strays = __ballot(stray), many = __ballot(tied);
-    in = wave_sum(in), out = wave_sum(out), root = wave_sum(root);
+    in = assign::wave_sum(in), out = assign::wave_sum(out), root = assign::wave_sum(root);
     if (lane == 0u) {
         if (in) atomicAdd(totals + 1, in);
         if (out) atomicAdd(totals + 2, out);

@@ -65,7 +65,7 @@ inline PieceRule join_piece_rule(uint64_t count, uint64_t capacity, uint64_t cei
     return {kPieceHalve, half > 64 ? half : 64};
 }
 
-// The abundance table's span rule (assign_abi.hip.h: assign_reads).  A span of reads is scanned in the tightening mode (each read's
+// The read-table calls' span rule (read_table.hip.h: read_table_spans, for the abundance table and the classification).  A span of reads is scanned in the tightening mode (each read's
 // bound follows its smallest distance) into `room` rows of the handle's row list; in that mode a count above the room only says
 // "did not fit".  The first room holds 64 rows per read of the span, at least 4096, at most the ceiling (SMAFA_ASSIGN_ROWS_MAX).
 // A span that did not fit: the room doubles, up to the ceiling, and the same reads are scanned again; at the ceiling the span is

@@ -259,11 +259,12 @@ struct smafa_db {
         // window of consensus_chunk sorted entries; the sort's double buffers are keys_a / keys_b / idx_a / idx_b (16 B per position).
         // count_ms (groups), filter_ms (keys, sort and bounds), link_ms (tally and vote), flatten_ms (measure and finish)
         DevBuf cons;
-        // abundance table (assign.hip.h): parent holds best[] (8 B per read), mark[] and its sums (4 B x 2 per read), live for one
-        // call; the sort's double buffers are keys_a / keys_b (8 B per read) and idx_a / idx_b (4 B per read).  count_ms (init),
-        // link_ms (the best passes), flatten_ms (bin, sort, heads, sums and fold)
-        // LCA classification (classify.hip.h): the same, with depth[] and ties[] (4 B x 2 per read) between best[] and mark[];
-        // filter_ms (the agree passes)
+        // read-table calls (read_table.hip.h: ReadTable): parent holds best[] (8 B per read), the call's own words, mark[] and its
+        // sums (4 B x 2 per read), live for one call; the sort's double buffers are keys_a / keys_b (8 B per read) and idx_a /
+        // idx_b (4 B per read).  count_ms (init), link_ms (the best passes), flatten_ms (keys, sort, heads, sums and fold)
+        // abundance table (assign.hip.h): no words of its own
+        // LCA classification (classify.hip.h): depth[] and ties[] (4 B x 2 per read) between best[] and mark[]; filter_ms (the
+        // agree passes)
     } join;
     uint64_t join_block = 65536;    // rows per block of the self-join (SMAFA_JOIN_BLOCK)
     uint64_t join_stride = 16;      // blocks a span of the self-join is dealt into (SMAFA_JOIN_STRIDE; 1: consecutive positions)
@@ -1642,8 +1643,10 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 }
 
 #include "self_join_abi.hip.h"  // the smafa_db_self_* entry points: argument checks, the device-pointer forms, the host forms
+#include "read_table.hip.h"     // the frame of a call that scans a caller's query set and tabulates it: opening, span loop, table, host form
 #include "assign_abi.hip.h"     // the abundance table: its call (assign_reads) and the two smafa_db_assign entry points
 #include "classify_abi.hip.h"   // the LCA classification: its call (classify_reads) and the two smafa_db_classify entry points
+#undef RC_TRY
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {
     if (!db || !query_codes || (!distances && db->n)) return set_error(SMAFA_ERR_INVALID, "smafa_distances: NULL argument");

@@ -1095,6 +1095,98 @@ int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius
     return smafa::exception_code("smafa_chimeras");
 }
 
+// ------------------------------------------------------------------------ verbs with a reads file
+// What `smafa table` and `smafa classify` share: a store verb with a reads file, per-read samples and weights files, an entry
+// buffer that grows by the call's own answer and the same three columns per entry.
+struct ReadsVerb {
+    StoreVerb v;
+    FreeGuard codes;  // the reads' code rows
+    uint64_t m = 0;
+    std::vector<uint32_t> samples, weights;  // where their files are given
+    uint32_t n_samples = 1;
+    const uint8_t *rows() const { return static_cast<const uint8_t *>(codes.p); }
+};
+
+// begin_store_verb for such a verb.  Checked in this order: the two paths and the bound, the verb's further checks, that at most
+// one of its side files (own: the kind of the verb's own file, the first of `side_paths`) is stdin; then the store, and — unless
+// the DB holds no row — the reads loaded in its alphabet and their length held against its rows'.
+static int begin_reads_verb(const char *who, const char *db_path, const char *query_fasta, uint32_t max_divergence, int device, ReadsVerb &r,
+                            const char *own, std::initializer_list<const char *> side_paths, const std::function<int()> &more_checks) {
+    int rc = begin_store_verb(who, db_path, max_divergence, device, r.v, [&] {
+        if (!query_fasta) return set_error(SMAFA_ERR_INVALID, "%s: NULL reads path", who);
+        const int mrc = more_checks();
+        if (mrc) return mrc;
+        int from_stdin = 0;
+        for (const char *path : side_paths) from_stdin += path && !strcmp(path, "-");
+        if (from_stdin > 1) return set_error(SMAFA_ERR_INVALID, "%s: at most one of the %s, samples and weights files may be stdin", who, own);
+        return (int)SMAFA_OK;
+    });
+    if (rc || r.v.empty) return rc;
+    smafa_db_info_t info{};
+    rc = smafa_db_info(r.v.store.db, &info);
+    if (rc) return rc;
+    uint8_t *rows = nullptr;
+    uint32_t L = 0;
+    log_line(1, "Reading reads file \"%s\"", query_fasta);
+    rc = smafa_fastx_load(query_fasta, info.alphabet, &rows, &r.m, &L);
+    if (rc) return rc;
+    r.codes.p = rows;
+    if (r.m && L != info.seq_len)  // src/lib.rs:72-79, as `smafa query` fails
+        return set_error(SMAFA_ERR_PANIC, "Cannot compute distances between seq of length %u and windows of lengths %u", L, info.seq_len);
+    return SMAFA_OK;
+}
+
+// a side file read whole and handed to parse(text)
+static int side_file(const char *who, const char *path, const char *what, const std::function<int(const std::string &)> &parse) {
+    std::string text;
+    const int rc = read_whole(who, what, path, text);
+    return rc ? rc : parse(text);
+}
+
+// the samples and weights files (nullptr: none), one line per read; n_samples: the largest sample number + 1
+static int read_samples_weights(const char *who, const char *samples_path, const char *weights_path, ReadsVerb &r) {
+    int rc = SMAFA_OK;
+    if (samples_path)
+        rc = side_file(who, samples_path, "samples", [&](const std::string &text) { return parse_weights(who, "samples", "sample", 0, text, r.m, r.samples); });
+    if (!rc && weights_path)
+        rc = side_file(who, weights_path, "weights", [&](const std::string &text) { return parse_weights(who, "weights", "weight", 1, text, r.m, r.weights); });
+    if (rc) return rc;
+    uint32_t top = 0;
+    for (uint32_t s : r.samples) top = std::max(top, s);
+    if (top == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: sample number %u is too large", who, top);
+    r.n_samples = top + 1u;
+    return SMAFA_OK;
+}
+
+// call() fills `entries` and totals[]; on SMAFA_ERR_CAPACITY totals[0] is the number it needs: once more with that many
+static int call_with_entries(std::vector<smafa_table_entry> &entries, const uint64_t *totals, const std::function<int()> &call) {
+    int rc = call();
+    if (rc == SMAFA_ERR_CAPACITY) {
+        entries.resize(totals[0]);
+        rc = call();
+    }
+    return rc;
+}
+
+// a number, -1 for SMAFA_NONE
+static void append_field(std::string &text, uint32_t f) {
+    if (f == SMAFA_NONE) text += "-1";
+    else append_u32(text, f);
+}
+
+// the first `count` entries, "{label}\t{sample}\t{count}\n" each: label(text, id) appends an entry's label
+static int write_entries(int out_fd, const std::vector<smafa_table_entry> &entries, uint64_t count,
+                         const std::function<void(std::string &, uint32_t)> &label) {
+    return write_rows(out_fd, count, kRowsPerWrite, [&](std::string &text, size_t e) {
+        label(text, entries[e].label);
+        text.push_back('\t');
+        append_u32(text, entries[e].sample);
+        text.push_back('\t');
+        text += std::to_string((unsigned long long)entries[e].count);
+        text.push_back('\n');
+    });
+}
+
 // ------------------------------------------------------------------------------------ table
 // The abundance table of a reads file against a DB file (smafa_db_assign), printed "{label}\t{sample}\t{count}\n" per entry in
 // table order — or "{read}\t{subject}\t{dist}\n" per read (per_read), or "{i}\t{count}\n" per subject (per_sequence); -1 for
@@ -1102,71 +1194,36 @@ int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius
 int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_divergence, const char *labels_path, const char *samples_path,
                 const char *weights_path, int per_read, int per_sequence, int out_fd, int device) try {
     const char *const who = "smafa_table";
-    StoreVerb v;
-    int rc = begin_store_verb(who, db_path, max_divergence, device, v, [&] {
-        if (!query_fasta) return set_error(SMAFA_ERR_INVALID, "%s: NULL reads path", who);
+    ReadsVerb r;
+    StoreVerb &v = r.v;
+    int rc = begin_reads_verb(who, db_path, query_fasta, max_divergence, device, r, "labels", {labels_path, samples_path, weights_path}, [&] {
         if (per_read && per_sequence) return set_error(SMAFA_ERR_INVALID, "%s: per_read and per_sequence exclude each other", who);
-        int from_stdin = 0;
-        for (const char *path : {labels_path, samples_path, weights_path}) from_stdin += path && !strcmp(path, "-");
-        if (from_stdin > 1) return set_error(SMAFA_ERR_INVALID, "%s: at most one of the labels, samples and weights files may be stdin", who);
         return (int)SMAFA_OK;
     });
     if (rc || v.empty) return rc;
-    smafa_db_info_t info{};
-    rc = smafa_db_info(v.store.db, &info);
+    const uint64_t m = r.m;
+    std::vector<uint32_t> labels;
+    if (labels_path) rc = side_file(who, labels_path, "labels", [&](const std::string &text) { return parse_labels(who, text, v.n, true, labels); });
+    if (!rc) rc = read_samples_weights(who, samples_path, weights_path, r);
     if (rc) return rc;
-    FreeGuard codes;
-    uint8_t *rows = nullptr;
-    uint64_t m = 0;
-    uint32_t L = 0;
-    log_line(1, "Reading reads file \"%s\"", query_fasta);
-    rc = smafa_fastx_load(query_fasta, info.alphabet, &rows, &m, &L);
-    if (rc) return rc;
-    codes.p = rows;
-    if (m && L != info.seq_len)  // src/lib.rs:72-79, as `smafa query` fails
-        return set_error(SMAFA_ERR_PANIC, "Cannot compute distances between seq of length %u and windows of lengths %u", L, info.seq_len);
-    std::vector<uint32_t> labels, samples, weights;
-    const auto side_file = [&](const char *path, const char *what, const auto &parse) {
-        std::string text;
-        const int frc = read_whole(who, what, path, text);
-        return frc ? frc : parse(text);
-    };
-    if (labels_path) rc = side_file(labels_path, "labels", [&](const std::string &text) { return parse_labels(who, text, v.n, true, labels); });
-    if (!rc && samples_path)
-        rc = side_file(samples_path, "samples", [&](const std::string &text) { return parse_weights(who, "samples", "sample", 0, text, m, samples); });
-    if (!rc && weights_path)
-        rc = side_file(weights_path, "weights", [&](const std::string &text) { return parse_weights(who, "weights", "weight", 1, text, m, weights); });
-    if (rc) return rc;
-    uint32_t top = 0;
-    for (uint32_t s : samples) top = std::max(top, s);
-    if (top == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: sample number %u is too large", who, top);
-    const uint32_t n_samples = top + 1u;
+    const uint32_t n_samples = r.n_samples;
     std::vector<uint32_t> subject(per_read ? m : 0), dist(per_read ? m : 0);
     std::vector<uint64_t> subject_counts(per_sequence ? v.n : 0);
     std::vector<smafa_table_entry> entries((size_t)std::min<uint64_t>(m, (uint64_t)1 << 16));
     uint64_t totals[4] = {0, 0, 0, 0};
-    const auto call = [&] {
-        return smafa_db_assign(v.store.db, rows, m, max_divergence, labels_path ? labels.data() : nullptr, samples_path ? samples.data() : nullptr,
-                               n_samples, weights_path ? weights.data() : nullptr, per_read ? subject.data() : nullptr,
+    rc = call_with_entries(entries, totals, [&] {
+        return smafa_db_assign(v.store.db, r.rows(), m, max_divergence, labels_path ? labels.data() : nullptr, samples_path ? r.samples.data() : nullptr,
+                               n_samples, weights_path ? r.weights.data() : nullptr, per_read ? subject.data() : nullptr,
                                per_read ? dist.data() : nullptr, per_sequence ? subject_counts.data() : nullptr,
                                entries.empty() ? nullptr : entries.data(), entries.size(), totals);
-    };
-    rc = call();
-    if (rc == SMAFA_ERR_CAPACITY) {
-        entries.resize(totals[0]);
-        rc = call();
-    }
+    });
     if (rc) return rc;
-    const auto field = [](std::string &text, uint32_t f) {
-        if (f == SMAFA_NONE) text += "-1";
-        else append_u32(text, f);
-    };
     if (per_read) rc = write_rows(out_fd, m, kRowsPerWrite, [&](std::string &text, size_t q) {
         append_u32(text, (uint32_t)q);
         text.push_back('\t');
-        field(text, subject[q]);
+        append_field(text, subject[q]);
         text.push_back('\t');
-        field(text, dist[q]);
+        append_field(text, dist[q]);
         text.push_back('\n');
     });
     else if (per_sequence) rc = write_rows(out_fd, v.n, kRowsPerWrite, [&](std::string &text, size_t i) {
@@ -1175,14 +1232,7 @@ int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_diver
         text += std::to_string((unsigned long long)subject_counts[i]);
         text.push_back('\n');
     });
-    else rc = write_rows(out_fd, totals[0], kRowsPerWrite, [&](std::string &text, size_t e) {
-        field(text, entries[e].label);
-        text.push_back('\t');
-        append_u32(text, entries[e].sample);
-        text.push_back('\t');
-        text += std::to_string((unsigned long long)entries[e].count);
-        text.push_back('\n');
-    });
+    else rc = write_entries(out_fd, entries, totals[0], append_field);
     if (rc) return rc;
     log_line(1, "%llu table entries of %llu reads in %u samples against %llu sequences within %u: weight %llu assigned, %llu unassigned, took %llu seconds",
              (unsigned long long)totals[0], (unsigned long long)m, n_samples, (unsigned long long)v.n, max_divergence,
@@ -1277,92 +1327,51 @@ static int parse_taxonomy(const char *who, const std::string &text, size_t n, Ta
 int smafa_classify(const char *db_path, const char *query_fasta, uint32_t max_divergence, uint32_t slack, const char *taxonomy_path,
                    const char *samples_path, const char *weights_path, int per_read, int out_fd, int device) try {
     const char *const who = "smafa_classify";
-    StoreVerb v;
-    int rc = begin_store_verb(who, db_path, max_divergence, device, v, [&] {
-        if (!query_fasta) return set_error(SMAFA_ERR_INVALID, "%s: NULL reads path", who);
+    ReadsVerb r;
+    StoreVerb &v = r.v;
+    int rc = begin_reads_verb(who, db_path, query_fasta, max_divergence, device, r, "taxonomy", {taxonomy_path, samples_path, weights_path}, [&] {
         if (!taxonomy_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL taxonomy path", who);
-        int from_stdin = 0;
-        for (const char *path : {taxonomy_path, samples_path, weights_path}) from_stdin += path && !strcmp(path, "-");
-        if (from_stdin > 1) return set_error(SMAFA_ERR_INVALID, "%s: at most one of the taxonomy, samples and weights files may be stdin", who);
         return (int)SMAFA_OK;
     });
     if (rc || v.empty) return rc;
-    smafa_db_info_t info{};
-    rc = smafa_db_info(v.store.db, &info);
-    if (rc) return rc;
-    FreeGuard codes;
-    uint8_t *rows = nullptr;
-    uint64_t m = 0;
-    uint32_t L = 0;
-    log_line(1, "Reading reads file \"%s\"", query_fasta);
-    rc = smafa_fastx_load(query_fasta, info.alphabet, &rows, &m, &L);
-    if (rc) return rc;
-    codes.p = rows;
-    if (m && L != info.seq_len)  // src/lib.rs:72-79, as `smafa query` fails
-        return set_error(SMAFA_ERR_PANIC, "Cannot compute distances between seq of length %u and windows of lengths %u", L, info.seq_len);
+    const uint64_t m = r.m;
     TaxonNodes nodes;
-    std::vector<uint32_t> wide, samples, weights;
+    std::vector<uint32_t> wide;
     uint32_t ranks = 1;
-    const auto side_file = [&](const char *path, const char *what, const auto &parse) {
-        std::string text;
-        const int frc = read_whole(who, what, path, text);
-        return frc ? frc : parse(text);
-    };
-    rc = side_file(taxonomy_path, "taxonomy", [&](const std::string &text) { return parse_taxonomy(who, text, v.n, nodes, wide, &ranks); });
-    if (!rc && samples_path)
-        rc = side_file(samples_path, "samples", [&](const std::string &text) { return parse_weights(who, "samples", "sample", 0, text, m, samples); });
-    if (!rc && weights_path)
-        rc = side_file(weights_path, "weights", [&](const std::string &text) { return parse_weights(who, "weights", "weight", 1, text, m, weights); });
+    rc = side_file(who, taxonomy_path, "taxonomy", [&](const std::string &text) { return parse_taxonomy(who, text, v.n, nodes, wide, &ranks); });
+    if (!rc) rc = read_samples_weights(who, samples_path, weights_path, r);
     if (rc) return rc;
     std::vector<uint32_t> lineage(v.n * ranks);  // the rows cut to the longest
     for (size_t i = 0; i < v.n; i++) std::copy(wide.begin() + i * 16, wide.begin() + i * 16 + ranks, lineage.begin() + i * ranks);
     std::vector<uint32_t>().swap(wide);
-    uint32_t top = 0;
-    for (uint32_t s : samples) top = std::max(top, s);
-    if (top == SMAFA_NONE) return set_error(SMAFA_ERR_INVALID, "%s: sample number %u is too large", who, top);
-    const uint32_t n_samples = top + 1u;
+    const uint32_t n_samples = r.n_samples;
     const size_t per = per_read ? m : 0;
     std::vector<uint32_t> subject(per), dist(per), taxon(per), depth(per), ties(per);
     std::vector<smafa_table_entry> entries((size_t)std::min<uint64_t>(m, (uint64_t)1 << 16));
     uint64_t totals[6] = {0, 0, 0, 0, 0, 0};
-    const auto call = [&] {
-        return smafa_db_classify(v.store.db, rows, m, max_divergence, slack, lineage.data(), ranks, samples_path ? samples.data() : nullptr, n_samples,
-                                 weights_path ? weights.data() : nullptr, per_read ? subject.data() : nullptr, per_read ? dist.data() : nullptr,
-                                 per_read ? taxon.data() : nullptr, per_read ? depth.data() : nullptr, per_read ? ties.data() : nullptr,
-                                 entries.empty() ? nullptr : entries.data(), entries.size(), totals);
-    };
-    rc = call();
-    if (rc == SMAFA_ERR_CAPACITY) {
-        entries.resize(totals[0]);
-        rc = call();
-    }
+    rc = call_with_entries(entries, totals, [&] {
+        return smafa_db_classify(v.store.db, r.rows(), m, max_divergence, slack, lineage.data(), ranks, samples_path ? r.samples.data() : nullptr,
+                                 n_samples, weights_path ? r.weights.data() : nullptr, per_read ? subject.data() : nullptr,
+                                 per_read ? dist.data() : nullptr, per_read ? taxon.data() : nullptr, per_read ? depth.data() : nullptr,
+                                 per_read ? ties.data() : nullptr, entries.empty() ? nullptr : entries.data(), entries.size(), totals);
+    });
     if (rc) return rc;
-    const auto field = [](std::string &text, uint32_t f) {
-        if (f == SMAFA_NONE) text += "-1";
-        else append_u32(text, f);
-    };
+    const auto lineage_of = [&](std::string &text, uint32_t id) { nodes.append_lineage(text, id); };
     if (per_read) rc = write_rows(out_fd, m, kRowsPerWrite, [&](std::string &text, size_t q) {
         append_u32(text, (uint32_t)q);
         text.push_back('\t');
-        field(text, subject[q]);
+        append_field(text, subject[q]);
         text.push_back('\t');
-        field(text, dist[q]);
+        append_field(text, dist[q]);
         text.push_back('\t');
         append_u32(text, ties[q]);
         text.push_back('\t');
-        field(text, depth[q]);
+        append_field(text, depth[q]);
         text.push_back('\t');
-        nodes.append_lineage(text, taxon[q]);
+        lineage_of(text, taxon[q]);
         text.push_back('\n');
     });
-    else rc = write_rows(out_fd, totals[0], kRowsPerWrite, [&](std::string &text, size_t e) {
-        nodes.append_lineage(text, entries[e].label);
-        text.push_back('\t');
-        append_u32(text, entries[e].sample);
-        text.push_back('\t');
-        text += std::to_string((unsigned long long)entries[e].count);
-        text.push_back('\n');
-    });
+    else rc = write_entries(out_fd, entries, totals[0], lineage_of);
     if (rc) return rc;
     log_line(1, "%llu taxon entries of %llu reads in %u samples against %llu sequences within %u, slack %u, %u ranks: weight %llu assigned (%llu on the "
              "root), %llu unassigned, %llu reads with ties, took %llu seconds",

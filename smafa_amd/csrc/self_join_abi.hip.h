@@ -565,4 +565,3 @@ int smafa_db_consensus(smafa_db *db, const uint32_t *labels, uint32_t *ids, uint
 } catch (...) {
     return smafa::exception_code("smafa_db_consensus");
 }
-#undef RC_TRY
