@@ -900,6 +900,44 @@ int smafa_db_assign(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 int smafa_db_classify_launch(smafa_db *db, smafa_qset *qs, uint32_t max_div, uint32_t slack, const void *d_lineage /* n_subjects x n_ranks uint32 */, uint32_t n_ranks, const void *d_samples /* n_queries uint32, may be NULL */, uint32_t n_samples, const void *d_weights /* n_queries uint32, may be NULL */, void *d_subject /* n_queries uint32, may be NULL */, void *d_dist /* may be NULL */, void *d_taxon /* may be NULL */, void *d_depth /* may be NULL */, void *d_ties /* may be NULL */, void *d_entries /* cap smafa_table_entry; NULL with cap == 0 counts only */, uint64_t cap, void *d_totals /* 6 uint64 */);
 int smafa_db_classify(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries, uint32_t max_div, uint32_t slack, const uint32_t *lineage, uint32_t n_ranks, const uint32_t *samples, uint32_t n_samples, const uint32_t *weights, uint32_t *subject, uint32_t *dist, uint32_t *taxon, uint32_t *depth, uint32_t *ties, smafa_table_entry *entries, uint64_t cap, uint64_t totals[6]);
 
+/* ------------------------------------------------- rows out of a store: a subset of it as a new store, its sequences back */
+/* Every other call answers "which of the store's sequences do I want?"; these two act on the answer, on the device.
+ *
+ * smafa_db_subset_launch: keep[] holds one uint32 per subject, non-zero: keep; invert != 0 turns it into a drop list (the flags
+ * of smafa_db_self_chimeras can be passed as they are).  *out is a NEW handle on the same device, with the same alphabet and
+ * seq_len, the source's layout (its column order and per-column code tables copied, not chosen again) and the source's plane
+ * count (a nucleotide store that held an N stays 3-plane even if no N survives); its knobs are read from the environment as
+ * smafa_db_create reads them, and it has a stream of its own.  The kept subjects are renumbered 0 .. k-1 in ascending old number;
+ * old_of_new[new] = old where the array is given.  The result has no index.  For every call of this header it is
+ * indistinguishable from a store made by smafa_db_create and ONE smafa_db_append of the kept rows' codes in ascending old number:
+ * the same subject numbers, distances and row order (the one exception is the choice among equal-weight forest edges, which is
+ * free anyway).  The rows keep the source's position order — deleting rows from a sorted run leaves it sorted, so nothing is
+ * sorted again — every run of the source keeps its kept rows and its "sorted", runs left without rows disappear, and the
+ * quarter rule of the re-sort counts the kept rows outside the source's first run where that run is sorted, else all k.  The
+ * zone words of the result are computed from its own tiles.  k == 0 gives a valid empty store with the layout set; a source
+ * without rows accepts keep == NULL.
+ * The SOURCE is not modified: its generation, block index, join state, retry rows and captured graph stay as they were.
+ * The work runs on db's current stream and is complete when the call returns (k is needed on the host: smafa_db_consensus_launch
+ * is the precedent); its kernels are in smafa_last_call_kernels(db), its device time in smafa_last_call_stats(db).
+ * Checks, in this order: db, out (then *out = NULL), n_kept (then *n_kept = 0), keep unless the store is empty, and a store of
+ * 2^31 rows or more is SMAFA_ERR_INVALID (the device scan counts in an int).  On any failure *out stays NULL and nothing is
+ * leaked; a failed allocation is SMAFA_ERR_NOMEM and leaves no stale HIP error behind for the source's next launch.
+ * smafa_db_subset: the same from host arrays; keep: n_subjects entries; old_of_new (or NULL): cap entries — cap < k with
+ * old_of_new != NULL is SMAFA_ERR_CAPACITY with *n_kept = k and *out == NULL (cap is not read where old_of_new is NULL).
+ *
+ * smafa_db_rows_launch: the code bytes of m subjects, m x seq_len bytes in source column order with source codes — what
+ * smafa_db_append was given.  d_subjects: m subject numbers on the device, in any order, repeats allowed; NULL: the range
+ * first .. first + m - 1 (first is not read where a list is given).  A listed number >= n_subjects gives a row of 0xff bytes and
+ * reads nothing of the store.  Checks, in this order: db; m == 0 is SMAFA_OK and touches nothing; d_codes; a range that passes
+ * the end of the store is SMAFA_ERR_INVALID.  Runs on db's current stream and is complete when the call returns; reported as
+ * above.  The call may bring the self-join's position table up to date, as a join would; nothing else of the handle changes.
+ * smafa_db_rows: the same to a host array; every listed number is checked on the host first and one >= n_subjects is
+ * SMAFA_ERR_INVALID with a text that names the entry. */
+int smafa_db_subset_launch(smafa_db *db, const void *d_keep /* n_subjects uint32 */, int invert, smafa_db **out, void *d_old_of_new /* n_subjects uint32, may be NULL */, uint64_t *n_kept /* host */);
+int smafa_db_subset(smafa_db *db, const uint32_t *keep, int invert, smafa_db **out, uint32_t *old_of_new /* may be NULL */, uint64_t cap, uint64_t *n_kept);
+int smafa_db_rows_launch(smafa_db *db, const void *d_subjects /* m uint32; NULL: first .. first+m-1 */, uint64_t first, uint64_t m, void *d_codes /* m * seq_len bytes */);
+int smafa_db_rows(smafa_db *db, const uint32_t *subjects, uint64_t first, uint64_t m, uint8_t *codes);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every
@@ -1106,6 +1144,13 @@ int smafa_table(const char *db_path, const char *query_fasta, uint32_t max_diver
  * for SMAFA_TAXON_ROOT, "unassigned" for SMAFA_NONE; per_read != 0: "{read}\t{subject}\t{dist}\t{ties}\t{depth}\t{lineage}\n" per
  * read instead, -1 for subject, dist and depth of an unassigned read.  An empty DB prints nothing. */
 int smafa_classify(const char *db_path, const char *query_fasta, uint32_t max_divergence, uint32_t slack, const char *taxonomy_path, const char *samples_path, const char *weights_path, int per_read, int out_fd, int device);
+/* `smafa subset` (not in the reference): the same DB, a list of sequence numbers and smafa_db_subset — keep_path: the sequences
+ * to keep, or drop_path: the ones to drop; exactly one of the two is given (both or neither is SMAFA_ERR_INVALID), "-" is stdin.
+ * The file holds one sequence number per line in its first column; further tab-separated columns are ignored, so the lines
+ * another verb printed can be piped in behind a filter; duplicates are allowed.  A line that is not of that form or a number
+ * the DB does not have is SMAFA_ERR_INVALID with a text that names the line.  out_path is written by smafa_db_save as a packed
+ * store that every verb reads; out_fd gets "{new}\t{old}\n" per kept sequence. */
+int smafa_subset(const char *db_path, const char *keep_path, const char *drop_path, const char *out_path, int out_fd, int device);
 /* `smafa neighbours` (not in the reference): the same DB, and per subject its neighbours within max_divergence, nearest first,
  * at most max_num_hits of them (SMAFA_NONE: all) — smafa_db_self_neighbours, a degrees-only call and then the sized one —
  * "{i}\t{j}\t{dist}\n" per entry, both directions of every pair, ordered by (i, dist, j).  An empty DB prints nothing. */

@@ -659,6 +659,59 @@ class SubjectStore:
                                              int(n_samples), ptr(d_weights), ptr(d_subject), ptr(d_dist), ptr(d_taxon), ptr(d_depth), ptr(d_ties),
                                              ptr(d_entries), int(cap), ptr(d_totals)))
 
+    # ---- rows out of the store: a subset of it as a new store, its sequences back ---------------------
+    def subset(self, keep, invert: bool = False) -> tuple["SubjectStore", np.ndarray]:
+        """(store, old_of_new) — smafa_db_subset: the kept subjects as a NEW store on the same device, renumbered 0 .. k-1 in
+        ascending old number; old_of_new[new] = old (uint32).  keep: a boolean or integer array of length len(self), non-zero:
+        keep; invert: the array lists the rows to DROP (the flags of self_chimeras as they are).  The result has this store's
+        layout and plane count and no index; it answers every call as a fresh store with push(codes[keep]) would.  This store
+        is not modified."""
+        n = len(self)
+        k = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint32)
+        if k.shape[0] != n:
+            raise ValueError(f"keep has {k.shape[0]} entries, the store has {n} subjects")
+        old_of_new = np.zeros(n, dtype=np.uint32)
+        sub = SubjectStore.__new__(SubjectStore)
+        sub._h = C.c_void_p()
+        sub.seq_len, sub.alphabet = self.seq_len, self.alphabet
+        kept = C.c_uint64(0)
+        check(lib().smafa_db_subset(self._h, _ptr(k) if n else None, 1 if invert else 0, C.byref(sub._h), _ptr(old_of_new) if n else None, n,
+                                    C.byref(kept)))
+        return sub, old_of_new[:kept.value].copy()
+
+    def subset_launch(self, d_keep: int, invert: bool = False, d_old_of_new: int = 0) -> tuple["SubjectStore", int]:
+        """device-resident form (smafa_db_subset_launch): len(self) uint32 in d_keep, len(self) uint32 of room in d_old_of_new (0: not
+        wanted) -> (store, k).  The call has waited for its work when it returns."""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        sub = SubjectStore.__new__(SubjectStore)
+        sub._h = C.c_void_p()
+        sub.seq_len, sub.alphabet = self.seq_len, self.alphabet
+        kept = C.c_uint64(0)
+        check(lib().smafa_db_subset_launch(self._h, ptr(d_keep), 1 if invert else 0, C.byref(sub._h), ptr(d_old_of_new), C.byref(kept)))
+        return sub, int(kept.value)
+
+    def rows(self, subjects=None, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """(m, seq_len) uint8 — smafa_db_rows: the code rows of the listed subjects (any order, repeats allowed), or of the range
+        first .. first + count - 1 (count None: to the end of the store), unpacked from the bit-planes on the device: the bytes
+        push() was given."""
+        if subjects is not None:
+            s = np.ascontiguousarray(np.asarray(subjects).reshape(-1), dtype=np.uint32)
+            m = s.shape[0]
+        else:
+            s, m = None, (len(self) - int(first) if count is None else int(count))
+            if m < 0:
+                raise ValueError(f"first is {first}, the store has {len(self)} subjects")
+        out = np.zeros((m, self.seq_len), dtype=np.uint8)
+        check(lib().smafa_db_rows(self._h, _ptr(s) if m and s is not None else None, int(first), m, _ptr(out) if m else None))
+        return out
+
+    def rows_launch(self, d_subjects: int, first: int, m: int, d_codes: int) -> None:
+        """device-resident form (smafa_db_rows_launch): m uint32 subject numbers in d_subjects (0: the range first .. first + m - 1),
+        m x seq_len bytes to d_codes; a listed number >= len(self) gives a row of 0xff.  The call has waited for its work when it
+        returns."""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().smafa_db_rows_launch(self._h, ptr(d_subjects), int(first), int(m), ptr(d_codes)))
+
     def last_call_stats(self) -> dict:
         ms, n, k = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().smafa_last_call_stats(self._h, C.byref(ms), C.byref(n), C.byref(k)))
@@ -1013,6 +1066,13 @@ def classify(db_path: str, query_fasta: str, max_divergence: int, taxonomy_path:
     enc = lambda p: os.fsencode(p) if p is not None else None  # noqa: E731
     check(lib().smafa_classify(os.fsencode(db_path), os.fsencode(query_fasta), _opt(max_divergence), int(slack), enc(taxonomy_path),
                                enc(samples_path), enc(weights_path), 1 if per_read else 0, out_fd, device))
+
+
+def subset(db_path: str, out_path: str, keep_path: Optional[str] = None, drop_path: Optional[str] = None, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa subset`: the sequences of the DB listed in keep_path, or all but the ones listed in drop_path ("-": stdin), saved to
+    out_path as a packed store; "new<TAB>old" lines to out_fd (smafa_subset)"""
+    enc = lambda p: os.fsencode(p) if p is not None else None  # noqa: E731
+    check(lib().smafa_subset(os.fsencode(db_path), enc(keep_path), enc(drop_path), os.fsencode(out_path), out_fd, device))
 
 
 def forest_linkage(edges, n: int, max_divergence: int) -> np.ndarray:

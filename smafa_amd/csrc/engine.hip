@@ -34,6 +34,7 @@
 #include "chimera.hip.h"
 #include "assign.hip.h"
 #include "classify.hip.h"
+#include "subset.hip.h"
 
 namespace smafa {
 
@@ -150,6 +151,7 @@ struct smafa_db {
     std::vector<uint32_t> perm;  // packed column j holds source column perm[j]
     std::vector<uint8_t> tab;    // [source column][code] -> stored code
     DevBuf d_perm, d_tab;
+    DevBuf d_inv;                // [source column][stored code] -> code, the inverse of tab: built by the first smafa_db_rows call (subset_abi.hip.h)
     uint32_t *d_order = nullptr;  // position -> subject index (cap_tiles * 256 entries)
     uint4 *d_zone = nullptr;      // per wave tile: shared filter bits (cap_tiles entries)
     struct Run { uint64_t rows; bool sorted; };
@@ -331,6 +333,13 @@ static void note_zone_words(smafa_db *db, uint32_t t0, const uint4 *z, size_t co
         slot = (uint8_t)(__builtin_popcount(z[i].y) + __builtin_popcount(z[i].w));
         db->zone_hist[slot]++;
     }
+}
+
+// mean of the shared filter bits over the store's tiles (the probes read it from the level-2 lines)
+static double zone_bits_mean(const smafa_db *db) {
+    uint64_t tiles = 0, bits = 0;
+    for (uint32_t b = 0; b <= 64; b++) tiles += db->zone_hist[b], bits += b * db->zone_hist[b];
+    return tiles ? (double)bits / (double)tiles : 0.0;
 }
 
 constexpr uint64_t kSortMin = 4096;  // appends of fewer rows keep their order (their tiles share few bits anyway)
@@ -1145,6 +1154,8 @@ int smafa_db_append(smafa_db *db, const uint8_t *codes, uint64_t n) try {
     if (n > (1u << 20)) {  // a bulk load's staging and sort buffers are not worth keeping
         for (DevBuf *b : {&db->upload, &db->keys_a, &db->keys_b, &db->idx_a, &db->idx_b, &db->sort_tmp}) b->release();
     }
+    log_line(2, "append of %llu rows: %llu in the store, %zu runs, %.2f shared filter bits per tile", (unsigned long long)n,
+             (unsigned long long)db->n, db->runs.size(), zone_bits_mean(db));
     return SMAFA_OK;
 } catch (...) {
     return smafa::exception_code("smafa_db_append");
@@ -1227,7 +1238,7 @@ void smafa_db_destroy(smafa_db *db) {
     if (db->d_order) (void)hipFree(db->d_order);
     if (db->d_zone) (void)hipFree(db->d_zone);
     for (DevBuf *b : {&db->upload, &db->hits, &db->count, &db->scratch, &db->ctrs, &db->keys_a, &db->keys_b, &db->sort_tmp,
-                      &db->idx_a, &db->idx_b, &db->d_perm, &db->d_tab, &db->scratch_q.qrec,
+                      &db->idx_a, &db->idx_b, &db->d_perm, &db->d_tab, &db->d_inv, &db->scratch_q.qrec,
                       &db->scratch_q.thr, &db->scratch_q.cnt, &db->scratch_q2.qrec, &db->scratch_q2.thr, &db->scratch_q2.cnt,
                       &db->scratch_q3.qrec, &db->scratch_q3.thr, &db->scratch_q3.cnt, &db->index.kp, &db->index.dir,
                       &db->index.stats, &db->index.rows, &db->join.pos_of, &db->join.out, &db->join.cnt, &db->join.parent,
@@ -1646,6 +1657,7 @@ int smafa_scan_hits(smafa_db *db, const uint8_t *query_codes, uint64_t n_queries
 #include "read_table.hip.h"     // the frame of a call that scans a caller's query set and tabulates it: opening, span loop, table, host form
 #include "assign_abi.hip.h"     // the abundance table: its call (assign_reads) and the two smafa_db_assign entry points
 #include "classify_abi.hip.h"   // the LCA classification: its call (classify_reads) and the two smafa_db_classify entry points
+#include "subset_abi.hip.h"     // rows out of a store: a subset of it as a new store, its sequences back as code bytes
 #undef RC_TRY
 
 int smafa_distances(smafa_db *db, const uint8_t *query_codes, uint32_t *distances) try {

@@ -952,6 +952,61 @@ int smafa_consensus(const char *db_path, const char *labels_path, int out_fd, in
     return smafa::exception_code("smafa_consensus");
 }
 
+// --------------------------------------------------------------------------------------- subset
+// A list of sequence numbers, one per line in the first column; whatever tab-separated columns follow are ignored, duplicates
+// are allowed.  `text` is the whole file; -> listed[n] (1 where the number occurs), or SMAFA_ERR_INVALID naming the first line
+// that is not of that form or names a sequence the database does not have.
+static int parse_number_list(const char *who, const std::string &text, size_t n, std::vector<uint32_t> &listed) {
+    listed.assign(n, 0u);
+    size_t at = 0, line = 0;
+    const auto bad = [&](const char *what) {
+        return set_error(SMAFA_ERR_INVALID, "%s: list line %llu: %s", who, (unsigned long long)line + 1, what);
+    };
+    for (; at < text.size(); line++) {
+        size_t digits = 0;
+        uint64_t v = 0;
+        while (at < text.size() && text[at] >= '0' && text[at] <= '9' && digits < 11) v = v * 10 + (uint64_t)(text[at++] - '0'), digits++;
+        if (digits == 0 || digits >= 11) return bad("no sequence number");
+        if (at < text.size() && text[at] != '\t' && text[at] != '\n' && text[at] != '\r') return bad("the sequence number is not a number");
+        if (v >= n) return bad("the database has no sequence of that number");
+        listed[(size_t)v] = 1u;
+        while (at < text.size() && text[at] != '\n') at++;  // further columns
+        if (at < text.size()) at++;
+    }
+    return SMAFA_OK;
+}
+
+// A subset of a DB file's sequences (smafa_db_subset) saved as a packed store, "{new}\t{old}\n" per kept sequence printed.
+int smafa_subset(const char *db_path, const char *keep_path, const char *drop_path, const char *out_path, int out_fd, int device) try {
+    const char *const who = "smafa_subset";
+    StoreVerb v;
+    int rc = begin_store_verb(who, db_path, 0 /* no bound to check */, device, v, [&] {
+        if (!out_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL output path", who);
+        if (keep_path && drop_path) return set_error(SMAFA_ERR_INVALID, "%s: a keep list or a drop list, not both", who);
+        if (!keep_path && !drop_path) return set_error(SMAFA_ERR_INVALID, "%s: a keep list or a drop list is needed", who);
+        return (int)SMAFA_OK;
+    });
+    if (rc) return rc;
+    if (v.empty) return set_error(SMAFA_ERR_INVALID, "%s: the database holds no sequence: there is no store to take a subset of", who);
+    std::string text;
+    rc = read_whole(who, "list", keep_path ? keep_path : drop_path, text);
+    std::vector<uint32_t> listed;
+    if (!rc) rc = parse_number_list(who, text, v.n, listed);
+    if (rc) return rc;
+    std::string().swap(text);
+    DbGuard sub;
+    std::vector<uint32_t> old_of_new(v.n);
+    uint64_t k = 0;
+    rc = smafa_db_subset(v.store.db, listed.data(), drop_path ? 1 : 0, &sub.db, old_of_new.data(), old_of_new.size(), &k);
+    if (!rc) rc = smafa_db_save(sub.db, out_path);
+    if (!rc) rc = write_rows(out_fd, (size_t)k, kRowsPerWrite, [&](std::string &out, size_t i) { append_row(out, {(uint32_t)i, old_of_new[i]}); });
+    if (rc) return rc;
+    log_line(1, "%llu of %llu sequences kept in \"%s\", took %llu seconds", (unsigned long long)k, (unsigned long long)v.n, out_path, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_subset");
+}
+
 // ------------------------------------------------------------------------------------ density
 // The density-cluster label and the degree of every subject of a DB file (smafa_db_self_density), printed
 // "{i}\t{label}\t{degree}\n" in subject order; noise rows have the label -1.

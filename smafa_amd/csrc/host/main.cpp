@@ -30,6 +30,8 @@
 //           best hits and counted per (taxon, sample); or per read its anchor, distance, ties, depth and lineage)
 //   neighbours -d/--database FILE  --max-divergence INT  [--max-num-hits INT]   (this build only: per subject its neighbours
 //           within the bound, nearest first)
+//   subset  -d/--database FILE  (--keep FILE|- | --drop FILE|-)  --output FILE   (this build only: the listed sequences, or all but
+//           them, as a packed store of their own; "new<TAB>old" per kept sequence)
 // plus -v/--verbose and --quiet (logging only; results are the only thing on stdout).
 // Additions of this build: --device N (query, cluster), --gpus N (query, cluster: GPUs 0..N-1, one handle and host thread
 // each; the output does not depend on N), --devices a,b,.. (query, cluster: explicit list, entries may repeat),
@@ -131,7 +133,12 @@ static int usage(const char *msg, FILE *to = stderr) {
             "neighbours -d, --database <FILE>  --max-divergence <INT>  [--max-num-hits <INT>]  [--device <N>]  (not in the reference: the\n"
             "        neighbour lists of the database's own sequences, one \"i<TAB>j<TAB>divergence\" line per sequence i and neighbour j\n"
             "        within the bound, both directions of every pair, ordered by i, then divergence, then j; --max-num-hits: at most\n"
-            "        that many lines per i, the nearest, ties to the smaller j)\n");
+            "        that many lines per i, the nearest, ties to the smaller j)\n"
+            "subset  -d, --database <FILE>  (--keep <FILE|-> | --drop <FILE|->)  --output <FILE>  [--device <N>]  (not in the reference: the\n"
+            "        listed sequences of the database, or all but the listed ones, written to --output as a packed store that every\n"
+            "        command reads, renumbered in their old order; one \"new<TAB>old\" line per kept sequence; the list holds one sequence\n"
+            "        number per line in its first column (further columns are ignored, repeats allowed, -: stdin):\n"
+            "        smafa chimeras ... | awk '$2 == 1' | smafa subset -d DB --drop - --output CLEAN.db)\n");
     return 2;
 }
 
@@ -169,7 +176,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr, *taxonomy = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr, *taxonomy = nullptr, *keep = nullptr, *drop = nullptr, *output = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2, slack = 0;
     bool have_min_pts = false, have_since = false;
@@ -232,6 +239,12 @@ int main(int argc, char **argv) {
             if (!parse_u32(value(), &slack)) return usage("--slack needs an unsigned integer");
         } else if (a == "--per-sequence" && cmd == "table") {
             per_sequence = true;
+        } else if (a == "--keep" && cmd == "subset") {
+            if (!(keep = value())) return usage("--keep needs a file, or - for stdin");
+        } else if (a == "--drop" && cmd == "subset") {
+            if (!(drop = value())) return usage("--drop needs a file, or - for stdin");
+        } else if (a == "--output" && cmd == "subset") {
+            if (!(output = value())) return usage("--output needs a value");
         } else if (a == "--since" && cmd == "pairs") {
             const char *v = value();
             char *end = nullptr;
@@ -351,6 +364,11 @@ int main(int argc, char **argv) {
         if (!have_max_div) return usage("neighbours needs --max-divergence");
         if (max_hits == 0) return usage("--max-num-hits needs a positive integer");
         rc = smafa_neighbours(database, max_div, max_hits, 1, (int)device);
+    } else if (cmd == "subset") {
+        if (!database || !output) return usage("subset needs --database and --output");
+        if (keep && drop) return usage("--keep and --drop exclude each other");
+        if (!keep && !drop) return usage("subset needs --keep or --drop");
+        rc = smafa_subset(database, keep, drop, output, 1, (int)device);
     } else if (cmd == "count") {
         if (count_paths.empty()) return usage("count needs --input");
         rc = smafa_count(count_paths.data(), count_paths.size(), 1);
