@@ -15,6 +15,7 @@ LENGTHS = (1, 31, 32, 33, 60, 64, 65, 130)         # around the 32-column word a
 SIZES = (1, 255, 256, 257, 4095, 4096, 5000)       # around the 256-row tile; 4096 is the first sorted append
 PLANES = {"nt2": 2, "nt3": 3, "aa": 5}
 MASKS = ("all", "none", "first", "last", "last_tile", "every_second", "random10", "random90")
+SUBSET_CALL = ["subset::keep_flags_kernel", "subset::run_ends_kernel", "subset::move_rows_kernel", "smafa::zone_kernel"]  # one subset call's launches
 
 
 def alphabet_of(kind):

@@ -1,33 +1,24 @@
-"""The kernel census of the components' namespace (CPU): the smafa_cc:: kernels in the gfx950 code object of the built
-libsmafa_amd.so must be exactly the ones tabled here, each beside the GPU test that runs it.  The components add no kernel
-to smafa:: or smafa_join:: (tests/test_kernel_census.py and tests/test_join_kernel_census.py pin those at 199 and at three
-names, and keep doing so)."""
+"""The kernel census of the components' namespace (CPU), as it stood before tests/test_namespace_census.py: the smafa_cc::
+kernels in the gfx950 code object are exactly the tabled ones, each beside the GPU test that names it.  The table is tests/kernel_namespaces.py's and the reader tests/code_object.py's; nothing imports this module."""
 import os
 import re
 
 import pytest
 
-from test_join_kernel_census import ROOT, binary_kernels  # noqa: F401  (the fixture that lists the code object's kernels)
+from code_object import ROOT, kernel_names
+from kernel_namespaces import NAMESPACES
 
-# kernel -> the GPU test that runs it and asserts it by name (smafa_last_call_kernels)
-CC_KERNELS = {
-    "smafa_cc::init_labels_kernel": "tests/test_gpu_components.py::test_dense_store",
-    "smafa_cc::link_rows_kernel": "tests/test_gpu_components.py::test_dense_store",
-    "smafa_cc::flatten_labels_kernel": "tests/test_gpu_components.py::test_against_the_join_and_the_query_path_at_scale",
-}
+CC_KERNELS = NAMESPACES["smafa_cc::"]
 
 
-def test_components_kernels_are_the_tabled_ones(binary_kernels):  # noqa: F811
+@pytest.fixture(scope="module")
+def binary_kernels():
+    return kernel_names()
+
+
+def test_components_kernels_are_the_tabled_ones(binary_kernels):
     found = {n for n in binary_kernels if n.startswith("smafa_cc::")}
     assert found == set(CC_KERNELS), (sorted(found - set(CC_KERNELS)), sorted(set(CC_KERNELS) - found))
-
-
-def test_other_namespaces_are_unchanged(binary_kernels):  # noqa: F811
-    assert len({n for n in binary_kernels if n.startswith("smafa::")}) == 199
-    assert {n for n in binary_kernels if n.startswith("smafa_join::")} == {
-        "smafa_join::store_records_kernel", "smafa_join::inverse_order_kernel", "smafa_join::join_filter_kernel"}
-    others = {n for n in binary_kernels if not n.startswith(("smafa::", "smafa_join::", "smafa_cc::"))}
-    assert not [n for n in others if "label" in n or "link_rows" in n], others
 
 
 def test_tabled_tests_exist_and_name_their_kernel():

@@ -11,9 +11,11 @@ import oracle
 import smafa_amd
 from smafa_amd import _lib
 from self_join_cases import replaned_case
-from subset_cases import (KINDS, LENGTHS, MASKS, PLANES, SIZES, DeviceArray, expected_subset, keep_mask, make_store,
+from kernel_namespaces import NAMESPACES
+from subset_cases import (KINDS, LENGTHS, MASKS, PLANES, SIZES, SUBSET_CALL, DeviceArray, expected_subset, keep_mask, make_store,
                           random_codes, two_family_case)
-from test_subset_kernel_census import SUBSET_CALL, SUBSET_KERNELS
+
+SUBSET_KERNELS = NAMESPACES["subset::"]
 
 pytestmark = pytest.mark.gpu
 

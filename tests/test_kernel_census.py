@@ -4,64 +4,16 @@ the kernels of its EXEMPT map (each with the existing test that runs it).  A new
 does a table entry the binary no longer has."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from code_object import ROOT, kernel_names
 from kernel_census_table import CENSUS, EXEMPT, SWITCHES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "smafa_amd", "lib", "libsmafa_amd.so")
-LLVM = "/opt/rocm/llvm/bin"
-TOOLS = {t: os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-
-
-def _tool(name):
-    path = TOOLS.get(name) or shutil.which(name)
-    return path if path and os.access(path, os.X_OK) else None
-
-
-def _strip_signature(name):
-    """'void smafa::k<1, 2>(args)' -> 'smafa::k<1, 2>'"""
-    name = name.strip()
-    if name.startswith("void "):
-        name = name[5:]
-    depth = 0
-    for i, ch in enumerate(name):
-        if ch == "<":
-            depth += 1
-        elif ch == ">":
-            depth -= 1
-        elif ch == "(" and depth == 0:
-            return name[:i]
-    return name
 
 
 @pytest.fixture(scope="module")
-def binary_kernels(tmp_path_factory):
-    missing = [t for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "c++filt") if not _tool(t)]
-    if missing:
-        pytest.skip("kernel census needs the LLVM tools of ROCm and c++filt: missing %s" % ", ".join(missing))
-    if not os.path.exists(LIB):
-        import smafa_amd
-
-        smafa_amd.build()
-    tmp = tmp_path_factory.mktemp("census")
-    fatbin, host, co = (str(tmp / n) for n in ("fatbin", "host.so", "gfx950.co"))
-    subprocess.run([_tool("llvm-objcopy"), "--dump-section=.hip_fatbin=" + fatbin, LIB, host], check=True, capture_output=True)
-    listed = subprocess.run([_tool("clang-offload-bundler"), "--list", "--type=o", "--input=" + fatbin], check=True,
-                            capture_output=True, text=True).stdout.split()
-    target = [t for t in listed if t.endswith("gfx950")]
-    assert len(target) == 1, listed
-    subprocess.run([_tool("clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fatbin, "--targets=" + target[0],
-                    "--output=" + co], check=True, capture_output=True)
-    syms = subprocess.run([_tool("llvm-readelf"), "-s", "--wide", co], check=True, capture_output=True, text=True).stdout
-    mangled = sorted({f[-1][: -len(".kd")] for f in (ln.split() for ln in syms.splitlines()) if f and f[-1].endswith(".kd")})
-    demangled = subprocess.run([_tool("c++filt")], input="\n".join(mangled), check=True, capture_output=True,
-                               text=True).stdout.splitlines()
-    assert len(demangled) == len(mangled)
-    return {n for n in map(_strip_signature, demangled) if n.startswith("smafa::")}
+def binary_kernels():
+    return {n for n in kernel_names() if n.startswith("smafa::")}
 
 
 def test_every_kernel_in_the_binary_is_mapped(binary_kernels):
