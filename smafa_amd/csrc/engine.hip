@@ -558,7 +558,7 @@ static int qset_fill(smafa_qset *qs, smafa_db *db, const uint8_t *query_codes, u
     qs->nq = n_queries;
     qs->serial = g_qset_serial.fetch_add(1);
     // whole 64-query chunks plus one: a chunk staged by scan_zone_kernel's LDS-DMA is always 64 records from wherever its
-    // query block starts (SMAFA_ZONE_FULL_DMA), so up to 63 records past the last query are read (zeros, never used)
+    // query block starts (kernels.hip.h, dma()), so up to 63 records past the last query are read (zeros, never used)
     const uint64_t padded = std::max<uint64_t>((n_queries + 63) / 64 * 64, 64) + 64;
     int rc = qs->qrec.ensure(padded * db->QS * sizeof(uint32_t));
     if (!rc) rc = qs->thr.ensure(padded * sizeof(uint32_t));

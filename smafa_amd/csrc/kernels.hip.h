@@ -52,37 +52,22 @@ __host__ __device__ constexpr int scan_min_waves(int ps, int w, int t) {
     const int regs = t * ps * w * 4 + 40;
     return regs <= 64 ? 8 : regs <= 80 ? 6 : regs <= 96 ? 5 : regs <= 128 ? 4 : regs <= 168 ? 3 : 2;
 }
-#ifndef SMAFA_CASCADE
-#define SMAFA_CASCADE 1  // 1: a one-word first-level bound in front of the folded bound (+7 % aa, +4 % nt measured)
-#endif
-#ifndef SMAFA_WIDE_AND_PAIR
-#define SMAFA_WIDE_AND_PAIR 1  // scan_wide_kernel keeps the two-subjects-per-popcount form of level 2: it only runs at bounds
-                               // level 1 prunes at, where the form is the cheaper one (one-word stores, 10M x 20 aa, bound 3:
-                               // 7.1 ms vs 8.6 ms per subject — profiles/r02_short_check.txt)
-#endif
-#ifndef SMAFA_SIGN_COMPARE
-#define SMAFA_SIGN_COMPARE 1  // scan_kernel's full comparison: one sign test per query instead of a compare per subject
-#endif
-#ifndef SMAFA_AND_PAIR
-#define SMAFA_AND_PAIR 0  // 1: the folded bound takes two subjects per popcount (popcount(a & b) <= both).  +5 % in round 1 at
-                          // bound 5; nothing today at tight bounds (the zone level runs in front), and at bounds 9-13 it
-                          // lets every query through where the per-subject fold still rejects them: scan_kernel, 10 000
-                          // queries x 10M aa, bound 10: 28.7 -> 8.4 ms (profiles/r02_bound_probe.txt)
-#endif
 
 // The plane the prefilter looks at: always plane 0.  Codes are re-coded PER COLUMN when a store is laid out (the
 // distance only depends on equality of codes within a column, so any per-column injective map keeps every result):
 // bit 0 of the re-coded symbol splits the column's letters into two sets of nearly equal total frequency, which makes
 // a mismatch flip the filter bit as often as the column allows (host: choose_layout() in engine.hip).  Without
 // statistics the nucleotide map is A=0 C=2 G=1 T=3 N=4: bit 0 separates {A,C} from {G,T}, so it sees both transitions.
-__host__ __device__ constexpr int filter_plane(int) { return 0; }
+constexpr int kFilterPlane = 0;
 // slot of word w of plane p inside a record
 // The bound sits right after the first two filter words, so the first uint4 of a record holds everything
 // levels 1 and 2 of scan_wide_kernel need: [f0 f1 bound f2 f3 ... | other planes] ([f0 bound] for one word).
 __host__ __device__ constexpr int bound_slot(int words) { return words < 2 ? words : 2; }
+// (`p < 0 ? p : p - 1`: no plane number is negative, but the kernels that pass one at run time — scan_generic_kernel,
+// kth_seed_kernel<0, 0, 0>, distances_kernel, the record kernels of the join and the delta join — cast it from unsigned, where the
+// compiler cannot tell; plain `p - 1` takes five instructions out of each of them, which is a change of their code)
 __host__ __device__ constexpr int qslot(int planes, int words, int p, int w) {
-    return p == filter_plane(planes) ? (w < bound_slot(words) ? w : w + 1)
-                                     : words + 1 + (p < filter_plane(planes) ? p : p - 1) * words + w;
+    return p == 0 ? (w < bound_slot(words) ? w : w + 1) : words + 1 + (p < 0 ? p : p - 1) * words + w;
 }
 
 struct ScanArgs {
@@ -146,6 +131,40 @@ __device__ __forceinline__ uint4 ld_nt(const uint4 *p) {
 // a | b | c through the fast bitop3 path (v_or3_b32 itself issues at the slow rate)
 __device__ __forceinline__ uint32_t or3(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0xFE);
+}
+
+// ---- What the scan kernels share.  A kernel uses one of these only where its code stays what it was, instruction for instruction:
+// scan_zone_kernel keeps its own read_record (33 of its 36 instantiations moved with this one), scan_wide_kernel its own fold (24).
+// vectors [from, to) of the query record at `rec` (LDS or global) into its words
+template <int RS>
+__device__ __forceinline__ void read_record(const uint4 *rec, uint32_t (&qw)[RS], int from, int to) {
+#pragma unroll
+    for (int v = from; v < to; v++) {
+        const uint4 x = rec[v];
+        qw[4 * v + 0] = x.x;
+        qw[4 * v + 1] = x.y;
+        qw[4 * v + 2] = x.z;
+        qw[4 * v + 3] = x.w;
+    }
+}
+// (The exact comparison over all planes is NOT shared: as a template over a callable subject source — (p, w) -> uint4, a tile in
+// registers or streamed — it changed the schedule or the register assignment of instantiations of every kernel that took it,
+// scan_kernel, scan_lazy_kernel, scan_zone_kernel and scan_zone_few_kernel alike, so each keeps its own text:
+// profiles/r30_kernel_identity.txt.)
+// The filter plane's lower bound for a lane's four subjects: words 1..W-1 (subjects' fw(w), the query's qf(w)) OR-ed onto the
+// word-0 masks m0..m3, one popcount per subject on top of ~bound — the sign bit of the result says "one of the four may be within
+// the bound".  (Two subjects per popcount, popcount(a & b) <= both, was the form of round 1: see scan_kernel.)
+template <int W, class Fw, class Qf>
+__device__ __forceinline__ uint32_t fold_sign(uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3, Fw &&fw, Qf &&qf, uint32_t nu) {
+#pragma unroll
+    for (int w = 1; w < W; w++) {
+        const uint4 v = fw(w);
+        m0 = or_xor(m0, v.x, qf(w));
+        m1 = or_xor(m1, v.y, qf(w));
+        m2 = or_xor(m2, v.z, qf(w));
+        m3 = or_xor(m3, v.w, qf(w));
+    }
+    return or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu, __builtin_popcount(m2) + nu) | (__builtin_popcount(m3) + nu);
 }
 
 // number of set bits of a wave mask in the lanes below the calling lane (v_mbcnt_lo/hi): a lane's rank among the
@@ -293,13 +312,10 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
     constexpr int RS = qrec_stride(PQ, W);  // words per record
     constexpr int RV = RS / 4;              // uint4 per record
     constexpr int NV = (kChunk * RV + 255) / 256;
-    constexpr int FP = filter_plane(PQ);
+    constexpr int FP = kFilterPlane;
     static_assert(FP < PS && PS <= PQ, "the filter plane must be one the subjects store");
     constexpr int BS = bound_slot(W);
     constexpr int HV = (W + 1 + 3) / 4;  // uint4s holding the filter words + bound slot
-    // two subjects per popcount only where the folded mask is dense enough to survive an AND (W >= 2);
-    // with a single word the bound is taken per subject
-    constexpr bool kPair = SMAFA_AND_PAIR && W > 1;
     __shared__ uint4 stage[2][kChunk * RV];
     __shared__ RowStage rs;
     int buf = 0;  // LDS buffer of the chunk being computed = parity of the row stage it appends to
@@ -361,10 +377,7 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
 
     // full comparison of one query against this lane's 4*T subjects; qw = the whole record
     auto full_compare = [&](const uint32_t(&qw)[RS], uint32_t q) {
-        const uint32_t U = ~qw[BS];
-        uint32_t lo = 0xffffffffu;  // SEED only
-#if SMAFA_SIGN_COMPARE
-        if (!SEED) {
+        if (!SEED) {  // (a plain `if`: what the lambda captures, and with it every instantiation's code, stays as it was)
             // The distances are accumulated on top of ~bound (v_bcnt's accumulator adds it for free), so "within the bound"
             // is the sign bit, the 4*T sign bits are OR-ed, and ONE compare + ballot per query replaces a compare and a
             // branch per subject (the launch with the prefilter off ran 90 scalar instructions per 1024 pairs, most of them
@@ -406,61 +419,44 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
                 for (int k = 0; k < 4; k++)
                     if (live && (int32_t)dd[t][k] < 0 && subj0 + k < a.n_subjects) emit(a, rs, buf, q, subj0 + k, dd[t][k] - nuU);
             }
-            return;
-        }
-#endif
-#pragma unroll
-        for (int t = 0; t < T; t++) {
-            uint32_t d[4];
-#pragma unroll
-            for (int w = 0; w < W; w++) {
-                uint32_t extra = 0;  // query bits in planes no subject has: a mismatch against every subject
-#pragma unroll
-                for (int p = PS; p < PQ; p++) extra |= qw[qslot(PQ, W, p, w)];
-                uint32_t m0 = extra, m1 = extra, m2 = extra, m3 = extra;
-#pragma unroll
-                for (int p = 0; p < PS; p++) {
-                    const uint4 v = s[t][p * W + w];
-                    const uint32_t qv = qw[qslot(PQ, W, p, w)];
-                    const bool first = p == 0 && PS == PQ;
-                    m0 = first ? (v.x ^ qv) : or_xor(m0, v.x, qv);
-                    m1 = first ? (v.y ^ qv) : or_xor(m1, v.y, qv);
-                    m2 = first ? (v.z ^ qv) : or_xor(m2, v.z, qv);
-                    m3 = first ? (v.w ^ qv) : or_xor(m3, v.w, qv);
-                }
-                d[0] = (w ? d[0] : 0u) + __builtin_popcount(m0);
-                d[1] = (w ? d[1] : 0u) + __builtin_popcount(m1);
-                d[2] = (w ? d[2] : 0u) + __builtin_popcount(m2);
-                d[3] = (w ? d[3] : 0u) + __builtin_popcount(m3);
-            }
-            const uint32_t subj0 = (tile0 + t) * kWaveTile + lane * 4u;
-            const bool live = tile0 + t < a.tile_end;  // a trailing tile slot holds a copy of another tile: ignore it
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const bool real = live && subj0 + k < a.n_subjects;
-                if (SEED) {
-                    if (real) lo = min(lo, d[k]);
-                } else if (real && d[k] <= U) {
-                    emit(a, rs, buf, q, subj0 + k, d[k]);
-                }
-            }
-        }
-        if (SEED) {
+        } else {
             // seed pass for the running minimum (its own instantiation: this code in the hot kernel cost 3.5 %
             // through register allocation alone): one atomicMin per wave instead of one per qualifying pair
+            const uint32_t U = ~qw[BS];
+            uint32_t lo = 0xffffffffu;
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                uint32_t d[4];
+#pragma unroll
+                for (int w = 0; w < W; w++) {
+                    uint32_t extra = 0;  // query bits in planes no subject has: a mismatch against every subject
+#pragma unroll
+                    for (int p = PS; p < PQ; p++) extra |= qw[qslot(PQ, W, p, w)];
+                    uint32_t m0 = extra, m1 = extra, m2 = extra, m3 = extra;
+#pragma unroll
+                    for (int p = 0; p < PS; p++) {
+                        const uint4 v = s[t][p * W + w];
+                        const uint32_t qv = qw[qslot(PQ, W, p, w)];
+                        const bool first = p == 0 && PS == PQ;
+                        m0 = first ? (v.x ^ qv) : or_xor(m0, v.x, qv);
+                        m1 = first ? (v.y ^ qv) : or_xor(m1, v.y, qv);
+                        m2 = first ? (v.z ^ qv) : or_xor(m2, v.z, qv);
+                        m3 = first ? (v.w ^ qv) : or_xor(m3, v.w, qv);
+                    }
+                    d[0] = (w ? d[0] : 0u) + __builtin_popcount(m0);
+                    d[1] = (w ? d[1] : 0u) + __builtin_popcount(m1);
+                    d[2] = (w ? d[2] : 0u) + __builtin_popcount(m2);
+                    d[3] = (w ? d[3] : 0u) + __builtin_popcount(m3);
+                }
+                const uint32_t subj0 = (tile0 + t) * kWaveTile + lane * 4u;
+                const bool live = tile0 + t < a.tile_end;  // a trailing tile slot holds a copy of another tile: ignore it
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (live && subj0 + k < a.n_subjects) lo = min(lo, d[k]);
+            }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) lo = min(lo, (uint32_t)__shfl_xor((int)lo, off, 64));
             if (lane == 0 && lo < U) atomicMin(a.thr + q, lo);
-        }
-    };
-    auto read_record = [&](const uint4 *rec, uint32_t(&qw)[RS], int from, int to) {
-#pragma unroll
-        for (int v = from; v < to; v++) {
-            const uint4 x = rec[v];
-            qw[4 * v + 0] = x.x;
-            qw[4 * v + 1] = x.y;
-            qw[4 * v + 2] = x.z;
-            qw[4 * v + 3] = x.w;
         }
     };
 
@@ -488,14 +484,14 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
                 for (uint32_t i = 0; i < nqc; i++, rec += RV) {
                     uint32_t qw[RS];
                     // fast path: filter-plane words + bound slot only (FOLD 2: the next plane's words as well)
-                    constexpr int HV2 = FOLD == 3 ? RV : FOLD == 2 ? (qslot(PQ, W, filter_plane(PQ) == 0 ? 1 : 0, W - 1) + 4) / 4 : HV;
+                    constexpr int HV2 = FOLD == 3 ? RV : FOLD == 2 ? (qslot(PQ, W, 1, W - 1) + 4) / 4 : HV;
                     read_record(rec, qw, 0, HV2 > HV ? HV2 : HV);
                     const uint32_t nu = qw[BS];
                     uint32_t any = 0;
                     bool go = true;  // wave-uniform: does this query reach the folded bound?
-#if SMAFA_CASCADE
                     // level 1: word 0 of the filter plane only — popcount(s ^ q) over 32 columns, one xor + one
                     // popcount per subject; weaker than the folded bound below but cheaper, and still exact
+                    // (+7 % aa, +4 % nt against the folded bound alone)
                     if (W > 1 && l1) {
                         uint32_t any1 = 0;
 #pragma unroll
@@ -509,11 +505,14 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
                         go = __ballot((int32_t)any1 < 0) != 0ull;  // nobody can qualify: next query
                         level1_passes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(level1_passes + (go ? 1u : 0u)));
                     }
-#endif
                     if (go) {
 #pragma unroll
                         for (int t = 0; t < T; t++) {
-                            // lower bound on the filter plane, folded over the words
+                            // lower bound on the filter plane, folded over the words, one popcount per subject.  (Two subjects
+                            // per popcount, popcount(a & b) <= both: +5 % in round 1 at bound 5, nothing at tight bounds since
+                            // the zone level runs in front, and at bounds 9-13 it lets every query through where this fold
+                            // still rejects them: 10 000 queries x 10M aa, bound 10: 28.7 ms paired, 8.4 ms this way —
+                            // profiles/r02_bound_probe.txt.)
                             uint32_t m0 = s[t][FP * W].x ^ qw[0], m1 = s[t][FP * W].y ^ qw[0];
                             uint32_t m2 = s[t][FP * W].z ^ qw[0], m3 = s[t][FP * W].w ^ qw[0];
 #pragma unroll
@@ -523,16 +522,12 @@ __global__ __launch_bounds__(256, scan_min_waves(PS, W, T)) void scan_kernel(con
                                 m2 = or_xor(m2, s[t][FP * W + w].z, qw[qslot(PQ, W, FP, w)]);
                                 m3 = or_xor(m3, s[t][FP * W + w].w, qw[qslot(PQ, W, FP, w)]);
                             }
-                            if (kPair) {
-                                // popcount(a & b) <= min(popcount a, popcount b): one popcount bounds two subjects
-                                const uint32_t t0 = __builtin_popcount(m0 & m1) + nu, t2 = __builtin_popcount(m2 & m3) + nu;
-                                any = t ? or3(any, t0, t2) : (t0 | t2);
-                            } else if (FOLD == 2) {
+                            if (FOLD == 2) {
                                 // FOLD 2 (launches whose bound is 18..32 at two words, 3 planes and more): the distance
                                 // over TWO planes, word by word — a column whose letters differ shows in the filter
                                 // plane or in the next one three times out of four (~45 of 60 columns for unrelated
                                 // sequences), for half the instructions of the full comparison
-                                constexpr int FP2 = FP == 0 ? 1 : 0;
+                                constexpr int FP2 = 1;
                                 uint32_t t0 = nu, t1 = nu, t2 = nu, t3 = nu;
 #pragma unroll
                                 for (int w = 0; w < W; w++) {
@@ -650,11 +645,10 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
     constexpr int RS = qrec_stride(PQ, W);
     constexpr int RV = RS / 4;
     constexpr int NV = (kChunk * RV + 255) / 256;
-    constexpr int FP = filter_plane(PQ);
+    constexpr int FP = kFilterPlane;
     static_assert(FP < PS && PS <= PQ, "the filter plane must be one the subjects store");
     constexpr int BS = bound_slot(W);
     constexpr int HV = (W + 1 + 3) / 4;
-    constexpr bool kPair = SMAFA_AND_PAIR && W > 1;  // see scan_kernel
     __shared__ uint4 stage[2][kChunk * RV];
     __shared__ RowStage rs;
     int buf = 0;  // LDS buffer of the chunk being computed = parity of the row stage it appends to
@@ -710,16 +704,6 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
             if (idx < nqc * RV) stage[b][idx] = pre[v];
         }
     };
-    auto read_record = [&](const uint4 *rec, uint32_t(&qw)[RS], int from, int to) {
-#pragma unroll
-        for (int v = from; v < to; v++) {
-            const uint4 x = rec[v];
-            qw[4 * v + 0] = x.x;
-            qw[4 * v + 1] = x.y;
-            qw[4 * v + 2] = x.z;
-            qw[4 * v + 3] = x.w;
-        }
-    };
     auto load_tile = [&](uint32_t tile, uint4(&s)[PS * W]) {  // all planes of one wave tile: L2/HBM -> registers
         const uint4 *src = planes + (size_t)tile * (PS * W * 64) + lane;
 #pragma unroll
@@ -765,18 +749,6 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
                 if (d[k] <= U && subj0 + k < a.n_subjects) emit(a, rs, buf, q, subj0 + k, d[k]);
         }
     };
-    // the filter plane of tile slot t folded over its words against the record's filter words
-    auto fold = [&](int t, const uint32_t(&qw)[RS], uint32_t &m0, uint32_t &m1, uint32_t &m2, uint32_t &m3) {
-        m0 = f[t][0].x ^ qw[0], m1 = f[t][0].y ^ qw[0];
-        m2 = f[t][0].z ^ qw[0], m3 = f[t][0].w ^ qw[0];
-#pragma unroll
-        for (int w = 1; w < W; w++) {
-            m0 = or_xor(m0, f[t][w].x, qw[qslot(PQ, W, FP, w)]);
-            m1 = or_xor(m1, f[t][w].y, qw[qslot(PQ, W, FP, w)]);
-            m2 = or_xor(m2, f[t][w].z, qw[qslot(PQ, W, FP, w)]);
-            m3 = or_xor(m3, f[t][w].w, qw[qslot(PQ, W, FP, w)]);
-        }
-    };
 
     if (q0 < q1) {
         fetch(q0);
@@ -815,7 +787,7 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
                         go = __ballot((int32_t)any1 < 0) != 0ull;
                         level1_passes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(level1_passes + (go ? 1u : 0u)));
                     }
-                    if (go) {  // level 2: the filter plane folded over its words, two subjects per popcount
+                    if (go) {  // level 2: the filter plane folded over its words, one popcount per subject (see scan_kernel)
                         uint32_t any = 0;
                         uint32_t tsign[T];
 #pragma unroll
@@ -832,12 +804,8 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
                                 }
                                 tsign[t] = or3(t0, t1, t2) | t3;
                             } else {
-                                uint32_t m0, m1, m2, m3;
-                                fold(t, qw, m0, m1, m2, m3);
-                                tsign[t] = kPair ? ((__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu))
-                                                 : (or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                                        __builtin_popcount(m2) + nu) |
-                                                    (__builtin_popcount(m3) + nu));
+                                tsign[t] = fold_sign<W>(f[t][0].x ^ qw[0], f[t][0].y ^ qw[0], f[t][0].z ^ qw[0], f[t][0].w ^ qw[0],
+                                                        [&](int w) { return f[t][w]; }, [&](int w) { return qw[qslot(PQ, W, FP, w)]; }, nu);
                             }
                             any |= tsign[t];
                         }
@@ -849,23 +817,6 @@ __global__ __launch_bounds__(256, lazy_min_waves(PS, W, T)) void scan_lazy_kerne
                             for (int t = 0; t < T; t++)
                                 if (__ballot((int32_t)tsign[t] < 0) != 0ull) live |= 1u << t;
                             live = (uint32_t)__builtin_amdgcn_readfirstlane((int)live);
-                            if (kPair) {
-                                // The two-subject AND passes whenever ONE of the pair is close on this plane (a
-                                // relative of the query next to anything): before fetching a tile, look at its
-                                // subjects one by one.  Rare path: recomputing the masks is cheaper than keeping them.
-#pragma unroll
-                                for (int t = 0; t < T; t++) {
-                                    if ((live >> t) & 1u) {
-                                        uint32_t m0, m1, m2, m3;
-                                        fold(t, qw, m0, m1, m2, m3);
-                                        const uint32_t each = or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                                                  __builtin_popcount(m2) + nu) |
-                                                              (__builtin_popcount(m3) + nu);
-                                        if (__ballot((int32_t)each < 0) == 0ull) live &= ~(1u << t);
-                                    }
-                                }
-                                live = (uint32_t)__builtin_amdgcn_readfirstlane((int)live);
-                            }
                             while (live) {  // ONE copy of the comparison code, whatever T is
                                 const uint32_t t = (uint32_t)__builtin_ctz(live);
                                 live &= live - 1;
@@ -934,32 +885,13 @@ __device__ __forceinline__ void emit_direct(const ScanArgs &a, uint32_t q, uint3
     if (g < a.cap) a.hits[g] = h;
 }
 
-constexpr int kZoneTiles = SMAFA_ZONE_TILES;
-
+// ---- Build-time tunables of the zone kernel (-D, for A/B builds through tools/variants.sh).  Numbers only: none of them picks a
+// code path.  (Tiles per wave and waves per workgroup — SMAFA_ZONE_TILES, SMAFA_ZONE_TILES_DIRECT_AA, SMAFA_ZONE_WG_WAVES — are the
+// host's too and sit in scan_plan.h.)
 // Waves per SIMD the register budget must allow.  The survivor loop is a chain of dependent slow-class instructions
 // (v_readlane -> scalar-operand xor -> bcnt -> or -> cmp -> branch), so one more resident wave pays as long as the hot
 // path does not spill: measured (profiles/r02_zone_variants.txt) aa 60 columns 2.55 -> 2.45 ms at 5 waves (3.06 at 6:
 // spills), nt 60 columns 6.38 -> 5.91 ms at 6 waves.  What caps it is the dense fallback's tile (PS * W vectors).
-#ifndef SMAFA_ZONE_WAVES_10
-#define SMAFA_ZONE_WAVES_10 5  // waves per SIMD asked for where a tile holds 5..10 vectors (aa 60 columns: 10)
-#endif
-#ifndef SMAFA_ZONE_SGPR_ZONE
-#define SMAFA_ZONE_SGPR_ZONE 1  // 1: word 0's zone words of the wave's tiles live in scalar registers (those of tiles 1.. end up
-                                // in spilled VGPR lanes); 0: they are read out of their VGPR lane where they are used
-#endif
-#ifndef SMAFA_ZONE_VGPR_MASK
-#define SMAFA_ZONE_VGPR_MASK 6  // word 0's zone masks also in vector registers for stores of up to this many vectors per tile
-                                // (nucleotides: -2.3 %; the amino-acid kernel has no register to spare: profiles/r03_zone_variants.txt)
-#endif
-#ifndef SMAFA_ZONE_OPAQUE_BUF
-#define SMAFA_ZONE_OPAQUE_BUF 1  // 1: the rare levels see the chunk parity through an opaque copy (their LDS addresses are formed there)
-#endif
-#ifndef SMAFA_ZONE_FULL_DMA
-#define SMAFA_ZONE_FULL_DMA 1  // 1: a staged chunk is always 64 whole records (the record array is padded by one chunk)
-#endif
-#ifndef SMAFA_ZONE_NLIVE
-#define SMAFA_ZONE_NLIVE 1  // 1: "tile slot t is inside the range" is ONE scalar (the number of live slots) instead of T lane masks
-#endif
 #ifndef SMAFA_ZONE_WAVES_4
 #define SMAFA_ZONE_WAVES_4 6  // waves per SIMD asked for where a tile holds up to 4 vectors (the 2-bit nucleotide store)
 #endif
@@ -968,24 +900,18 @@ constexpr int kZoneTiles = SMAFA_ZONE_TILES;
                               // 8 bytes of scratch instead of 82 / none, one more resident wave: 3.09 -> 2.98 ms (7: the same;
                               // profiles/r04_zone_variants.txt)
 #endif
+#ifndef SMAFA_ZONE_WAVES_10
+#define SMAFA_ZONE_WAVES_10 5  // ... where a tile holds 5..10 vectors (aa 60 columns: 10)
+#endif
 #ifndef SMAFA_ZONE_WAVES_DIRECT_AA
 #define SMAFA_ZONE_WAVES_DIRECT_AA 7  // the unstaged five-plane two-word kernel (see zone_tiles)
 #endif
-// Pigeonhole key test between the zone level and level 1 (unstaged two-word kernels).  The zone level counts k columns in
-// which every subject of a tile mismatches the query; a hit in that tile then has at most b = bound - k mismatches in the
-// other columns.  Take disjoint column sets of the filter plane — Y: word 0 bits 32-KB..31, X: word 1 & key_xmask, Z: word
-// 1 bits key_zlo..key_zlo+KB-1 (ScanArgs; bits past the row length are zero in subjects and queries alike) — and let a key be
-// a subject's filter bits on one set.  A hit matches the query exactly on at least NS - b of the NS sets, once the query's
-// bits on the columns the tile shares are replaced by the tile's own (q ^ ((q ^ common) & shared): the zone level's masked
-// word, already at hand).  So with one 2^KB-bit bitmap per (tile, set) of the keys its subjects have — built per wave in LDS
-// in the prologue — a survivor whose found sets and budget b add up to less than NS cannot have a hit in the tile.  Lane per
-// query like the zone level: 64 queries at a time, one LDS gather per set, instead of level 1's serial iteration per survivor.
-// Extra keys in a bitmap (padding rows of the last tile) only let more through: the row list is the same set.
-#ifndef SMAFA_ZONE_KEYS
-#define SMAFA_ZONE_KEYS 3  // key sets: 0 (no key test), 2 (Y and X) or 3 (Y, X and Z)
+#ifndef SMAFA_ZONE_VGPR_MASK
+#define SMAFA_ZONE_VGPR_MASK 6  // word 0's zone masks also in vector registers for stores of up to this many vectors per tile
+                                // (nucleotides: -2.3 %; the amino-acid kernel has no register to spare: profiles/r03_zone_variants.txt)
 #endif
 #ifndef SMAFA_ZONE_KEY_BITS
-#define SMAFA_ZONE_KEY_BITS 12  // bits per key: 2^KB-bit bitmaps (12: 512 bytes per tile and set)
+#define SMAFA_ZONE_KEY_BITS 12  // bits per key of the key test below: 2^KB-bit bitmaps (12: 512 bytes per tile and set)
 #endif
 // ScanArgs::key_gate by alphabet (run-time: SMAFA_ZONE_KEY_GATE, for both; 65 turns the test off).  Same box, ms per launch
 // (profiles/r05_zone_keys.txt): aa 10M x 10k bound 5, gate 0 / 1 / 2 / 3 / 5: 0.566 / 0.562 / 0.575 / 0.564 / 0.570 (no test: 1.67);
@@ -996,46 +922,53 @@ constexpr int kZoneTiles = SMAFA_ZONE_TILES;
 #ifndef SMAFA_ZONE_KEY_GATE_NT
 #define SMAFA_ZONE_KEY_GATE_NT 2  // nucleotides
 #endif
-// 1: a wave whose tiles share no key column (zone mask & key columns == 0 for every tile slot: the sorted 10M-row stores, whose
-// ~15 shared bits are word 0's leading columns) forms the three keys' LDS addresses and bit positions ONCE per chunk — substituting
-// the tile's shared bits is the identity on the key columns there — and runs the chunk in two phases: zone level and key test of
-// all its tiles, then the survivor loops (the hoisted values die before the first loop, whose rare levels use every register).
-// Waves with a tile that does share a key column (dense families, duplicates, small stores) keep the per-tile form.
-// 0: the per-tile form only.
-#ifndef SMAFA_ZONE_KEY_HOIST
-#define SMAFA_ZONE_KEY_HOIST 1
-#endif
-// 1: level 2 of the key-test kernels (two filter words) touches neither global nor scalar memory.  The query's filter word 1 is the
-// head word lane i already holds (v_readlane, like word 0), the tile's filter word 1 — loaded once in the prologue for the bitmaps —
-// stays with the wave (zone_f1_home), and the query record is read behind level 2's rejections, for level 3 alone.
-// 0: the record through scalar loads and the tile's word 1 from L2 in front of level 2, one serial round trip per level-2 entry.
-#ifndef SMAFA_ZONE_L2_LANES
-#define SMAFA_ZONE_L2_LANES 1
-#endif
-// Where the tile's filter word 1 lives between the prologue and level 2 — 0: nowhere (read from L2 per entry), 1: LDS, one uint4
-// per lane and tile slot, lane-linear (conflict-free ds_read_b128; 1 KB per slot and wave), 2: registers (4 VGPRs per slot, fetched
-// again behind the dense walk like word 0).  Amino acids, 2 tiles at 7 waves per SIMD: 6144 B of bitmaps + 4096 B per two-wave
-// workgroup, 14 workgroups = 140 KB of the CU's 160 KB.  The nucleotide shapes' 4 tiles x 3 bitmaps already take 12288 B per
-// workgroup, 12 workgroups at 6 waves per SIMD = 144 KB: another 8 KB each does not fit, and their register budget is spent — L2.
+// Where the tile's filter word 1 lives between the prologue of a key-test kernel and its level 2 — 0: nowhere (read from L2 per
+// entry), 1: LDS, one uint4 per lane and tile slot, lane-linear (conflict-free ds_read_b128; 1 KB per slot and wave).  Amino acids,
+// 2 tiles at 7 waves per SIMD: 6144 B of bitmaps + 4096 B per two-wave workgroup, 14 workgroups = 140 KB of the CU's 160 KB.  The
+// nucleotide shapes' 4 tiles x 3 bitmaps already take 12288 B per workgroup, 12 workgroups at 6 waves per SIMD = 144 KB: another
+// 8 KB each does not fit — L2.  (A register home, 4 VGPRs per slot fetched again behind the dense walk like word 0, was written
+// and never chosen: the nucleotide shapes' register budget is spent — profiles/r10_zone_level2.txt.)
 #ifndef SMAFA_ZONE_F1_HOME_AA
 #define SMAFA_ZONE_F1_HOME_AA 1
 #endif
 #ifndef SMAFA_ZONE_F1_HOME_NT
 #define SMAFA_ZONE_F1_HOME_NT 0
 #endif
-__host__ __device__ constexpr int zone_f1_home(int ps, int w, bool direct) {
-    return !(SMAFA_ZONE_L2_LANES && direct && w == 2 && SMAFA_ZONE_KEYS > 0) ? 0 : ps == 5 ? SMAFA_ZONE_F1_HOME_AA : SMAFA_ZONE_F1_HOME_NT;
-}
-// 1: the hoisted form runs the zone level of ALL tile slots first, then the 3 x T bitmap gathers back to back under their slots'
-// survivor masks, ONE wait, then the T key tails: one LDS latency per chunk instead of one per tile slot.  The gate is one decision
-// per chunk — every slot is tested if any slot has key_gate survivors (0: always, 65: never, as before).
-// 0: slot by slot behind a gate branch each, which keeps the slots' gathers apart.
-#ifndef SMAFA_ZONE_KEY_BATCH
-#define SMAFA_ZONE_KEY_BATCH 1
-#endif
-__host__ __device__ constexpr int zone_key_sets(int w, bool direct) { return direct && w == 2 ? SMAFA_ZONE_KEYS : 0; }
-static_assert(SMAFA_ZONE_KEYS == 0 || SMAFA_ZONE_KEYS == 2 || SMAFA_ZONE_KEYS == 3, "SMAFA_ZONE_KEYS: 0, 2 or 3");
 static_assert(SMAFA_ZONE_KEY_BITS >= 8 && SMAFA_ZONE_KEY_BITS <= 16, "SMAFA_ZONE_KEY_BITS: 8..16");
+static_assert((SMAFA_ZONE_F1_HOME_AA == 0 || SMAFA_ZONE_F1_HOME_AA == 1) && (SMAFA_ZONE_F1_HOME_NT == 0 || SMAFA_ZONE_F1_HOME_NT == 1),
+              "SMAFA_ZONE_F1_HOME_*: 0 (L2) or 1 (LDS)");
+
+// Pigeonhole key test between the zone level and level 1 (unstaged two-word kernels).  The zone level counts k columns in
+// which every subject of a tile mismatches the query; a hit in that tile then has at most b = bound - k mismatches in the
+// other columns.  Take disjoint column sets of the filter plane — Y: word 0 bits 32-KB..31, X: word 1 & key_xmask, Z: word
+// 1 bits key_zlo..key_zlo+KB-1 (ScanArgs; bits past the row length are zero in subjects and queries alike) — and let a key be
+// a subject's filter bits on one set.  A hit matches the query exactly on at least NS - b of the NS sets, once the query's
+// bits on the columns the tile shares are replaced by the tile's own (q ^ ((q ^ common) & shared): the zone level's masked
+// word, already at hand).  So with one 2^KB-bit bitmap per (tile, set) of the keys its subjects have — built per wave in LDS
+// in the prologue — a survivor whose found sets and budget b add up to less than NS cannot have a hit in the tile.  Lane per
+// query like the zone level: 64 queries at a time, one LDS gather per set, instead of level 1's serial iteration per survivor.
+// Extra keys in a bitmap (padding rows of the last tile) only let more through: the row list is the same set.
+// Three key sets (Y, X and Z) where the test runs, the unstaged two-word kernels; none elsewhere.  (Two sets, Y and X: 0.6986 ms
+// where three take 0.573, aa 10M x 10k bound 5 — profiles/r05_zone_keys.txt.)
+__host__ __device__ constexpr int zone_key_sets(int w, bool direct) { return direct && w == 2 ? 3 : 0; }
+// How the key-test kernels (zone_key_sets() > 0) run a chunk — each of these was a build switch until its round had settled it:
+//  * HOISTED KEYS (profiles/r06_zone_hoist.txt).  A wave whose tiles share no key column (zone mask & key columns == 0 for every
+//    tile slot: the sorted 10M-row stores, whose ~15 shared bits are word 0's leading columns) forms the three keys' LDS addresses
+//    and bit positions ONCE per chunk — substituting the tile's shared bits is the identity on the key columns there — and runs the
+//    chunk in two phases: zone level and key test of all its tiles, then the survivor loops (the hoisted values die before the first
+//    loop, whose rare levels use every register).  Waves with a tile that does share a key column (dense families, duplicates,
+//    small stores) keep the per-tile form.
+//  * ONE GATHER BATCH PER CHUNK (profiles/r10_zone_level2.txt).  The hoisted form runs the zone level of ALL tile slots first, then
+//    the 3 x T bitmap gathers back to back under their slots' survivor masks, ONE wait, then the T key tails: one LDS latency per
+//    chunk instead of one per tile slot.  The gate is one decision per chunk — every slot is tested if any slot has key_gate
+//    survivors (0: always, 65: never).  (Slot by slot behind a gate branch each kept the slots' gathers apart.)
+//  * LEVEL 2 FROM LANES (profiles/r10_zone_level2.txt) touches neither global nor scalar memory.  The query's filter word 1 is the
+//    head word lane i already holds (v_readlane, like word 0), the tile's filter word 1 — loaded once in the prologue for the
+//    bitmaps — stays with the wave (zone_f1_home), and the query record is read behind level 2's rejections, for level 3 alone.
+//    (Before: the record through scalar loads and the tile's word 1 from L2 in front of level 2, one serial round trip per entry.)
+__host__ __device__ constexpr int zone_f1_home(int ps, int w, bool direct) {
+    return zone_key_sets(w, direct) == 0 ? 0 : ps == 5 ? SMAFA_ZONE_F1_HOME_AA : SMAFA_ZONE_F1_HOME_NT;
+}
 
 __host__ __device__ constexpr int zone_min_waves(int ps, int w, bool direct = false) {
     return (direct && ps == 5 && w == 2 && SMAFA_ZONE_TILES == 4) ? SMAFA_ZONE_WAVES_DIRECT_AA
@@ -1061,9 +994,8 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     constexpr int WGW = kZoneWgWaves;  // waves per workgroup
     constexpr int NT = WGW * 64;
     constexpr int NV = (kChunk * RV + NT - 1) / NT;
-    constexpr int FP = filter_plane(PQ);
+    constexpr int FP = kFilterPlane;
     constexpr int BS = bound_slot(W);
-    constexpr bool kPair = SMAFA_AND_PAIR && W > 1;
     __shared__ uint4 stage[2][kChunk * RV];
     __shared__ uint32_t nu_lds[2][kChunk];  // !FIXED: ~bound of the staged queries
     __shared__ RowStageT<(WGW == 1 ? 64 : kStageRows)> rs;
@@ -1074,7 +1006,7 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     __shared__ uint4 keymap[NS ? WGW * T * NS * KW / 4 : 1];
     // ... and where level 2 finds the tile's filter word 1 (see zone_f1_home)
     constexpr int kF1Home = NS > 0 ? zone_f1_home(PS, W, DIRECT) : 0;
-    constexpr bool kL2Lanes = NS > 0 && W == 2 && SMAFA_ZONE_L2_LANES;
+    constexpr bool kL2Lanes = NS > 0 && W == 2;  // level 2 from lanes (see zone_f1_home)
     __shared__ uint4 f1_lds[kF1Home == 1 ? WGW * T * 64 : 1];
     int buf = 0;  // LDS buffer of the chunk being computed = parity of the row stage it appends to
 
@@ -1087,21 +1019,19 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     const uint32_t qblock = blockIdx.x / a.n_wg_tiles;
     const uint32_t tile0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.tile_begin + (wg_tile * WGW + wave) * T));
     const bool active = tile0 < a.tile_end;
-    // tile slots of this wave that lie inside the range: one scalar (T lane masks, kept across the chunk loop, were being
-    // spilled into VGPR lanes)
+    // tile slots of this wave that lie inside the range: one scalar (T lane masks `tile0 + t < a.tile_end`, kept across the chunk
+    // loop, were being spilled into VGPR lanes: aa 1.918 -> 1.903 ms, nt 3.859 -> 3.776 — profiles/r03_zone_variants.txt)
     const uint32_t n_live = active ? min((uint32_t)T, a.tile_end - tile0) : 0u;
     const uint32_t q0 = a.q_begin + qblock * a.qb_size;
     const uint32_t q1 = min(q0 + a.qb_size, a.q_end);
 
     // word 0 of the filter plane of this lane's 16 subjects; tile slots past the range copy tile_begin (valid memory)
     uint4 f0[T];
-    uint4 f1_reg[kF1Home == 2 ? T : 1];  // word 1 likewise, where its home is registers
     auto load_filter = [&]() {
 #pragma unroll
         for (int t = 0; t < T; t++) {
-            const bool live = SMAFA_ZONE_NLIVE ? (uint32_t)t < n_live : tile0 + t < a.tile_end;
+            const bool live = (uint32_t)t < n_live;
             f0[t] = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W) * 64 + lane];
-            if constexpr (kF1Home == 2) f1_reg[t] = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
         }
     };
     load_filter();
@@ -1110,7 +1040,8 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     uint4 vz = make_uint4(0u, 0u, 0u, 0u);
     if (lane < (uint32_t)T && tile0 + lane < a.tile_end) vz = a.zone[tile0 + lane];
     // word 0's zone words go to scalar registers once (they are used by every chunk); word 1 rarely shares anything
-    // (a 10M-row store spends its ~15 shared bits in word 0): its part of the check runs only for waves that need it
+    // (a 10M-row store spends its ~15 shared bits in word 0): its part of the check runs only for waves that need it.
+    // (Read out of their VGPR lane per use instead, no spill lane at all: nt 3.776 -> 3.844 ms — profiles/r03_zone_variants.txt.)
     uint32_t zc0[T], zm0[T];
 #pragma unroll
     for (int t = 0; t < T; t++) {
@@ -1140,13 +1071,13 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     auto key_x = [&](uint32_t w1) -> uint32_t { return w1 & a.key_xmask; };
     auto key_z = [&](uint32_t w1) -> uint32_t { return __builtin_amdgcn_ubfe(w1, a.key_zlo, KB); };
     // no tile slot of this wave shares a key column (slots past the range: zone words 0): a query's keys on this wave's tiles
-    // are then its own filter bits — see SMAFA_ZONE_KEY_HOIST
-    constexpr bool kHoist = NS > 0 && SMAFA_ZONE_KEY_HOIST;
+    // are then its own filter bits — the hoisted form (see zone_key_sets)
+    constexpr bool kHoist = NS > 0;
     bool key_hoist = false;
     if constexpr (kHoist) {
         uint32_t shared_keys = 0;
 #pragma unroll
-        for (int t = 0; t < T; t++) shared_keys |= key_y(zm0[t]) | key_x(zm1s[t]) | (NS > 2 ? key_z(zm1s[t]) : 0u);
+        for (int t = 0; t < T; t++) shared_keys |= key_y(zm0[t]) | key_x(zm1s[t]) | key_z(zm1s[t]);
         key_hoist = shared_keys == 0u;
     }
     // this wave's bitmaps: u32 word j of (tile slot t, set s) at km[(t * NS + s) * KW + j]
@@ -1164,21 +1095,16 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
 #pragma unroll
         for (int t = 0; t < T; t++) {
             const bool live = (uint32_t)t < n_live;
-            uint4 f1;
-            if constexpr (kF1Home == 2) f1 = f1_reg[t];
-            else f1 = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
+            const uint4 f1 = planes[(size_t)(live ? tile0 + t : a.tile_begin) * (PS * W * 64) + (FP * W + 1) * 64 + lane];
             if constexpr (kF1Home == 1) f1_home[t * 64 + lane] = f1;
             const uint32_t w0[4] = {f0[t].x, f0[t].y, f0[t].z, f0[t].w};
             const uint32_t w1[4] = {f1.x, f1.y, f1.z, f1.w};
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t ky = key_y(w0[k]), kx = key_x(w1[k]);
+                const uint32_t ky = key_y(w0[k]), kx = key_x(w1[k]), kz = key_z(w1[k]);
                 atomicOr(&km[(t * NS + 0) * KW + (ky >> 5)], 1u << (ky & 31u));
                 atomicOr(&km[(t * NS + 1) * KW + (kx >> 5)], 1u << (kx & 31u));
-                if (NS > 2) {
-                    const uint32_t kz = key_z(w1[k]);
-                    atomicOr(&km[(t * NS + (NS > 2 ? 2 : 0)) * KW + (kz >> 5)], 1u << (kz & 31u));
-                }
+                atomicOr(&km[(t * NS + 2) * KW + (kz >> 5)], 1u << (kz & 31u));
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -1190,14 +1116,14 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
     // ~thr0, !FIXED keeps the chunk's per-query ~bound in nu_lds (read from thr at the top of the previous chunk, one
     // register per thread in flight, written at its end).
     auto dma = [&](int b, uint32_t qc) {  // lands at wave base + lane * 16 (lane-linear)
-        // SMAFA_ZONE_FULL_DMA: always the whole chunk — the record array is padded by a chunk (engine.hip qset_fill), the heads
-        // of queries past the block are masked where they are read: no per-chunk count / compare / exec mask around the DMA
-        const uint32_t nqc = SMAFA_ZONE_FULL_DMA ? (uint32_t)kChunk : min((uint32_t)kChunk, q1 - qc);
+        // always the whole chunk — the record array is padded by a chunk (engine.hip qset_fill), the heads of queries past the
+        // block are masked where they are read: no per-chunk count / compare / exec mask around the DMA (nt 3.52 -> 3.49 ms by
+        // itself, 3.35 -> 3.26 next to the opaque chunk parity of the rare levels — profiles/r04_zone_variants.txt)
         const uint4 *src = reinterpret_cast<const uint4 *>(qrec + (size_t)qc * RS);
 #pragma unroll
         for (int v = 0; v < NV; v++) {
             const uint32_t idx = tid + v * NT;
-            if (idx < nqc * RV)
+            if (idx < (uint32_t)(kChunk * RV))  // (a compile-time bound: it only cuts the last v where kChunk * RV % NT != 0)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + idx),
                                                  (__attribute__((address_space(3))) void *)(&stage[b][wave * 64 + v * NT]), 16, 0, 0);
         }
@@ -1207,6 +1133,7 @@ __global__ __launch_bounds__(kZoneWgWaves * 64, zone_min_waves(PS, W, DIRECT)) v
         return tid < min((uint32_t)kChunk, q1 - qc) ? ~ld_relaxed(a.thr + qc + tid) : 0u;
     };
     uint32_t nu_next = 0;
+    // (this kernel's own: with the shared read_record<RS> in its place 33 of the 36 instantiations come out differently)
     auto read_record = [&](const uint4 *rec, uint32_t(&qw)[RS]) {
 #pragma unroll
         for (int v = 0; v < RV; v++) {
@@ -1335,9 +1262,8 @@ __global__ __launch_bounds__(256) void scan_zone_few_kernel(const uint4 *__restr
     constexpr int T = kFewTiles;
     constexpr int RS = qrec_stride(PQ, W);
     constexpr int RV = RS / 4;
-    constexpr int FP = filter_plane(PQ);
+    constexpr int FP = kFilterPlane;
     constexpr int BS = bound_slot(W);
-    constexpr bool kPair = SMAFA_AND_PAIR && W > 1;
     __shared__ RowStage rs;
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -1397,33 +1323,12 @@ __global__ __launch_bounds__(256) void scan_zone_few_kernel(const uint4 *__restr
                 // levels 2 and 3 (rare): the whole record, from global memory
                 const uint32_t q = a.q_begin + (uint32_t)i;
                 uint32_t qw[RS];
-                const uint4 *rec = reinterpret_cast<const uint4 *>(qrec + (size_t)q * RS);
-#pragma unroll
-                for (int v = 0; v < RV; v++) {
-                    const uint4 x = rec[v];
-                    qw[4 * v + 0] = x.x;
-                    qw[4 * v + 1] = x.y;
-                    qw[4 * v + 2] = x.z;
-                    qw[4 * v + 3] = x.w;
-                }
+                read_record(reinterpret_cast<const uint4 *>(qrec + (size_t)q * RS), qw, 0, RV);
                 qw[BS] = nu;  // the record's bound slot is filled in at staging time elsewhere; here from thr / thr0
-                uint32_t m0 = ft.x ^ qw[0], m1 = ft.y ^ qw[0], m2 = ft.z ^ qw[0], m3 = ft.w ^ qw[0];
-#pragma unroll
-                for (int w = 1; w < W; w++) {  // filter words 1.. of the tile, from L2/HBM
-                    const uint4 v = planes[(size_t)tile * (PS * W * 64) + (FP * W + w) * 64 + lane];
-                    m0 = or_xor(m0, v.x, qw[qslot(PQ, W, FP, w)]);
-                    m1 = or_xor(m1, v.y, qw[qslot(PQ, W, FP, w)]);
-                    m2 = or_xor(m2, v.z, qw[qslot(PQ, W, FP, w)]);
-                    m3 = or_xor(m3, v.w, qw[qslot(PQ, W, FP, w)]);
-                }
-                if (kPair) {
-                    const uint32_t sign = (__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu);
-                    if (__ballot((int32_t)sign < 0) == 0ull) continue;
-                }
-                if (W > 1) {
-                    const uint32_t each = or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                              __builtin_popcount(m2) + nu) |
-                                          (__builtin_popcount(m3) + nu);
+                if (W > 1) {  // level 2: filter words 1.. of the tile, from L2/HBM
+                    const uint32_t each = fold_sign<W>(ft.x ^ qw[0], ft.y ^ qw[0], ft.z ^ qw[0], ft.w ^ qw[0],
+                                                       [&](int w) { return planes[(size_t)tile * (PS * W * 64) + (FP * W + w) * 64 + lane]; },
+                                                       [&](int w) { return qw[qslot(PQ, W, FP, w)]; }, nu);
                     if (__ballot((int32_t)each < 0) == 0ull) continue;
                 }
                 // exact comparison against the 4 subjects this lane owns in the tile
@@ -1492,8 +1397,8 @@ __global__ __launch_bounds__(256, 4) void scan_wide_kernel(const uint4 *__restri
     static_assert(FW >= 1 && FW <= 4, "1 (two planes of a one-word store) to 4 filter words resident");
     constexpr int kWideGroup = wide_group(PS);
     constexpr int NV = kWideStage / 256;
-    constexpr int FP = filter_plane(PQ);
-    constexpr int FP2 = FP == 0 ? 1 : 0;  // ONE: the second plane of level 2 (slot 2 of a one-word record)
+    constexpr int FP = kFilterPlane;
+    constexpr int FP2 = 1;  // ONE: the second plane of level 2 (slot 2 of a one-word record)
     static_assert(FP < PS && FP2 < PS && PS <= PQ, "the filter planes must be ones the subjects store");
     const uint32_t RS = (uint32_t)qrec_stride(PQ, (int)W);
     const uint32_t RV = RS / 4;
@@ -1786,7 +1691,9 @@ __global__ __launch_bounds__(256, 4) void scan_wide_kernel(const uint4 *__restri
                         level1_passes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(level1_passes + (go ? 1u : 0u)));
                         if (!go) return;
                     }
-                    // level 2: the resident words folded, two subjects per popcount
+                    // level 2: the resident words folded, two subjects per popcount (popcount(a & b) <= both): this kernel only
+                    // runs at bounds level 1 prunes at, where that form is the cheaper one (one-word stores, 10M x 20 aa, bound 3:
+                    // 7.1 ms vs 8.6 ms per subject — profiles/r02_short_check.txt)
                     uint32_t qf[NF];
                     qf[0] = qw0;
                     qf[1] = ONE ? head.z : head.y;
@@ -1804,15 +1711,14 @@ __global__ __launch_bounds__(256, 4) void scan_wide_kernel(const uint4 *__restri
                             m2 = or_xor(m2, f[t][w].z, qf[w]);
                             m3 = or_xor(m3, f[t][w].w, qf[w]);
                         }
-                        const uint32_t sign =
-                            SMAFA_WIDE_AND_PAIR ? ((__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu))
-                                           : (or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                                  __builtin_popcount(m2) + nu) |
-                                              (__builtin_popcount(m3) + nu));
+                        const uint32_t sign = (__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu);
                         if (__ballot((int32_t)sign < 0) != 0ull) live |= 1u << t;
                     }
                     live = (uint32_t)__builtin_amdgcn_readfirstlane((int)live);
-                    if (SMAFA_WIDE_AND_PAIR && live != 0) {  // subjects one by one before a tile is streamed (see scan_lazy_kernel)
+                    // The two-subject AND passes whenever ONE of the pair is close on this plane (a relative of the query next to
+                    // anything): before a tile is streamed, look at its subjects one by one.  Rare path: recomputing the masks is
+                    // cheaper than keeping them.
+                    if (live != 0) {
 #pragma unroll
                         for (int t = 0; t < T; t++) {
                             if ((live >> t) & 1u) {
@@ -1884,7 +1790,7 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(const uint4 *__restri
     const uint32_t qblock = blockIdx.x / a.n_wg_tiles;
     const uint32_t tile0 = a.tile_begin + (wg_tile * kWgWaves + wave) * kGenericTiles;
     const bool active = tile0 < a.tile_end;  // idle waves still take part in the barriers of the row flushes
-    const uint32_t FP = (uint32_t)filter_plane((int)PQ);
+    const uint32_t FP = (uint32_t)kFilterPlane;
     const size_t tile_stride = (size_t)PS * W * 64;
     uint4 f[kGenericTiles];
 #pragma unroll

@@ -27,7 +27,6 @@
                 // out of the chunk loop as T lane masks that then live in spilled VGPR lanes)
                 uint32_t nl = PLAIN ? (uint32_t)T : n_live;
                 if constexpr (!PLAIN) asm volatile("" : "+s"(nl));
-                if (!SMAFA_ZONE_SGPR_ZONE) asm volatile("" : "+v"(vz.x), "+v"(vz.y));  // (read out of vz where they are used)
                 // Tile by tile, unrolled (the rare levels' address math stays inside their branch thanks to the opaque
                 // tile number below; a run-time tile loop cost 4 % on aa and 27 % on nt at bound 3 in per-tile
                 // bookkeeping — profiles/r02_zone_variants.txt).
@@ -37,8 +36,7 @@
                 // nucleotides at bound 3: scalar instructions 1.5 per 1024 pairs against 1.7 vector ones.)
                 auto zone_keys = [&](auto slot) -> unsigned long long {
                     constexpr uint32_t t = decltype(slot)::value;
-                    const uint32_t zc = SMAFA_ZONE_SGPR_ZONE ? zc0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.x, (int)t);
-                    const uint32_t zm = SMAFA_ZONE_SGPR_ZONE ? zm0[t] : (uint32_t)__builtin_amdgcn_readlane((int)vz.y, (int)t);
+                    const uint32_t zc = zc0[t], zm = zm0[t];
                     const uint32_t d0 = (hq0 ^ zc) & (kMaskInVgpr ? zmv[t] : zm);  // the columns counted
                     uint32_t u = __builtin_popcount(d0) + hnu;
                     uint32_t d1 = 0;
@@ -59,11 +57,9 @@
                                 const uint32_t vy = km[(t * NS + 0) * KW + (ky >> 5)];
                                 const uint32_t vx = km[(t * NS + 1) * KW + (kx >> 5)];
                                 uint32_t found = ((vy >> (ky & 31u)) & 1u) + ((vx >> (kx & 31u)) & 1u);
-                                if (NS > 2) {
-                                    const uint32_t kz = key_z(s1);
-                                    const uint32_t vz_ = km[(t * NS + (NS > 2 ? 2 : 0)) * KW + (kz >> 5)];
-                                    found += (vz_ >> (kz & 31u)) & 1u;
-                                }
+                                const uint32_t kz = key_z(s1);  // (set Z behind the other two: the compiler's schedule follows the text)
+                                const uint32_t vz_ = km[(t * NS + 2) * KW + (kz >> 5)];
+                                found += (vz_ >> (kz & 31u)) & 1u;
                                 pass = found + ~u >= (uint32_t)NS;
                             }
                             m = __ballot(pass);
@@ -100,15 +96,11 @@
                         // for (6 % of the launch)
                         uint32_t tile_r = tile;
                         asm volatile("" : "+s"(tile_r));
-#if SMAFA_ZONE_OPAQUE_BUF
                         // ... and the chunk parity likewise: the LDS addresses of the staged record and of the row stage
-                        // (five scalar instructions) were being formed in front of EVERY tile's survivor loop
+                        // (five scalar instructions) were being formed in front of EVERY tile's survivor loop (nt 3.52 ->
+                        // 3.35 ms — profiles/r04_zone_variants.txt)
                         int buf_r = __builtin_amdgcn_readfirstlane(buf);
                         asm volatile("" : "+s"(buf_r));
-#define SMAFA_ZONE_BUF buf_r
-#else
-#define SMAFA_ZONE_BUF buf
-#endif
                         uint32_t qw[RS];
                         if constexpr (kL2Lanes) {
                             // ---- level 2, two filter words, no memory but the wave's own: the query's word 1 out of lane i like
@@ -116,52 +108,29 @@
                             const uint32_t q1w = (uint32_t)__builtin_amdgcn_readlane((int)hq1, i);
                             uint4 v;
                             if constexpr (kF1Home == 1) v = f1_home[t * 64 + lane];
-                            else if constexpr (kF1Home == 2) v = f1_reg[t];
                             else v = planes[(size_t)tile_r * (PS * W * 64) + (FP * W + 1) * 64 + lane];
-                            const uint32_t m0 = or_xor(ft.x ^ q0w, v.x, q1w), m1 = or_xor(ft.y ^ q0w, v.y, q1w);
-                            const uint32_t m2 = or_xor(ft.z ^ q0w, v.z, q1w), m3 = or_xor(ft.w ^ q0w, v.w, q1w);
-                            if (kPair) {  // two subjects per popcount first (see scan_kernel)
-                                const uint32_t sign = (__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu);
-                                if (__ballot((int32_t)sign < 0) == 0ull) continue;
-                            }
-                            const uint32_t each = or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                                      __builtin_popcount(m2) + nu) |
-                                                  (__builtin_popcount(m3) + nu);
+                            const uint32_t each = fold_sign<2>(ft.x ^ q0w, ft.y ^ q0w, ft.z ^ q0w, ft.w ^ q0w, [&](int) { return v; },
+                                                               [&](int) { return q1w; }, nu);
                             if (__ballot((int32_t)each < 0) == 0ull) continue;
                             read_record(reinterpret_cast<const uint4 *>(qrec + (size_t)(qc + (uint32_t)i) * RS), qw);
                             qw[BS] = nu;
                             passes++;
-                            stream_compare(tile_r, qw, qc + (uint32_t)i, SMAFA_ZONE_BUF);
+                            stream_compare(tile_r, qw, qc + (uint32_t)i, buf_r);
                             continue;
                         }
                         // ---- level 2 (rare): the filter plane folded over all its words, words 1.. from L2/HBM
                         if (DIRECT) read_record(reinterpret_cast<const uint4 *>(qrec + (size_t)(qc + (uint32_t)i) * RS), qw);
-                        else read_record(&stage[SMAFA_ZONE_BUF][(uint32_t)i * RV], qw);
+                        else read_record(&stage[buf_r][(uint32_t)i * RV], qw);
                         qw[BS] = nu;  // the staged record carries no bound
-                        uint32_t m0 = ft.x ^ qw[0], m1 = ft.y ^ qw[0], m2 = ft.z ^ qw[0], m3 = ft.w ^ qw[0];
                         if (W > 1) {
                             const uint4 *src = planes + (size_t)tile_r * (PS * W * 64) + (FP * W) * 64 + lane;
-#pragma unroll
-                            for (int w = 1; w < W; w++) {
-                                const uint4 v = src[w * 64];
-                                m0 = or_xor(m0, v.x, qw[qslot(PQ, W, FP, w)]);
-                                m1 = or_xor(m1, v.y, qw[qslot(PQ, W, FP, w)]);
-                                m2 = or_xor(m2, v.z, qw[qslot(PQ, W, FP, w)]);
-                                m3 = or_xor(m3, v.w, qw[qslot(PQ, W, FP, w)]);
-                            }
-                            if (kPair) {  // two subjects per popcount first (see scan_kernel)
-                                const uint32_t sign = (__builtin_popcount(m0 & m1) + nu) | (__builtin_popcount(m2 & m3) + nu);
-                                if (__ballot((int32_t)sign < 0) == 0ull) continue;
-                            }
-                            const uint32_t each = or3(__builtin_popcount(m0) + nu, __builtin_popcount(m1) + nu,
-                                                      __builtin_popcount(m2) + nu) |
-                                                  (__builtin_popcount(m3) + nu);
+                            const uint32_t each = fold_sign<W>(ft.x ^ qw[0], ft.y ^ qw[0], ft.z ^ qw[0], ft.w ^ qw[0], [&](int w) { return src[w * 64]; },
+                                                               [&](int w) { return qw[qslot(PQ, W, FP, w)]; }, nu);
                             if (__ballot((int32_t)each < 0) == 0ull) continue;
                         }
                         // ---- level 3: all planes, exactly
                         passes++;
-                        stream_compare(tile_r, qw, qc + (uint32_t)i, SMAFA_ZONE_BUF);
-#undef SMAFA_ZONE_BUF
+                        stream_compare(tile_r, qw, qc + (uint32_t)i, buf_r);
                     }
                 };
                 static_assert(T <= 8, "tile slots are spelled out below");
@@ -175,8 +144,6 @@
                     if constexpr (T > 6) f(std::integral_constant<uint32_t, 6>{});
                     if constexpr (T > 7) f(std::integral_constant<uint32_t, 7>{});
                 };
-                static_assert(!kHoist || (SMAFA_ZONE_NLIVE && SMAFA_ZONE_SGPR_ZONE),
-                              "the two-phase form of the key-test kernels is written for SMAFA_ZONE_NLIVE = SMAFA_ZONE_SGPR_ZONE = 1");
                 if constexpr (kHoist) {
                     // Two phases: zone level and key test of every tile slot first (one survivor mask per slot, in scalars),
                     // then the survivor loops — what the first phase keeps per chunk is dead before the first loop.
@@ -187,7 +154,7 @@
                         // formed in one opaque instruction: as plain arithmetic the compiler re-adds the base in front of every
                         // gather.)
                         // (Computed for every chunk, 9 VALU, also where no tile reaches the gate or the test is off, gate 65.)
-                        const uint32_t ky = key_y(hq0), kx = key_x(hq1), kz = NS > 2 ? key_z(hq1) : 0u;
+                        const uint32_t ky = key_y(hq0), kx = key_x(hq1), kz = key_z(hq1);
                         typedef const __attribute__((address_space(3))) uint32_t *lds_u32;
                         const uint32_t km_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)km;
                         auto word_of = [&](uint32_t key) -> uint32_t {  // LDS address of word key >> 5 of (tile slot 0, set 0)
@@ -195,80 +162,55 @@
                             asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(at) : "v"(key >> 5), "s"(km_lds));
                             return at;
                         };
-                        const uint32_t ay = word_of(ky), ax = word_of(kx), az = NS > 2 ? word_of(kz) : 0u;
+                        const uint32_t ay = word_of(ky), ax = word_of(kx), az = word_of(kz);
                         // lanes past the block are masked out of the ballot (scalar) instead of out of ~bound (per lane)
                         // (a FULL chunk has no such lane)
                         const unsigned long long in_block = FULL ? ~0ull : ~0ull >> (64u - nqc);
                         auto hoisted = [&](auto with_w1) {
-                            if constexpr (SMAFA_ZONE_KEY_BATCH) {
-                                // zone level of every slot; slots past the range keep an empty mask (an active wave's slot 0 is
-                                // inside it) and, in the last wave alone, gather from their own bitmaps for nothing
-                                uint32_t u[T];
-                                bool test = false;
-                                unsigned long long any = 0ull;
+                            // zone level of every slot; slots past the range keep an empty mask (an active wave's slot 0 is
+                            // inside it) and, in the last wave alone, gather from their own bitmaps for nothing
+                            uint32_t u[T];
+                            bool test = false;
+                            unsigned long long any = 0ull;
+                            each_slot([&](auto slot) {
+                                constexpr uint32_t t = decltype(slot)::value;
+                                u[t] = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
+                                if (decltype(with_w1)::value) u[t] += __builtin_popcount((hq1 ^ zc1s[t]) & zm1s[t]);
+                                unsigned long long m = __builtin_amdgcn_ballot_w64((int32_t)u[t] < 0);
+                                if constexpr (!FULL) m &= in_block;
+                                ms[t] = PLAIN || t == 0u || nl > t ? m : 0ull;
+                                if constexpr (PLAIN) any |= m;
+                                else test = test || (uint32_t)__builtin_popcountll(ms[t]) >= a.key_gate;
+                            });
+                            // PLAIN: one count for the chunk — the queries that survive ANY slot against the gate (0: always,
+                            // 65: never, like the count per slot; in between the test runs for a superset of the chunks, and
+                            // it only ever removes pairs that have no hit)
+                            if constexpr (PLAIN) test = (uint32_t)__builtin_popcountll(any) >= a.key_gate;
+                            if (test) {
+                                // all gathers under their slots' survivors, nothing between them that waits: ONE LDS latency per
+                                // chunk.  (Slot by slot behind a gate branch each, every tile waited out its own latency — the
+                                // form of profiles/r06_zone_hoist.txt; see profiles/r10_zone_level2.txt.)  General body: lanes
+                                // that did not survive keep 0 = nothing found, so their u stays >= 0 below.
+                                // PLAIN: no zero fill — what a lane that did not survive holds is unspecified; it counts at most NS
+                                // found sets on u >= 0, which stays above -NS, and ms[t] already leaves the lane out.
+                                uint32_t g[T][3];
                                 each_slot([&](auto slot) {
                                     constexpr uint32_t t = decltype(slot)::value;
-                                    u[t] = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
-                                    if (decltype(with_w1)::value) u[t] += __builtin_popcount((hq1 ^ zc1s[t]) & zm1s[t]);
-                                    unsigned long long m = __builtin_amdgcn_ballot_w64((int32_t)u[t] < 0);
-                                    if constexpr (!FULL) m &= in_block;
-                                    ms[t] = PLAIN || t == 0u || nl > t ? m : 0ull;
-                                    if constexpr (PLAIN) any |= m;
-                                    else test = test || (uint32_t)__builtin_popcountll(ms[t]) >= a.key_gate;
-                                });
-                                // PLAIN: one count for the chunk — the queries that survive ANY slot against the gate (0: always,
-                                // 65: never, like the count per slot; in between the test runs for a superset of the chunks, and
-                                // it only ever removes pairs that have no hit)
-                                if constexpr (PLAIN) test = (uint32_t)__builtin_popcountll(any) >= a.key_gate;
-                                if (test) {
-                                    // all gathers under their slots' survivors, nothing between them that waits.  General body: lanes
-                                    // that did not survive keep 0 = nothing found, so their u stays >= 0 below.
-                                    // PLAIN: no zero fill — what a lane that did not survive holds is unspecified; it counts at most NS
-                                    // found sets on u >= 0, which stays above -NS, and ms[t] already leaves the lane out.
-                                    uint32_t g[T][3];
-                                    each_slot([&](auto slot) {
-                                        constexpr uint32_t t = decltype(slot)::value;
-                                        if constexpr (PLAIN) asm volatile("" : "=v"(g[t][0]), "=v"(g[t][1]), "=v"(g[t][2]));
-                                        else g[t][0] = g[t][1] = g[t][2] = 0u;
-                                        if ((int32_t)u[t] < 0) {
-                                            g[t][0] = *(lds_u32)(uintptr_t)(ay + ((t * NS + 0) * KW) * 4u);
-                                            g[t][1] = *(lds_u32)(uintptr_t)(ax + ((t * NS + 1) * KW) * 4u);
-                                            if (NS > 2) g[t][2] = *(lds_u32)(uintptr_t)(az + ((t * NS + (NS > 2 ? 2 : 0)) * KW) * 4u);
-                                        }
-                                    });
-                                    // found sets + budget ~u >= NS  <=>  u - found < -NS
-                                    each_slot([&](auto slot) {
-                                        constexpr uint32_t t = decltype(slot)::value;
-                                        uint32_t found = __builtin_amdgcn_ubfe(g[t][0], ky, 1) + __builtin_amdgcn_ubfe(g[t][1], kx, 1);
-                                        if (NS > 2) found += __builtin_amdgcn_ubfe(g[t][2], kz, 1);
-                                        ms[t] &= __builtin_amdgcn_ballot_w64((int32_t)(u[t] - found) < -(int32_t)NS);
-                                    });
-                                }
-                            } else {
-                            auto one = [&](auto slot) -> unsigned long long {
-                                constexpr uint32_t t = decltype(slot)::value;
-                                uint32_t u = __builtin_popcount((hq0 ^ zc0[t]) & (kMaskInVgpr ? zmv[t] : zm0[t])) + nu0;
-                                if (decltype(with_w1)::value) u += __builtin_popcount((hq1 ^ zc1s[t]) & zm1s[t]);
-                                unsigned long long m = __builtin_amdgcn_ballot_w64((int32_t)u < 0) & in_block;
-                                // (This scalar branch per tile keeps the tiles' gathers apart: each tile still waits out its own
-                                // LDS latency, the 3 x T gathers do NOT issue back to back — profiles/r06_zone_hoist.txt.)
-                                if ((uint32_t)__builtin_popcountll(m) >= a.key_gate) {
-                                    // found sets + budget ~u >= NS  <=>  u - found < -NS; lanes that did not survive keep u >= 0
-                                    if ((int32_t)u < 0) {
-                                        uint32_t found = __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(ay + ((t * NS + 0) * KW) * 4u), ky, 1) +
-                                                         __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(ax + ((t * NS + 1) * KW) * 4u), kx, 1);
-                                        if (NS > 2) found += __builtin_amdgcn_ubfe(*(lds_u32)(uintptr_t)(az + ((t * NS + (NS > 2 ? 2 : 0)) * KW) * 4u), kz, 1);
-                                        u -= found;
+                                    if constexpr (PLAIN) asm volatile("" : "=v"(g[t][0]), "=v"(g[t][1]), "=v"(g[t][2]));
+                                    else g[t][0] = g[t][1] = g[t][2] = 0u;
+                                    if ((int32_t)u[t] < 0) {
+                                        g[t][0] = *(lds_u32)(uintptr_t)(ay + ((t * NS + 0) * KW) * 4u);
+                                        g[t][1] = *(lds_u32)(uintptr_t)(ax + ((t * NS + 1) * KW) * 4u);
+                                        g[t][2] = *(lds_u32)(uintptr_t)(az + ((t * NS + 2) * KW) * 4u);
                                     }
-                                    asm("" : "+v"(u));  // (or the compare is moved into the `if` and its lane mask rebuilt behind it)
-                                    m &= __builtin_amdgcn_ballot_w64((int32_t)u < -(int32_t)NS);
-                                }
-                                return m;
-                            };
-                            each_slot([&](auto slot) {  // (an active wave's slot 0 is inside the range)
-                                constexpr uint32_t t = decltype(slot)::value;
-                                ms[t] = t == 0u || nl > t ? one(slot) : 0ull;
-                            });
+                                });
+                                // found sets + budget ~u >= NS  <=>  u - found < -NS
+                                each_slot([&](auto slot) {
+                                    constexpr uint32_t t = decltype(slot)::value;
+                                    const uint32_t found = __builtin_amdgcn_ubfe(g[t][0], ky, 1) + __builtin_amdgcn_ubfe(g[t][1], kx, 1) +
+                                                           __builtin_amdgcn_ubfe(g[t][2], kz, 1);
+                                    ms[t] &= __builtin_amdgcn_ballot_w64((int32_t)(u[t] - found) < -(int32_t)NS);
+                                });
                             }
                         };
                         // word 1's share of the zone level under a scalar branch: it is rare (zone_w1)
@@ -284,7 +226,7 @@
                 } else {
                     each_slot([&](auto slot) {
                         constexpr uint32_t t = decltype(slot)::value;
-                        if (SMAFA_ZONE_NLIVE ? nl > t : tile0 + t < a.tile_end) survivors(slot, zone_keys(slot));
+                        if (nl > t) survivors(slot, zone_keys(slot));
                     });
                 }
                 // an exact comparison from L2 costs ~60 VALU per (query, tile) pair, the dense walk below ~25 for EVERY
@@ -307,11 +249,11 @@
                 // dense neighbourhoods: one pass over the chunk per tile, that tile's planes in registers
                 for (uint32_t t = 0; t < (uint32_t)T; t++) {
                     const uint32_t tile = tile0 + t;
-                    if (SMAFA_ZONE_NLIVE ? t >= n_live : tile >= a.tile_end) break;
+                    if (t >= n_live) break;
                     uint4 s[PS * W];
                     uint32_t tile_d = tile;  // opaque: the walk's addresses are formed here, not kept (spilled) from the prologue
                     asm volatile("" : "+s"(tile_d));
-                    const uint4 *src = planes + (size_t)(SMAFA_ZONE_NLIVE ? tile_d : tile) * (PS * W * 64) + lane;
+                    const uint4 *src = planes + (size_t)tile_d * (PS * W * 64) + lane;
 #pragma unroll
                     for (int i = 0; i < PS * W; i++) s[i] = src[i * 64];
                     const uint4 *rec = DIRECT ? reinterpret_cast<const uint4 *>(qrec + (size_t)qc * RS) : &stage[buf][0];

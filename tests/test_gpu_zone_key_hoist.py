@@ -1,4 +1,4 @@
-"""GPU parity of both forms of the key test of scan_zone_kernel<.., DIRECT> in ONE launch (kernels.hip.h, SMAFA_ZONE_KEY_HOIST).
+"""GPU parity of both forms of the key test of scan_zone_kernel<.., DIRECT> in ONE launch (kernels.hip.h: kHoist, key_hoist).
 
 A wave whose tile slots share no key column takes the hoisted form (keys from the query's own filter words, once per chunk);
 a wave with a tile that shares one takes the per-tile form (keys with the tile's shared bits substituted).  The store here has

@@ -1,7 +1,7 @@
-"""GPU parity of level 2 of scan_zone_kernel<.., DIRECT> on two-word stores (kernels.hip.h: SMAFA_ZONE_L2_LANES, zone_f1_home).
+"""GPU parity of level 2 of scan_zone_kernel<.., DIRECT> on two-word stores (kernels.hip.h: kL2Lanes, zone_f1_home).
 
 Level 2 folds the filter plane over both its words.  In the key-test kernels the query's filter word 1 comes out of lane i of the
-chunk's heads and the tile's filter word 1 from where the prologue left it (LDS, registers or L2, per shape); the query record is
+chunk's heads and the tile's filter word 1 from where the prologue left it (LDS or L2, per shape); the query record is
 read only for level 3.  The queries here are built, on the CPU, to stop at each of those levels next to known subjects:
 
   (a) filter word 0 as the subject's, BOUND + 1 filter-bit flips in word 1                : passes level 1, rejected at level 2

@@ -36,7 +36,7 @@ def bound_slot(words):
 
 
 def qslot(planes, words, p, w):
-    if p == 0:  # filter_plane: always plane 0
+    if p == 0:  # kFilterPlane: always plane 0
         return w if w < bound_slot(words) else w + 1
     return words + 1 + (p - 1) * words + w
 
@@ -63,10 +63,10 @@ def test_the_restated_layout_is_the_headers():
         "constexpr int kWaveTile = %d;" % WAVE_TILE,
         "constexpr int round_up4(int x) { return (x + 3) & ~3; }",
         "constexpr int qrec_stride(int planes, int words) { return round_up4(planes * words + 1); }",
-        "constexpr int filter_plane(int) { return 0; }",
+        "constexpr int kFilterPlane = 0;",
         "constexpr int bound_slot(int words) { return words < 2 ? words : 2; }",
-        "constexpr int qslot(int planes, int words, int p, int w) { return p == filter_plane(planes) ? (w < bound_slot(words) ? w : w + 1) "
-        ": words + 1 + (p < filter_plane(planes) ? p : p - 1) * words + w; }",
+        "constexpr int qslot(int planes, int words, int p, int w) { return p == 0 ? (w < bound_slot(words) ? w : w + 1) "
+        ": words + 1 + (p < 0 ? p : p - 1) * words + w; }",
     ):
         assert text in k, text
     j = _source("join.hip.h")

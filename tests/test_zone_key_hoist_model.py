@@ -1,4 +1,4 @@
-"""CPU model of the hoisted key test of scan_zone_kernel<.., DIRECT> (kernels.hip.h, SMAFA_ZONE_KEY_HOIST).
+"""CPU model of the hoisted key test of scan_zone_kernel<.., DIRECT> (kernels.hip.h: kHoist, key_hoist).
 
 The kernel forms one flag per wave — no tile slot's zone masks (zm0, zm1) touch a key column — and, where it holds, takes a
 query's three keys from its own filter words instead of from the words with the tile's shared bits substituted.  Checked here,

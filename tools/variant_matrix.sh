@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of scan-kernel variants on the GPU box.  Run-time knobs (no rebuild): SMAFA_TILES=1|2 (wave tiles per
-# wave), SMAFA_FILTER=0|1, SMAFA_NT_PLANES=3.  Build-time knobs go through EXTRA (e.g. -DSMAFA_AND_PAIR=0).
+# wave), SMAFA_FILTER=0|1, SMAFA_NT_PLANES=3.  Build-time knobs go through EXTRA (e.g. -DSMAFA_ZONE_WAVES_10=4).
 set -u
 cd "$(dirname "$0")/.."
 export OUT=${OUT:-bench_out}
