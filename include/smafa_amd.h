@@ -938,6 +938,31 @@ int smafa_db_subset(smafa_db *db, const uint32_t *keep, int invert, smafa_db **o
 int smafa_db_rows_launch(smafa_db *db, const void *d_subjects /* m uint32; NULL: first .. first+m-1 */, uint64_t first, uint64_t m, void *d_codes /* m * seq_len bytes */);
 int smafa_db_rows(smafa_db *db, const uint32_t *subjects, uint64_t first, uint64_t m, uint8_t *codes);
 
+/* ------------------------------------------------- abundance-peak clusters with given weights (the sizes of dereplicated sequences) */
+/* smafa_db_self_peaks with one line changed: weight[i] = weights_in[i] + the sum of weights_in[j] over the OTHER subjects within
+ * distance r of i.  Keys, parents, labels, n_peaks, the kept pair list, the two phases, the edges and the failures are those of
+ * smafa_db_self_peaks; with every weight 1 the two calls give the same bytes.  A weight of 0 is allowed and is simply the lightest.
+ * A sum of weights_in above 4294967295 is SMAFA_ERR_INVALID (no weight can wrap), found on the device before anything is weighed.
+ * max_div >= seq_len with r >= seq_len: every weight is that sum.  A NULL weights_in is SMAFA_ERR_INVALID unless the store is
+ * empty (checked behind the radius, in front of cap).
+ * What the weights are for: smafa_db_self_peaks at radius 0 counts abundance through the pairs at distance 0, c(c-1)/2 kept pairs
+ * for a sequence of c copies, and raw reads hold sequences of 10^5 copies.  Dereplicate them first (vsearch --derep_fulllength,
+ * DADA2's derepFastq, numpy.unique: this library has no such call yet), store every distinct sequence once and pass the sizes.
+ * With S the store of the distinct rows of R in the order of their first copies, old_of_new[u] = the first row of R that holds
+ * sequence u, unique_of[i] = the sequence of row i and sizes[u] = its copies, the peaks of S under weights_in = sizes are the peaks
+ * of R, exactly: labels_R[i] == old_of_new[labels_S[unique_of[i]]] and weights_R[i] == weights_S[unique_of[i]] for every i, and
+ * n_peaks is the same — a raw row's heaviest neighbour is always the first of a sequence's copies, and the new numbers keep the
+ * order of those, so ties break the same way.  The join of S keeps no pair at distance 0.
+ * The kernels are the plain call's: the weights are an argument of smafa_pk::init_peaks_kernel (which copies and sums them where
+ * it writes ones) and of smafa_pk::weigh_keep_kernel, and smafa_last_call_kernels reads as for smafa_db_self_peaks.  What the
+ * call adds: one host wait behind the first launch (the sum is checked before anything is weighed) and, where r >= seq_len, one
+ * more launch of init_peaks_kernel, which then writes the sum into every weight; otherwise the launch count is the plain call's. */
+int smafa_db_self_peaks_weighted_launch(smafa_db *db, uint32_t max_div, uint32_t radius, const void *d_weights_in /* n_subjects uint32 */, void *d_labels, void *d_parents /* may be NULL */, void *d_weights /* may be NULL */, void *d_n_peaks /* uint64 */);
+int smafa_db_self_peaks_weighted(smafa_db *db, uint32_t max_div, uint32_t radius, const uint32_t *weights_in, uint32_t *labels, uint32_t *parents, uint32_t *weights, uint64_t cap, uint64_t *n_peaks);
+/* smafa_peaks_weighted: smafa_peaks with the weights of a file, "i<TAB>weight" lines as for smafa_chimeras (further columns are
+ * ignored, a sequence without a line weighs 0, "-": stdin).  SMAFA_ERR_INVALID: a NULL path or weights_path. */
+int smafa_peaks_weighted(const char *db_path, uint32_t max_divergence, uint32_t radius, const char *weights_path, int out_fd, int device);
+
 /* ------------------------------------------------- the same store on several GPUs */
 /*
  * "queries sharded across the handle's devices internally".  A group is ONE subject store replicated on every

@@ -48,6 +48,7 @@ EXPORTS = [
     "smafa_db_assign_launch", "smafa_db_assign", "smafa_table",
     "smafa_db_classify_launch", "smafa_db_classify", "smafa_classify",
     "smafa_db_subset_launch", "smafa_db_subset", "smafa_db_rows_launch", "smafa_db_rows", "smafa_subset",
+    "smafa_db_self_peaks_weighted_launch", "smafa_db_self_peaks_weighted", "smafa_peaks_weighted",
     "smafa_makedb", "smafa_makedb_packed", "smafa_query", "smafa_query_multi", "smafa_cluster", "smafa_cluster_multi", "smafa_cluster_sharded", "smafa_count",
 ]
 
@@ -222,6 +223,9 @@ def lib() -> C.CDLL:
     l.smafa_db_rows_launch.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
     l.smafa_db_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
     l.smafa_subset.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
+    l.smafa_db_self_peaks_weighted_launch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    l.smafa_db_self_peaks_weighted.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, u64p]
+    l.smafa_peaks_weighted.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int]
     l.smafa_count.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_int]
     _lib = l
     return l

@@ -366,21 +366,37 @@ class SubjectStore:
                                                  C.c_void_p(d_counts) if d_counts else None))
 
     # ---- abundance-peak clusters -----------------------------------------------------------
-    def self_peaks(self, max_divergence: int, radius: Optional[int] = 0, parents: bool = True, weights: bool = True):
+    def self_peaks(self, max_divergence: int, radius: Optional[int] = 0, parents: bool = True, weights: bool = True, weights_in=None):
         """(labels, parents, weights, n_peaks) — smafa_db_self_peaks: weights[i] = 1 + the number of other subjects within
         `radius` of subject i (0: its exact copies; None: max_divergence), parents[i] = the subject of greatest (weight,
         smaller number) among i and the subjects within max_divergence of it — i itself makes i a peak — labels[i] = the peak
         reached from i along the parents.  uint32, one per subject; parents / weights are None where not wanted.  The pairs
-        stay on the device."""
+        stay on the device.  weights_in (uint32, one per subject; smafa_db_self_peaks_weighted): weights[i] = weights_in[i] + the
+        sum of weights_in over the other subjects within `radius` — the sizes of dereplicated sequences, on the store of the distinct ones:
+        its peaks are then the peaks of the raw rows."""
         n = self.info().n_subjects
         labels = np.zeros(max(n, 1), dtype=np.uint32)
         par = np.zeros(max(n, 1), dtype=np.uint32) if parents else None
         wts = np.zeros(max(n, 1), dtype=np.uint32) if weights else None
         count = C.c_uint64(0)
-        check(lib().smafa_db_self_peaks(self._h, _opt(max_divergence), _opt(radius), labels.ctypes.data,
-                                        par.ctypes.data if parents else None, wts.ctypes.data if weights else None, n,
-                                        C.byref(count)))
+        if weights_in is None:
+            check(lib().smafa_db_self_peaks(self._h, _opt(max_divergence), _opt(radius), labels.ctypes.data,
+                                            par.ctypes.data if parents else None, wts.ctypes.data if weights else None, n,
+                                            C.byref(count)))
+        else:
+            given = _given(weights_in, n, "weights_in")
+            check(lib().smafa_db_self_peaks_weighted(self._h, _opt(max_divergence), _opt(radius), _ptr(given), labels.ctypes.data,
+                                                     par.ctypes.data if parents else None, wts.ctypes.data if weights else None, n,
+                                                     C.byref(count)))
         return labels[:n], (par[:n] if parents else None), (wts[:n] if weights else None), int(count.value)
+
+    def self_peaks_weighted_launch(self, max_divergence: int, radius: Optional[int], d_weights_in: int, d_labels: int, d_parents: int,
+                                   d_weights: int, d_n_peaks: int) -> None:
+        """device-resident form (smafa_db_self_peaks_weighted_launch): self_peaks_launch with n_subjects uint32 given weights in
+        d_weights_in"""
+        ptr = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().smafa_db_self_peaks_weighted_launch(self._h, _opt(max_divergence), _opt(radius), ptr(d_weights_in), ptr(d_labels),
+                                                        ptr(d_parents), ptr(d_weights), ptr(d_n_peaks)))
 
     def self_peaks_launch(self, max_divergence: int, radius: Optional[int], d_labels: int, d_parents: int, d_weights: int,
                           d_n_peaks: int) -> None:
@@ -1007,6 +1023,12 @@ def peaks(db_path: str, max_divergence: int, radius: Optional[int] = 0, out_fd: 
     """`smafa peaks`: "i\\tlabel\\tparent\\tweight" per subject of the DB file — its abundance-peak label and parent at
     max_divergence and its weight at `radius` (smafa_db_self_peaks) — to out_fd."""
     check(lib().smafa_peaks(os.fsencode(db_path), _opt(max_divergence), _opt(radius), out_fd, device))
+
+
+def peaks_weighted(db_path: str, max_divergence: int, weights_path: str, radius: Optional[int] = 0, out_fd: int = 1, device: int = 0) -> None:
+    """`smafa peaks --sizes`: the lines of peaks(), the weights read from weights_path ("i\\tweight" lines, "-": stdin) and summed
+    within `radius` (smafa_db_self_peaks_weighted)"""
+    check(lib().smafa_peaks_weighted(os.fsencode(db_path), _opt(max_divergence), _opt(radius), os.fsencode(weights_path), out_fd, device))
 
 
 def chimeras(db_path: str, max_divergence: int, min_fold: int = 2, radius: Optional[int] = 0, weights_path: Optional[str] = None,

@@ -1098,6 +1098,38 @@ static int parse_weights(const char *who, const char *what, const char *value, u
     return SMAFA_OK;
 }
 
+// smafa_peaks with the weights of a file (smafa_db_self_peaks_weighted): the same lines
+int smafa_peaks_weighted(const char *db_path, uint32_t max_divergence, uint32_t radius, const char *weights_path, int out_fd, int device) try {
+    const char *const who = "smafa_peaks_weighted";
+    StoreVerb v;
+    int rc = begin_store_verb(who, db_path, max_divergence, device, v, [&] {
+        if (!weights_path) return set_error(SMAFA_ERR_INVALID, "%s: NULL weights path", who);
+        if (radius == SMAFA_NONE || radius <= max_divergence) return (int)SMAFA_OK;
+        return set_error(SMAFA_ERR_INVALID, "%s: radius %u is larger than max_divergence %u", who, radius, max_divergence);
+    });
+    if (rc || v.empty) return rc;
+    const size_t n = v.n;
+    std::vector<uint32_t> given;
+    {
+        std::string text;
+        rc = read_whole(who, "weights", weights_path, text);
+        if (!rc) rc = parse_weights(who, "weights", "weight", 0, text, n, given);
+        if (rc) return rc;
+    }
+    std::vector<uint32_t> labels(n), parents(n), weights(n);
+    uint64_t n_peaks = 0;
+    rc = smafa_db_self_peaks_weighted(v.store.db, max_divergence, radius, given.data(), labels.data(), parents.data(), weights.data(), n, &n_peaks);
+    if (!rc) rc = write_rows(out_fd, n, kRowsPerWrite, [&](std::string &text, size_t i) {
+        append_row(text, {(uint32_t)i, labels[i], parents[i], weights[i]});
+    });
+    if (rc) return rc;
+    log_line(1, "%llu peaks among %llu sequences within %u, given weights summed within %u, took %llu seconds", (unsigned long long)n_peaks,
+             (unsigned long long)n, max_divergence, radius == SMAFA_NONE ? max_divergence : radius, v.seconds());
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_peaks_weighted");
+}
+
 // The verdict of the chimera check for every subject of a DB file (smafa_db_self_chimeras), printed
 // "{i}\t{flag}\t{left_parent}\t{left_len}\t{right_parent}\t{right_len}\t{weight}\n" in subject order, -1 for SMAFA_NONE.
 int smafa_chimeras(const char *db_path, uint32_t max_divergence, uint32_t radius, uint32_t min_fold, const char *weights_path, int out_fd,

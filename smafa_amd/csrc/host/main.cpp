@@ -18,8 +18,8 @@
 //           and stable print them, its size, the member nearest to its consensus, the greatest divergence from it, and the consensus)
 //   density -d/--database FILE  --max-divergence INT  --min-pts INT   (this build only: the density cluster (DBSCAN) and the
 //           number of neighbours within the bound of every subject)
-//   peaks   -d/--database FILE  --max-divergence INT  [--radius INT]   (this build only: the abundance-peak cluster, the parent
-//           and the weight of every subject)
+//   peaks   -d/--database FILE  --max-divergence INT  [--radius INT] [--sizes FILE|-]   (this build only: the abundance-peak cluster,
+//           the parent and the weight of every subject; --sizes: the weights of a file, the sizes of dereplicated sequences, summed)
 //   chimeras -d/--database FILE  --max-divergence INT  [--min-fold INT] [--radius INT] [--weights FILE|-]   (this build only: the
 //           chimera check, per subject its flag, its best left and right parent with the shared prefix / suffix length, its weight)
 //   table   -d/--database FILE  -q/--query FILE  --max-divergence INT  [--labels FILE|-] [--samples FILE|-] [--weights FILE|-]
@@ -97,11 +97,13 @@ static int usage(const char *msg, FILE *to = stderr) {
             "        clusters (DBSCAN) of the database's own sequences, one \"i<TAB>label<TAB>degree\" line per sequence; degree = the\n"
             "        number of other sequences within the bound; a sequence is core if degree + 1 >= min-pts; label = the smallest\n"
             "        core sequence number of its cluster, for a non-core sequence that of its smallest core neighbour, -1 for noise)\n"
-            "peaks   -d, --database <FILE>  --max-divergence <INT>  [--radius <INT>]  [--device <N>]  (not in the reference: abundance-peak\n"
+            "peaks   -d, --database <FILE>  --max-divergence <INT>  [--radius <INT>] [--sizes <FILE|->]  [--device <N>]  (not in the reference: abundance-peak\n"
             "        clusters of the database's own sequences, one \"i<TAB>label<TAB>parent<TAB>weight\" line per sequence; weight = 1 +\n"
             "        the number of other sequences within the radius (default 0: the number of exact copies); parent = the heaviest\n"
             "        sequence within the bound, ties to the smaller number, the sequence itself if none outranks it (a peak);\n"
-            "        label = the peak reached by following the parents)\n"
+            "        label = the peak reached by following the parents; --sizes: \"i<TAB>weight\" lines in any order, the sizes of\n"
+            "        sequences that were dereplicated (further columns are ignored, a sequence without a line weighs 0, -: stdin):\n"
+            "        weight = the sequence's own weight + those of the other sequences within the radius)\n"
             "chimeras -d, --database <FILE>  --max-divergence <INT>  [--min-fold <INT>] [--radius <INT>] [--weights <FILE|->]  [--device <N>]\n"
             "        (not in the reference: two-parent chimeras among the database's own sequences, one\n"
             "        \"i<TAB>flag<TAB>left_parent<TAB>left_len<TAB>right_parent<TAB>right_len<TAB>weight\" line per sequence; a parent is a\n"
@@ -176,7 +178,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     const bool is_cluster = cmd == "cluster";
-    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr, *taxonomy = nullptr, *keep = nullptr, *drop = nullptr, *output = nullptr;
+    const char *input = nullptr, *database = nullptr, *query = nullptr, *labels = nullptr, *weights = nullptr, *samples = nullptr, *taxonomy = nullptr, *keep = nullptr, *drop = nullptr, *output = nullptr, *sizes = nullptr;
     std::vector<const char *> count_paths;
     uint32_t max_div = SMAFA_NONE, max_hits = SMAFA_NONE, limit = SMAFA_NONE, device = 0, min_pts = 0, radius = 0, min_cluster_size = 0, min_fold = 2, slack = 0;
     bool have_min_pts = false, have_since = false;
@@ -243,6 +245,8 @@ int main(int argc, char **argv) {
             if (!(keep = value())) return usage("--keep needs a file, or - for stdin");
         } else if (a == "--drop" && cmd == "subset") {
             if (!(drop = value())) return usage("--drop needs a file, or - for stdin");
+        } else if (a == "--sizes" && cmd == "peaks") {
+            if (!(sizes = value())) return usage("--sizes needs a file, or - for stdin");
         } else if (a == "--output" && cmd == "subset") {
             if (!(output = value())) return usage("--output needs a value");
         } else if (a == "--since" && cmd == "pairs") {
@@ -344,7 +348,7 @@ int main(int argc, char **argv) {
     } else if (cmd == "peaks") {
         if (!database) return usage("peaks needs --database");
         if (!have_max_div) return usage("peaks needs --max-divergence");
-        rc = smafa_peaks(database, max_div, radius, 1, (int)device);
+        rc = sizes ? smafa_peaks_weighted(database, max_div, radius, sizes, 1, (int)device) : smafa_peaks(database, max_div, radius, 1, (int)device);
     } else if (cmd == "chimeras") {
         if (!database) return usage("chimeras needs --database");
         if (!have_max_div) return usage("chimeras needs --max-divergence");

@@ -17,6 +17,13 @@
 //   crown_kernel        only at a bound no two rows can exceed: the greatest key of the store, one slot
 //   settle_kernel       parent[i] from best[i] (or the crown); labels = parents, weights, peaks counted
 //   jump_kernel         pointer doubling in place on the labels, launched by the host until a round changes nothing
+// With GIVEN weights (smafa_db_self_peaks_weighted_launch: the sizes of a store dereplicated elsewhere) one line changes — weight[i]
+// = w_in[i] + the sum of w_in[j] over the OTHER subjects within r — and the first two kernels take the weights as an argument:
+//   init_peaks_kernel   mode 2: weight[i] = w_in[i], and the sum of all w_in[] in one 8-byte total (one atomicAdd per wave)
+//   weigh_keep_kernel   w_in != nullptr: w_in[b] and w_in[a] in place of the two ones
+// The host checks that total against 2^32 - 1 before anything is weighed, so no weight can wrap; everything said below about
+// weight[] holds unchanged (atomicAdd of integers only, each pair presented once).  Both arguments default to nullptr: the
+// launches of the calls that count ones read as they did, and the kernels keep their names.
 //
 // Two phases, with a kernel boundary between them.  A key is known only once EVERY pair has been weighed, so no climb can
 // run while a weigh is still running: phase 1 is the whole join with weigh_keep_kernel per piece, phase 2 climbs.  Phase 2
@@ -64,9 +71,20 @@ __device__ __forceinline__ unsigned long long key_of(uint32_t weight, uint32_t i
 }
 
 // mode 0, in front of the join: weight[i] = w0.  mode 1, between the phases: best[i] = the row's own key (weight[] final).
+// mode 2, in front of the join of a call with given weights: weight[i] = w_in[i], and *total (zeroed by the host) += their sum,
+// reduced across the wave first — every lane of a wave reaches the reduction.
 __global__ __launch_bounds__(256) void init_peaks_kernel(unsigned long long *__restrict__ best, uint32_t *__restrict__ weight,
-                                                         uint32_t n, uint32_t w0, uint32_t mode) {
+                                                         uint32_t n, uint32_t w0, uint32_t mode,
+                                                         const uint32_t *__restrict__ w_in = nullptr, unsigned long long *total = nullptr) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (mode == 2u) {
+        uint32_t w = 0;
+        if (i < n) weight[i] = w = w_in[i];
+        unsigned long long sum = w;
+        for (int off = 32; off > 0; off >>= 1) sum += smafa::shfl_u64(sum, (int)((threadIdx.x & 63u) ^ (uint32_t)off));
+        if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(total, sum);
+        return;
+    }
     if (i < n) {
         if (mode == 0u)
             weight[i] = w0;
@@ -76,7 +94,8 @@ __global__ __launch_bounds__(256) void init_peaks_kernel(unsigned long long *__r
 }
 
 // A raw piece list under the exactly-once rule (piece.hip.h).  A kept row within the radius raises both weights; EVERY kept
-// row leaves as {a, b, dist} in subject numbers for the kept list through piece::block_append; rows past cap are counted in
+// row leaves as {a, b, dist} in subject numbers for the kept list through piece::block_append; with w_in the two weights are
+// raised by the OTHER row's given weight instead of 1; rows past cap are counted in
 // ctl[0] (the kept total, exact at any capacity; zeroed by the host once per call) and not stored.  The trip count of the
 // loop is uniform per workgroup, so the two barriers of an append are met by all four waves.
 __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__restrict__ list, unsigned long long total,
@@ -84,7 +103,7 @@ __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__rest
                                                          const uint32_t *__restrict__ order,
                                                          const uint32_t *__restrict__ pos_of, uint32_t *weight,
                                                          uint32_t radius, smafa_hit *kept, unsigned long long cap,
-                                                         unsigned long long *ctl) {
+                                                         unsigned long long *ctl, const uint32_t *__restrict__ w_in = nullptr) {
     __shared__ uint32_t s_wave[2][4];
     __shared__ unsigned long long s_first[2];
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
@@ -97,8 +116,8 @@ __global__ __launch_bounds__(256) void weigh_keep_kernel(const smafa_hit *__rest
             h = list[i];
             keep = piece::keep_once(h, p0, S, R, order, pos_of);
             if (keep && h.dist <= radius) {
-                atomicAdd(weight + h.query, 1u);
-                atomicAdd(weight + h.subject, 1u);
+                atomicAdd(weight + h.query, w_in ? w_in[h.subject] : 1u);
+                atomicAdd(weight + h.subject, w_in ? w_in[h.query] : 1u);
             }
         }
         const unsigned long long slot = piece::block_append(keep, ctl, 1u, s_wave, s_first, set);

@@ -711,6 +711,83 @@ static int join_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_t 
     return SMAFA_OK;
 }
 
+// smafa_db_self_peaks_weighted_launch: join_peaks with the caller's weights (peaks.hip.h) — a call of its own beside it, with the
+// same passes and the same kernels: init_peaks_kernel in mode 2 where it runs in mode 0 there, weigh_keep_kernel with the weights as
+// its last argument; keys, the kept list, the climb, the settle pass and the jump rounds are join_peaks's.  ctl[1] takes the sum of the weights, read
+// behind the seed launch: past 2^32 - 1 the call fails before anything is weighed.  A radius no two rows can exceed: every weight
+// is that sum (init_peaks_kernel, mode 0).
+// radius <= max_div; d_weights_in: n entries; d_parents, d_weights: n entries each, or nullptr
+static int join_peaks_weighted(smafa_db *db, const char *who, uint32_t max_div, uint32_t radius, const uint32_t *d_weights_in, uint32_t *d_labels,
+                               uint32_t *d_parents, uint32_t *d_weights, unsigned long long *d_count) {
+    auto &J = db->join;
+    const bool crowned = max_div >= db->L;
+    const uint32_t scan_div = crowned ? radius : max_div;
+    JoinCall c{db, db->n < 2 || scan_div >= db->L};
+    RC_TRY(join_begin(c, d_count, 1, 1));
+    if (c.nothing) return SMAFA_OK;
+    const uint32_t n = (uint32_t)db->n;
+    RC_TRY(J.parent.ensure((size_t)n * 3u * sizeof(uint32_t)));
+    RC_TRY(J.ctl.ensure(4 * sizeof(unsigned long long)));
+    unsigned long long *const best = J.parent.as<unsigned long long>();
+    uint32_t *const weight = J.parent.as<uint32_t>() + 2 * (size_t)n;
+    RC_TRY(timed_begin(c, &J.count_ms, "peaks: weight[] seeded"));
+    HIP_TRY(hipMemsetAsync(J.ctl.p, 0, 4 * sizeof(unsigned long long), db->stream));
+    hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, best, weight, n, 0u, 2u, d_weights_in,
+                       J.ctl.as<unsigned long long>() + 1);
+    RC_TRY(timed_end(c));
+    unsigned long long sum = 0;
+    HIP_TRY(hipMemcpyAsync(&sum, J.ctl.as<unsigned long long>() + 1, sizeof sum, hipMemcpyDeviceToHost, db->stream));
+    RC_TRY(timed_sync(c));
+    if (sum > 0xffffffffull) return set_error(SMAFA_ERR_INVALID, "%s: the weights sum to %llu, a weight holds at most 4294967295", who, sum);
+    if (scan_div >= db->L)  // every row within the radius of every other: every weight is the sum
+        RC_TRY(timed_pass(c, &J.count_ms, "peaks: weight[] initialised", [&] {
+            hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, best, weight, n, (uint32_t)sum, 0u);
+        }));
+    const auto launch_weigh = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_pk::weigh_keep_kernel, list_grid(p.count), dim3(256), 0,
+                           db->stream, p.list, p.count, p.p0, p.S, p.R, p.order, J.pos_of.as<uint32_t>(), weight, radius,
+                           J.kept.as<smafa_hit>(), crowned ? 0ull : (unsigned long long)kept_room(db), J.ctl.as<unsigned long long>(),
+                           d_weights_in);
+    };
+    const auto launch_climb = [&](const JoinPiece &p) {
+        hipLaunchKernelGGL(smafa_pk::climb_kernel, list_grid(p.count), dim3(256), 0, db->stream, p.list, p.count, p.p0, p.S, p.R, p.order,
+                           weight, best);
+    };
+    const char *const weighed = "peaks: a piece's rows weighed", *const climbed = "peaks: a piece's rows climbed";
+    JoinConsumer weigh = crowned ? timed_consumer(c, &J.count_ms, weighed, launch_weigh) : keeping_consumer(c, &J.count_ms, weighed, launch_weigh);
+    JoinConsumer climb = timed_consumer(c, &J.link_ms, climbed, launch_climb);
+    if (!c.no_scans) {
+        RC_TRY(join_positions(c));
+        RC_TRY(join_pass(c, scan_div, weigh));
+    }
+    unsigned long long kept_total = 0;
+    RC_TRY(read_ctl(c, &kept_total, 1));
+    const KeptPlan plan = crowned ? kKeptNothing : kept_plan(db, kept_total, "peaks", "climb");
+    RC_TRY(timed_begin(c, &J.link_ms, plan == kKeptOnce ? climbed : weigh.used ? weighed : "peaks: weight[] seeded"));
+    if (crowned)
+        hipLaunchKernelGGL(smafa_pk::crown_kernel, row_grid(n), dim3(256), 0, db->stream, weight, n, J.ctl.as<unsigned long long>() + 2);
+    else
+        hipLaunchKernelGGL(smafa_pk::init_peaks_kernel, row_grid(n), dim3(256), 0, db->stream, best, weight, n, 0u, 1u);
+    HIP_TRY(hipGetLastError());
+    climb.used = plan == kKeptOnce;
+    if (climb.used) launch_climb(kept_piece(db, kept_total));
+    RC_TRY(timed_end(c, climb.used ? 2u : 1u));
+    if (plan == kKeptJoinAgain) RC_TRY(join_pass(c, scan_div, climb));
+    RC_TRY(peaks_settle(c, crowned, climb.used, d_labels, d_parents, d_weights, d_count));
+    join_finish(c);
+    note_call_kernel(db, "smafa_pk::init_peaks_kernel");
+    if (weigh.used) note_call_kernel(db, "smafa_pk::weigh_keep_kernel");
+    if (climb.used) note_call_kernel(db, "smafa_pk::climb_kernel");
+    if (crowned) note_call_kernel(db, "smafa_pk::crown_kernel");
+    note_call_kernel(db, "smafa_pk::settle_kernel");
+    if (J.jump_rounds) note_call_kernel(db, "smafa_pk::jump_kernel");
+    log_line(2, "weighted peaks of %u rows at bound %u, radius %u: %u scans (%u of them repeats) in %u join%s, records %.3f ms, scans %.3f ms, "
+             "weigh/keep %.3f ms, climb %.3f ms, settle+jump %.3f ms in %u jump round%s, %llu pairs kept", n, max_div, radius, J.blocks + J.rescans,
+             J.rescans, J.joins, J.joins == 1 ? "" : "s", J.rec_ms, J.scan_ms, J.count_ms, J.link_ms, J.flatten_ms, J.jump_rounds,
+             J.jump_rounds == 1 ? "" : "s", kept_total);
+    return SMAFA_OK;
+}
+
 // smafa_db_self_chimeras_launch (chimera.hip.h): d_flags is n flags, d_count one counter, J.parent holds left[] and right[] (8 B
 // each per subject) and weight[] (4 B) behind them.  Phase 1 is the peaks call's: the join with smafa_pk::weigh_keep_kernel per
 // piece, which raises both weights of every kept pair within the radius and moves every kept pair to J.kept while that has room.

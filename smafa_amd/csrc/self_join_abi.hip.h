@@ -417,6 +417,50 @@ int smafa_db_self_peaks(smafa_db *db, uint32_t max_div, uint32_t radius, uint32_
     return smafa::exception_code("smafa_db_self_peaks");
 }
 
+// ---- peaks with given weights
+// behind self_args and radius_arg: the weights, unless the store is empty
+int smafa_db_self_peaks_weighted_launch(smafa_db *db, uint32_t max_div, uint32_t radius, const void *d_weights_in, void *d_labels, void *d_parents,
+                                        void *d_weights, void *d_n_peaks) try {
+    const char *const who = "smafa_db_self_peaks_weighted_launch";
+    RC_TRY(self_args(who, db, d_labels, "labels", d_n_peaks, "n_peaks", max_div, "peaks need a bound"));
+    RC_TRY(radius_arg(who, radius, max_div));
+    if (!d_weights_in && db->n) return missing(who, "weights_in");
+    return join_peaks_weighted(db, who, max_div, radius == SMAFA_NONE ? max_div : radius, (const uint32_t *)d_weights_in, (uint32_t *)d_labels,
+                               (uint32_t *)d_parents, (uint32_t *)d_weights, (unsigned long long *)d_n_peaks);
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_peaks_weighted_launch");
+}
+
+int smafa_db_self_peaks_weighted(smafa_db *db, uint32_t max_div, uint32_t radius, const uint32_t *weights_in, uint32_t *labels, uint32_t *parents,
+                                 uint32_t *weights, uint64_t cap, uint64_t *n_peaks) try {
+    const char *const who = "smafa_db_self_peaks_weighted";
+    RC_TRY(self_args(who, db, labels, "labels", n_peaks, "n_peaks", max_div, "peaks need a bound"));
+    RC_TRY(radius_arg(who, radius, max_div));
+    if (!weights_in && db->n) return missing(who, "weights_in");
+    RC_TRY(labels_cap_arg(who, db, cap));  // (nothing is written, the count included)
+    *n_peaks = 0;
+    const HostForm h{db};
+    auto &J = db->join;
+    const uint64_t n = db->n;
+    // the labels, the parents and weights behind them on their way to the caller, and the caller's weights on their way in
+    RC_TRY(h.stage(std::max<uint64_t>(n, 1) * 4u * sizeof(uint32_t), 1));
+    uint32_t *const d_labels = J.out.as<uint32_t>(), *const d_in = d_labels + 3 * n;
+    if (n) HIP_TRY(hipMemcpyAsync(d_in, weights_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, db->stream));
+    RC_TRY(join_peaks_weighted(db, who, max_div, radius == SMAFA_NONE ? max_div : radius, d_in, d_labels, parents ? d_labels + n : nullptr,
+                               weights ? d_labels + 2 * n : nullptr, h.cnt()));
+    unsigned long long count = 0;
+    RC_TRY(h.fetch(&count, h.cnt(), sizeof count));
+    RC_TRY(h.fetch(labels, d_labels, n * sizeof(uint32_t)));
+    RC_TRY(h.fetch(parents, d_labels + n, n * sizeof(uint32_t)));
+    RC_TRY(h.fetch(weights, d_labels + 2 * n, n * sizeof(uint32_t)));
+    RC_TRY(h.wait());
+    *n_peaks = count;
+    trim({&db->hits, &J.kept});
+    return SMAFA_OK;
+} catch (...) {
+    return smafa::exception_code("smafa_db_self_peaks_weighted");
+}
+
 // ---- chimeras
 // behind self_args: the radius, then the fold (nothing is written before they pass)
 static int chimera_args(const char *who, uint32_t radius, uint32_t max_div, uint32_t min_fold) {
