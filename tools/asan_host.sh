@@ -10,7 +10,7 @@ OUT=${OUT:-/tmp/asan}
 mkdir -p "$OUT"
 make -C "$ROOT/smafa_amd/csrc" -j8 >/dev/null
 cd "$ROOT/smafa_amd/csrc"
-for f in common group qsession inflate_other alphabet fastx dbfile select packed layout drivers; do
+for f in common group qsession inflate_other alphabet fastx dbfile select packed layout drivers store_verbs cluster; do
   g++ -O1 -g -std=c++17 -fPIC -pthread -fsanitize=address,undefined -fno-omit-frame-pointer -c host/$f.cpp -o "$OUT/$f.o"
 done
 g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -c host/main.cpp -o "$OUT/main.o"
